@@ -10,8 +10,12 @@ with no data-path collective); after the timed steps the per-pair best models ar
 with one RCCL all-gather over xGMI (inside the timed region).  Timing: barrier +
 device sync on both sides, max over ranks.
 
-Extra fields: roofline of the dominant kernel (k_f8_count) from HIP events on its stream,
-the numpy-exact parity mode measured on the same workload, and the oracle CPU baseline.
+A plain run sets up, warms up, times the steps and prints one JSON line: the headline and the
+roofline of the dominant kernel (k_f8_count32q) from HIP events on its stream inside the timed
+steps.  ``--dump-outputs DIR`` also writes what the last timed step returned (below).
+``--full`` adds everything measured in runs of its own: the oracle CPU baseline, the plain
+float64 counting kernel, the numpy-exact parity mode on the same workload, and the other
+BASELINE.json configs (``extras``); the ``--no-*`` options drop single legs of a full run.
 """
 import os
 
@@ -651,6 +655,25 @@ def load_clock():
         return None
 
 
+def dump_outputs(path, rank, r, inl, gathered):
+    """--dump-outputs: what plan.result() returned for the last timed step, as float64 .npy
+    files (a few kB): F (3, 3), inliers (S_RANSAC, the indices in order), record (RECORD_FIELDS)
+    and, at several GPUs, gathered (the all-gathered per-pair records, on rank 0).  Rank 0
+    writes the plain names, rank k > 0 writes <name>_rank<k>.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"F": np.array(r.F[:], np.float64).reshape(3, 3),
+              "inliers": np.asarray(inl, np.float64),
+              "record": np.array([getattr(r, k) for k in RECORD_FIELDS], np.float64)}
+    if gathered is not None and rank == 0:
+        arrays["gathered"] = np.array(gathered, np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+
+
+RECORD_FIELDS = ("best_index", "best_count", "best_std", "best_norm", "max_count_fast",
+                 "n_candidates", "guard_mismatch")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -658,6 +681,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--hyps", type=int, default=HYPS)
     ap.add_argument("--n", type=int, default=N_CORR)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline, the fp64 counting kernel, the parity "
+                         "mode and the extras (each in runs of its own, after the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-procs", type=int, default=0,
                     help="oracle worker processes (default: host_cores())")
@@ -670,6 +698,11 @@ def main():
     ap.add_argument("--harness-only", action="store_true",
                     help="launcher + TcpHub handshake only, no device (CPU test)")
     args = ap.parse_args()
+    # a plain run measures the headline only; every other leg belongs to --full
+    do_cpu = args.full and not args.no_cpu_baseline
+    do_fp64 = args.full and not args.no_fp64_count
+    do_parity = args.full and not args.no_parity_mode
+    do_extras = args.full and not args.no_extras
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no external launcher: this process becomes one, before any HIP call
@@ -684,7 +717,7 @@ def main():
             sys.exit(3)   # before the hub handshake: the other ranks would wait on it
         dist = Dist(world)
         cpu = None
-        if rank == 0 and not args.no_cpu_baseline:
+        if rank == 0 and do_cpu:
             cp1, cp2, _ = synth.two_view(args.n, OUTLIERS, seed=1)
             cpu = cpu_baseline(cp1, cp2, args.cpu_seconds, args.cpu_procs or host_cores()[0])
         harness_only(rank, world, dist, args, cpu)
@@ -692,7 +725,7 @@ def main():
         return
     dist = Dist(world)
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and do_cpu:
         # before any HIP call of this process: the worker processes are forked from it.  At
         # world > 1 the other ranks wait for rank 0 at the first hub exchange meanwhile (their
         # GPUs idle: nothing of the timed region overlaps the CPU baseline)
@@ -792,6 +825,9 @@ def main():
     el = time.perf_counter() - t0
     dist.barrier()
     el = dist.max(el)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, r, inl,
+                     out.reshape(world, 12) if comm else None)
     total_hyps = H * args.steps * world
     value = total_hyps / el
 
@@ -883,7 +919,7 @@ def main():
                                 "peak": PEAK_HBM_GBS, "unit": "GB/s",
                                 "frac": pmc / (c_ms * 1e-3) / 1e9 / PEAK_HBM_GBS}
 
-    if not args.no_fp64_count:
+    if do_fp64:
         # the plain float64 counting kernel on the same runs: the precision question settled
         # by measurement (identical counts; bounded by the FP64 vector peak)
         plan.set_count_precision(True)
@@ -907,7 +943,7 @@ def main():
                                       "(reference-order residuals); counts are bit-identical "
                                       "to the fp32 + exact-guard-band default"}
 
-    if not args.no_parity_mode:
+    if do_parity:
         # numpy-exact sampling + the same GPU pipeline: the np.random stream parsed on the
         # GPU (rs_f8_plan_run_np).  Weak: every rank its own pair's run.  Sharded: ONE pair's
         # H hypotheses split over the ranks (rs_f8_plan_run_np_slice + c* all-reduce and
@@ -1043,7 +1079,7 @@ def main():
         line["parity_mode"] = pm
     if cpu is not None:
         line["cpu_baseline"] = cpu
-    if not args.no_extras:
+    if do_extras:
         ex = extras(ctx, rank, world, dist, xcomm if comm else None)
         if rank == 0:
             line["extras"] = ex

@@ -1,5 +1,6 @@
 """bench.py's own rank launcher (``bench.py --gpus N`` with no torch.distributed.run) and the
-TcpHub harness, on the CPU: ``--harness-only`` never opens a device."""
+TcpHub harness, on the CPU: ``--harness-only`` never opens a device.  One GPU test runs a plain
+``bench.py`` with ``--dump-outputs``."""
 import json
 import os
 import subprocess
@@ -83,10 +84,38 @@ def test_rccl_failure_in_one_device_rehearsal_uses_the_hub():
 
 def test_cpu_baseline_is_reported_at_world_two():
     # rank 0 times the oracle before any HIP call also when the world has several ranks
-    p = _run(["--gpus", "2", "--harness-only", "--cpu-seconds", "0.6", "--cpu-procs", "2"])
+    p = _run(["--gpus", "2", "--harness-only", "--full", "--cpu-seconds", "0.6", "--cpu-procs",
+              "2"])
     assert p.returncode == 0, p.stderr
     cb = json.loads(p.stdout.strip())["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] == 2 and cb["value"] > 0
+
+
+def test_plain_run_leaves_the_cpu_baseline_to_full():
+    p = _run(["--gpus", "1", "--harness-only", "--cpu-seconds", "0.6", "--cpu-procs", "2"])
+    assert p.returncode == 0, p.stderr
+    assert "cpu_baseline" not in json.loads(p.stdout.strip())
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_step_and_repeats_it(tmp_path):
+    """A plain run prints the headline line without the --full legs, and --dump-outputs writes
+    what the last timed step returned; the same arguments give the same arrays."""
+    import numpy as np
+    got = []
+    for d in ("a", "b"):
+        p = _run(["--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs",
+                  str(tmp_path / d)])
+        assert p.returncode == 0, p.stderr
+        rec = json.loads(p.stdout.strip())
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["value"] > 0
+        assert not {"cpu_baseline", "fp64_count", "parity_mode", "extras"} & set(rec)
+        got.append({f.name: np.load(f) for f in sorted((tmp_path / d).iterdir())})
+    assert sorted(got[0]) == ["F.npy", "inliers.npy", "record.npy"]
+    for name, a in got[0].items():
+        assert a.dtype == np.float64 and np.array_equal(a, got[1][name]), name
+    assert got[0]["F.npy"].shape == (3, 3)
+    assert len(got[0]["inliers.npy"]) == got[0]["record.npy"][1] > 0   # best_count
 
 
 def test_under_torch_distributed_run_as_the_driver_launches_it():

@@ -14,5 +14,5 @@ for d in 0 8; do
   RSAMD_SOLVE_DIAG=$d timeout -k 10 120 python3 tools/solve_split.py >> $OUT/solve_split.txt 2>&1 || exit 1
 done
 cat $OUT/solve_split.txt
-timeout -k 10 200 python3 bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-extras > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
+timeout -k 10 200 python3 bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-extras > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
 python3 -c "import json;d=json.load(open('$OUT/bench.json'));print('value',d['value'],'ms',d['ms_per_step'],'count',d['kernels_ms'],'parity',d.get('parity_mode',{}).get('value'))"

@@ -12,9 +12,9 @@ export TMPDIR=/tmp
 cd $R
 timeout -k 10 300 python -u -m pytest tests/test_gpu_np_shard.py -x -q -k projection --timeout 120 --timeout-method thread > $OUT/pytest_proj.log 2>&1 || { echo projection test failed; tail -30 $OUT/pytest_proj.log; exit 1; }
 tail -3 $OUT/pytest_proj.log
-RSAMD_BENCH_DEVICE=0 timeout -k 10 400 python bench.py --gpus 2 --steps 20 --warmup 50 > $OUT/bench2.json 2> $OUT/bench2.err || { echo bench2 failed; tail -30 $OUT/bench2.err; exit 1; }
+RSAMD_BENCH_DEVICE=0 timeout -k 10 400 python bench.py --gpus 2 --full --steps 20 --warmup 50 > $OUT/bench2.json 2> $OUT/bench2.err || { echo bench2 failed; tail -30 $OUT/bench2.err; exit 1; }
 python -c "import json,sys; d=json.load(open('$OUT/bench2.json')); print('n_gpus', d['n_gpus'], d['config']['exchange'], d['value'])"
-timeout -k 10 500 python bench.py --steps 100 --warmup 200 > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; tail -30 $OUT/bench.err; exit 1; }
+timeout -k 10 500 python bench.py --full --steps 100 --warmup 200 > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; tail -30 $OUT/bench.err; exit 1; }
 python - <<EOF
 import json
 d = json.load(open("$OUT/bench.json"))

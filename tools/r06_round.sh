@@ -15,7 +15,7 @@ if [ "$2" != "skip-tests" ]; then
   [ $rc -eq 0 ] || exit 1
   timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo smoke failed; exit 1; }
 fi
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; tail $OUT/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; tail $OUT/bench.err; exit 1; }
 echo bench ok
 bash $R/tools/r06_traffic.sh $TAG/traffic > $OUT/traffic.log 2>&1 || { echo traffic failed; tail -20 $OUT/traffic.log; exit 1; }
 echo traffic ok

@@ -16,5 +16,5 @@ if [ -n "$2" ]; then  # E5 A/B: the product against lib_ab/$2
     echo -n "$2 "; RSAMD_LIB=$(pwd)/tsbb15-3d-reconstruction-project_amd/lib_ab/$2/librsamd.so timeout -k 10 120 python3 tools/probe_e5.py || exit 1
   done
 fi
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; tail $OUT/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; tail $OUT/bench.err; exit 1; }
 echo bench ok

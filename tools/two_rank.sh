@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/${1:-two}
 mkdir -p $OUT
 cd $R
-RSAMD_BENCH_DEVICE=0 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 20 > $OUT/bench2.json 2> $OUT/bench2.err
+RSAMD_BENCH_DEVICE=0 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --full --steps 20 --warmup 20 > $OUT/bench2.json 2> $OUT/bench2.err
 st=$?
 echo "rc=$st"
 [ $st -eq 0 ] || { tail -5 $OUT/bench2.err; exit 1; }
