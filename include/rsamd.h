@@ -1,10 +1,12 @@
 /*
- * rsamd.h -- C ABI of the MI355X-native RANSAC-F / PnP hot path.
+ * rsamd.h -- C ABI of the MI355X-native RANSAC-F / PnP hot path and of the bundle adjustment
+ * that follows it (rs_bundle_adjust: Tables.BundleAdjustment2 as a Schur-complement
+ * Levenberg-Marquardt on the GPU).
  *
  * Drop-in boundary for bioengstrom/tsbb15-3d-reconstruction-project (snapshot v0).  The
  * reference has no FFI: its boundary is the Python module surface.  Each
  * entry point below names the reference function it replaces; the Python shims in
- * tsbb15_amd/ (lab3.py, fun.py, ransac.py, pnp.py, cv.py) bind these through ctypes with the
+ * tsbb15_amd/ (lab3.py, fun.py, ransac.py, pnp.py, cv.py, tables.py) bind these through ctypes with the
  * reference's names, argument meaning and ValueError behaviour.
  *
  * Conventions
@@ -512,6 +514,44 @@ int rs_ba_residuals(rs_ctx *ctx, const double *cams, int64_t nC, const double *p
 int rs_ba_jacobian(rs_ctx *ctx, const double *cams, int64_t nC, const double *pts, int64_t nP,
                    const int32_t *obs_view, const int32_t *obs_point, int64_t n, double *Jc,
                    double *Jp);
+
+/* Tables.BundleAdjustment2 (tables.py:260-338): the objective of rs_ba_residuals minimised over
+ * the cameras (12 free parameters each, camera 0 never touched) and the points by
+ * Levenberg-Marquardt, fp64 throughout, the points eliminated by a Schur complement and the
+ * reduced camera system solved by Cholesky on the GPU.  cams (nC, 3, 4) and pts (nP, 3) are
+ * refined in place.  The rules are those of oracle/tables_ref.bundle_adjust_lm:
+ *   - lam = 1e-3, nu = 2 at the start; V* = V + lam diag(V), U* = U + lam diag(U);
+ *   - a trial is accepted iff cost_new < cost and the predicted reduction is > 0; then
+ *     lam *= max(1/3, 1 - (2 rho - 1)^3), nu = 2; otherwise lam *= nu, nu *= 2;
+ *   - a trial with a non-positive Cholesky pivot or a non-finite cost is a rejected trial;
+ *   - status 1: an accepted step gained <= ftol * cost; 2: lam > 1e32; 0: max_iter
+ *     linearisations done.
+ * Cameras and points without an observation come back bit for bit unchanged and stay out of the
+ * linear system; nC == 1 refines the points only.  RS_EINVAL: an index out of range, n == 0, a
+ * non-finite initial cost, nC > RS_BA_MAX_CAMERAS, n > 2^24, or more than 2^27 pairs of
+ * observations that share a point between two free cameras.  The same inputs give bitwise the
+ * same outputs (no floating-point atomics; every sum in a fixed order). */
+#define RS_BA_MAX_CAMERAS 128   /* reduced system up to 1524 x 1524 */
+
+typedef struct rs_ba_info {
+  double cost_init;       /* 0.5 |r|^2 at the start                                        */
+  double cost;            /* 0.5 |r|^2 at the end                                          */
+  double lambda;          /* the damping after the last trial                              */
+  int32_t iterations;     /* linearisations                                                */
+  int32_t rejected;       /* rejected trials                                               */
+  int32_t status;         /* 0 max_iter, 1 converged (ftol), 2 lam > 1e32                  */
+  int32_t reserved;
+} rs_ba_info;             /* 40 bytes */
+
+int rs_bundle_adjust(rs_ctx *ctx, double *cams, int64_t nC, double *pts, int64_t nP,
+                     const int32_t *obs_view, const int32_t *obs_point, const double *uv,
+                     int64_t n, int32_t max_iter, double ftol, rs_ba_info *info);
+
+/* HIP events between the kernels of the next rs_bundle_adjust calls (enable != 0).  Returns the
+ * last timed call's device ms summed per kernel -- k_ba_linearize, k_ba_camera, k_ba_pointsum,
+ * k_ba_point, k_ba_schur, k_ba_chol, k_ba_step, k_ba_cost + k_ba_final -- and its trials. */
+#define RS_BA_TIMING_SLOTS 8
+int rs_ba_timing(rs_ctx *ctx, int32_t enable, double *ms, int64_t *trials);
 
 /* ------------------------------------------------------------------------------------------
  * Multi-GPU (RCCL over xGMI).  One process per GPU; the unique id travels out of band.

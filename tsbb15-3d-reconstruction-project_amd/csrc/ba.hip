@@ -1,0 +1,882 @@
+// Bundle adjustment on the GPU: Tables.BundleAdjustment2 (tables.py:260-338) minimised by the
+// Levenberg-Marquardt of oracle/tables_ref.bundle_adjust_lm -- Marquardt diagonal damping,
+// Nielsen update, points eliminated by a Schur complement, camera 0 fixed.  All fp64.
+//
+// The problem is uploaded once and stays on the device for the whole call; the host runs the LM
+// loop and reads one small record (trial cost, predicted reduction, failure flag) from pinned
+// host memory per trial.  Every sum is taken in a fixed order over a CSR row or by a fixed tree,
+// no floating-point atomics: the same inputs give bitwise the same outputs.
+//
+// per linearisation
+//   k_ba_linearize   lane per observation: r, the Jacobian blocks and W_i = Jc^T Jp (12x3).
+//                    Jc is stored as its 6 generators (xh / w, a / w, b / w), not 2x12 dense
+//   k_ba_camera      workgroup per free camera: U_c (12x12), g_c over its CSR row
+//   k_ba_pointsum    lane per point: V_p (3x3 symmetric), g_p over its CSR row
+// per trial (U, V, W, g are reused across rejected trials, as the oracle reuses them)
+//   k_ba_point       lane per observation: (V + lam diag V)^-1 of its point, Y_i = W_i V*^-1
+//   k_ba_schur       workgroup per camera block pair a <= b (free cameras):
+//                    S_ab = [a == b] U*_a - sum_p Y_{a,p} W_{b,p}^T, and the right-hand side
+//   k_ba_chol        one workgroup: left-looking blocked Cholesky of S, 12-wide block columns,
+//                    the matrix in global memory / L2 and a tile of the panel in LDS; the
+//                    right-hand side rides along as one more row (forward solve), then the
+//                    backward solve.  Raises the flag on a non-positive pivot
+//   k_ba_step        lane per point: dx_p by back-substitution, trial points and cameras, the
+//                    point's share of the predicted reduction
+//   k_ba_cost        lane per observation: squared trial residual
+//   k_ba_final       one workgroup: cost and predicted reduction by fixed-order reductions,
+//                    the status record into pinned host memory
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <utility>
+#include <vector>
+
+#include "common.h"
+#include "ctx.h"
+
+namespace rsd {
+
+constexpr int kBaCamTile = 256;        // observations of a camera row per LDS tile (16 KiB)
+constexpr int kBaSchurTile = 32;       // observation pairs per LDS tile (2 x 9 KiB)
+constexpr int kBaCholThreads = 512;
+constexpr int kBaCholRows = 2;         // rows of the panel a thread updates per pass
+constexpr int kBaCholBatch = 12;       // columns whose L entries are in flight together
+constexpr int kBaCholTile = 240;        // columns of the panel tile in LDS (x 12 rows); a multiple of 12
+constexpr int kBaMaxFree = RS_BA_MAX_CAMERAS;  // ys[] of k_ba_chol: 12 * kBaMaxFree doubles
+constexpr int kBaFinalThreads = 1024;
+
+// Row `row` (0: u, 1: v) of Jc at camera entry k, from g = xh / w (4), aw = a / w, bw = b / w:
+// Jc[0] = [-g, 0, g aw], Jc[1] = [0, -g, g bw].
+__device__ __forceinline__ double ba_jc(const double *j6, int row, int k) {
+  const int grp = k >> 2;
+  const double g = j6[k & 3];
+  if (grp == 2) return g * j6[4 + row];
+  return grp == row ? -g : 0.0;
+}
+
+// v of lane `lane` (wave-uniform) in every lane.
+__device__ __forceinline__ double ba_bcast(double v, int lane) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
+  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+  return __hiloint2double(hi, lo);
+}
+
+// Inverse of the damped V* = V + lam diag(V) (V symmetric as 00 01 02 11 12 22) through its
+// Cholesky factor.  False on a non-positive (or NaN) pivot.
+__device__ __forceinline__ bool ba_inv3(const double *V, double lam, double *Vi) {
+  const double a00 = V[0] + lam * V[0], a11 = V[3] + lam * V[3], a22 = V[5] + lam * V[5];
+  const double a10 = V[1], a20 = V[2], a21 = V[4];
+  bool ok = a00 > 0.0;
+  const double l00 = sqrt(a00);
+  const double l10 = a10 / l00, l20 = a20 / l00;
+  const double d1 = a11 - l10 * l10;
+  ok = ok && d1 > 0.0;
+  const double l11 = sqrt(d1);
+  const double l21 = (a21 - l20 * l10) / l11;
+  const double d2 = a22 - l20 * l20 - l21 * l21;
+  ok = ok && d2 > 0.0;
+  const double l22 = sqrt(d2);
+  // M = L^-1 (lower), V*^-1 = M^T M
+  const double m00 = 1.0 / l00, m11 = 1.0 / l11, m22 = 1.0 / l22;
+  const double m10 = -l10 * m00 * m11;
+  const double m21 = -l21 * m11 * m22;
+  const double m20 = -(l20 * m00 + l21 * m10) * m22;
+  Vi[0] = m00 * m00 + m10 * m10 + m20 * m20;
+  Vi[1] = m10 * m11 + m20 * m21;
+  Vi[2] = m20 * m22;
+  Vi[3] = m11 * m11 + m21 * m21;
+  Vi[4] = m21 * m22;
+  Vi[5] = m22 * m22;
+  return ok;
+}
+
+__global__ __launch_bounds__(256) void k_ba_linearize(
+    const double *__restrict__ cams, const double *__restrict__ pts,
+    const int32_t *__restrict__ ov, const int32_t *__restrict__ op,
+    const double *__restrict__ uv, int n, double *__restrict__ r, double *__restrict__ jcs,
+    double *__restrict__ Jp, double *__restrict__ W) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double *c = cams + 12 * ov[i];
+  const double *p = pts + 3 * op[i];
+  const double xh[4] = {p[0], p[1], p[2], 1.0};
+  const double a = c[0] * xh[0] + c[1] * xh[1] + c[2] * xh[2] + c[3];
+  const double b = c[4] * xh[0] + c[5] * xh[1] + c[6] * xh[2] + c[7];
+  const double w = c[8] * xh[0] + c[9] * xh[1] + c[10] * xh[2] + c[11];
+  const double iw = 1.0 / w, iw2 = iw * iw;
+  const double aw = a / w, bw = b / w;
+  r[2 * i] = uv[2 * i] - aw;
+  r[2 * i + 1] = uv[2 * i + 1] - bw;
+  double g[4], j0[3], j1[3];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) g[k] = xh[k] / w;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    j0[k] = -(c[k] * w - a * c[8 + k]) * iw2;
+    j1[k] = -(c[4 + k] * w - b * c[8 + k]) * iw2;
+  }
+  double *j6 = jcs + 6 * static_cast<int64_t>(i);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) j6[k] = g[k];
+  j6[4] = aw;
+  j6[5] = bw;
+  double *jp = Jp + 6 * static_cast<int64_t>(i);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    jp[k] = j0[k];
+    jp[3 + k] = j1[k];
+  }
+  // W = Jc^T Jp: rows 0-3 = -g_k Jp[0], rows 4-7 = -g_k Jp[1], rows 8-11 = g_k (aw Jp[0] + bw Jp[1])
+  double *wi = W + 36 * static_cast<int64_t>(i);
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      wi[3 * k + q] = -g[k] * j0[q];
+      wi[3 * (4 + k) + q] = -g[k] * j1[q];
+      wi[3 * (8 + k) + q] = (g[k] * aw) * j0[q] + (g[k] * bw) * j1[q];
+    }
+}
+
+// U_c = sum Jc^T Jc and g_c = sum Jc^T r over the camera's observations, in CSR order.  The
+// row is staged through LDS in tiles (generators and residual of each observation, gathered
+// by all threads); every thread then walks the tile in order for its own entry.
+__global__ __launch_bounds__(192) void k_ba_camera(
+    const int32_t *__restrict__ cam_of_slot, const int32_t *__restrict__ cam_off,
+    const int32_t *__restrict__ cam_obs, const double *__restrict__ jcs,
+    const double *__restrict__ r, double *__restrict__ U, double *__restrict__ gc) {
+  __shared__ double sj[kBaCamTile * 8];
+  const int slot = blockIdx.x, tid = threadIdx.x;
+  const int cam = cam_of_slot[slot];
+  const int lo = cam_off[slot], hi = cam_off[slot + 1];
+  const int rr = tid < 144 ? tid / 12 : tid - 144, cc = tid % 12;
+  double s = 0.0;
+  for (int base = lo; base < hi; base += kBaCamTile) {
+    const int cnt = min(kBaCamTile, hi - base);
+    __syncthreads();
+    for (int idx = tid; idx < cnt * 8; idx += 192) {
+      const int64_t i = cam_obs[base + idx / 8];
+      const int f = idx % 8;
+      sj[idx] = f < 6 ? jcs[6 * i + f] : r[2 * i + f - 6];
+    }
+    __syncthreads();
+    if (tid < 144) {
+      for (int o = 0; o < cnt; ++o) {
+        const double *j6 = sj + 8 * o;
+        s += ba_jc(j6, 0, rr) * ba_jc(j6, 0, cc) + ba_jc(j6, 1, rr) * ba_jc(j6, 1, cc);
+      }
+    } else if (tid < 156) {
+      for (int o = 0; o < cnt; ++o) {
+        const double *j6 = sj + 8 * o;
+        s += ba_jc(j6, 0, rr) * j6[6] + ba_jc(j6, 1, rr) * j6[7];
+      }
+    }
+  }
+  if (tid < 144)
+    U[144 * cam + tid] = s;
+  else if (tid < 156)
+    gc[12 * cam + rr] = s;
+}
+
+// V_p = sum Jp^T Jp (00 01 02 11 12 22) and g_p = sum Jp^T r over the point's observations.
+__global__ __launch_bounds__(256) void k_ba_pointsum(
+    const int32_t *__restrict__ pt_off, const int32_t *__restrict__ pt_obs, int nP,
+    const double *__restrict__ Jp, const double *__restrict__ r, double *__restrict__ V,
+    double *__restrict__ gp) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= nP) return;
+  double v[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
+  for (int o = pt_off[p]; o < pt_off[p + 1]; ++o) {
+    const int64_t i = pt_obs[o];
+    const double *j = Jp + 6 * i;
+    const double r0 = r[2 * i], r1 = r[2 * i + 1];
+    v[0] += j[0] * j[0] + j[3] * j[3];
+    v[1] += j[0] * j[1] + j[3] * j[4];
+    v[2] += j[0] * j[2] + j[3] * j[5];
+    v[3] += j[1] * j[1] + j[4] * j[4];
+    v[4] += j[1] * j[2] + j[4] * j[5];
+    v[5] += j[2] * j[2] + j[5] * j[5];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) g[q] += j[q] * r0 + j[3 + q] * r1;
+  }
+#pragma unroll
+  for (int q = 0; q < 6; ++q) V[6 * static_cast<int64_t>(p) + q] = v[q];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) gp[3 * static_cast<int64_t>(p) + q] = g[q];
+}
+
+// Y_i = W_i V*^-1 of the observation's point; the first observation of each point also keeps
+// V*^-1 for k_ba_step and reports a non-positive pivot.
+__global__ __launch_bounds__(256) void k_ba_point(
+    const int32_t *__restrict__ op, const int32_t *__restrict__ pt_off,
+    const int32_t *__restrict__ pt_obs, int n, const double *__restrict__ V, double lam,
+    const double *__restrict__ W, double *__restrict__ Y, double *__restrict__ Vinv,
+    int32_t *__restrict__ flag) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t p = op[i];
+  double vi[6];
+  const bool ok = ba_inv3(V + 6 * p, lam, vi);
+  if (pt_obs[pt_off[p]] == i) {
+#pragma unroll
+    for (int q = 0; q < 6; ++q) Vinv[6 * p + q] = vi[q];
+    if (!ok) flag[0] = 1;
+  }
+  const double *w = W + 36 * static_cast<int64_t>(i);
+  double *y = Y + 36 * static_cast<int64_t>(i);
+#pragma unroll
+  for (int k = 0; k < 12; ++k) {
+    const double w0 = w[3 * k], w1 = w[3 * k + 1], w2 = w[3 * k + 2];
+    y[3 * k] = w0 * vi[0] + w1 * vi[1] + w2 * vi[2];
+    y[3 * k + 1] = w0 * vi[1] + w1 * vi[3] + w2 * vi[4];
+    y[3 * k + 2] = w0 * vi[2] + w1 * vi[4] + w2 * vi[5];
+  }
+}
+
+// The reduced system, lower triangle, element (i, m), i >= m, at S[m * ld + i]; row N (ld =
+// N + 1) is the right-hand side -g_c + sum_i Y_i g_p.  Block pair `blockIdx.x` in the order
+// (0,0) (0,1) .. (0,nf-1) (1,1) ..; its (i, j) observation pairs ent[pair_off[.] ..] are sorted
+// by point.
+__global__ __launch_bounds__(192) void k_ba_schur(
+    int nf, const int64_t *__restrict__ pair_off, const int32_t *__restrict__ ent,
+    const double *__restrict__ Y, const double *__restrict__ W, const double *__restrict__ U,
+    const double *__restrict__ gc, const double *__restrict__ gp,
+    const int32_t *__restrict__ op, const int32_t *__restrict__ cam_of_slot,
+    const int32_t *__restrict__ cam_off, const int32_t *__restrict__ cam_obs, double lam,
+    double *__restrict__ S, int ld) {
+  int a = 0, rest = blockIdx.x;
+  while (rest >= nf - a) {
+    rest -= nf - a;
+    ++a;
+  }
+  const int b = a + rest, tid = threadIdx.x;
+  const int N = ld - 1;
+  __shared__ double sy[kBaSchurTile * 36], sw[kBaSchurTile * 36];
+  const int rr = tid / 12, cc = tid % 12;
+  double s = 0.0;
+  const int64_t lo = pair_off[blockIdx.x], hi = pair_off[blockIdx.x + 1];
+  for (int64_t e0 = lo; e0 < hi; e0 += kBaSchurTile) {
+    const int cnt = static_cast<int>(hi - e0 < kBaSchurTile ? hi - e0 : kBaSchurTile);
+    __syncthreads();
+    for (int idx = tid; idx < cnt * 36; idx += 192) {
+      const int64_t e = e0 + idx / 36;
+      const int f = idx % 36;
+      sy[idx] = Y[36 * static_cast<int64_t>(ent[2 * e]) + f];
+      sw[idx] = W[36 * static_cast<int64_t>(ent[2 * e + 1]) + f];
+    }
+    __syncthreads();
+    if (tid < 144) {
+      for (int e = 0; e < cnt; ++e) {
+        const double *y = sy + 36 * e + 3 * rr;
+        const double *w = sw + 36 * e + 3 * cc;
+        s += y[0] * w[0] + y[1] * w[1] + y[2] * w[2];
+      }
+    }
+  }
+  if (tid < 144) {
+    double u = 0.0;
+    if (a == b) {
+      u = U[144 * cam_of_slot[a] + tid];
+      if (rr == cc) u += lam * u;
+    }
+    // element (12a + rr, 12b + cc) = element (12b + cc, 12a + rr) of the lower triangle
+    S[static_cast<int64_t>(12 * a + rr) * ld + 12 * b + cc] = u - s;
+  }
+  if (a != b) return;
+  // right-hand side of block row a: the camera's row staged the same way (Y_i, g_p of its point)
+  const int k = tid - 144;
+  double t = tid >= 144 && tid < 156 ? -gc[12 * cam_of_slot[a] + k] : 0.0;
+  for (int o0 = cam_off[a]; o0 < cam_off[a + 1]; o0 += kBaSchurTile) {
+    const int cnt = min(kBaSchurTile, cam_off[a + 1] - o0);
+    __syncthreads();
+    for (int idx = tid; idx < cnt * 36; idx += 192)
+      sy[idx] = Y[36 * static_cast<int64_t>(cam_obs[o0 + idx / 36]) + idx % 36];
+    for (int idx = tid; idx < cnt * 3; idx += 192)
+      sw[idx] = gp[3 * static_cast<int64_t>(op[cam_obs[o0 + idx / 3]]) + idx % 3];
+    __syncthreads();
+    if (tid >= 144 && tid < 156) {
+      for (int o = 0; o < cnt; ++o) {
+        const double *y = sy + 36 * o + 3 * k;
+        const double *g = sw + 3 * o;
+        t += y[0] * g[0] + y[1] * g[1] + y[2] * g[2];
+      }
+    }
+  }
+  if (tid >= 144 && tid < 156) S[static_cast<int64_t>(12 * a + k) * ld + N] = t;
+}
+
+// Cholesky of S (N = 12 nf) and both triangular solves in one workgroup.  Left-looking by 12-wide
+// block columns: for block column k every row i >= 12k gets A[i, 12k..] -= L[i, :12k] L[12k.., :12k]^T
+// with the 12 x 12k factor rows in an LDS tile and kBaCholRows rows of the panel per thread, the
+// L entries of kBaCholBatch columns requested together (DESIGN.md section 10 has the measured
+// alternatives); then the diagonal block is
+// factorised in the first wave's registers and the rows below are solved against it.  The right-hand
+// side is row N of the matrix, so the factorisation leaves y = L^-1 rhs there.  dc (nC, 12) gets
+// the camera steps (rows of cameras outside the system stay zero); on a non-positive pivot it
+// gets zeros and the flag.
+__global__ __launch_bounds__(kBaCholThreads) void k_ba_chol(
+    double *__restrict__ S, int N, const int32_t *__restrict__ cam_of_slot,
+    double *__restrict__ dc, int32_t *__restrict__ flag) {
+  __shared__ double Ts[kBaCholTile * 12];
+  __shared__ double D[144];
+  __shared__ double ys[12 * kBaMaxFree];
+  __shared__ int bad;
+  const int tid = threadIdx.x, ld = N + 1, R = N + 1, nb = N / 12;
+  if (tid == 0) bad = 0;
+  __syncthreads();
+  for (int k = 0; k < nb; ++k) {
+    const int c0 = 12 * k;
+    for (int m0 = 0; m0 < c0; m0 += kBaCholTile) {
+      const int mc = min(kBaCholTile, c0 - m0);
+      __syncthreads();
+      for (int idx = tid; idx < mc * 12; idx += kBaCholThreads)
+        Ts[idx] = S[static_cast<int64_t>(m0 + idx / 12) * ld + c0 + idx % 12];
+      __syncthreads();
+      for (int base = c0; base < R; base += kBaCholThreads * kBaCholRows) {
+        // rows base + q * blockDim + tid, q < nq (uniform); a lane past the last row works on
+        // row R - 1 and stores nothing
+        const int nq = min(kBaCholRows, (R - base + kBaCholThreads - 1) / kBaCholThreads);
+        double acc[kBaCholRows][12];
+        int row[kBaCholRows];
+#pragma unroll
+        for (int q = 0; q < kBaCholRows; ++q) {
+          row[q] = min(base + q * kBaCholThreads + tid, R - 1);
+          if (q < nq) {
+#pragma unroll
+            for (int c = 0; c < 12; ++c) acc[q][c] = S[static_cast<int64_t>(c0 + c) * ld + row[q]];
+          }
+        }
+        // kBaCholBatch columns at a time: their L entries are all requested before the first is
+        // used (one memory latency per batch, not per column); mc is a multiple of 12
+        for (int m = 0; m < mc; m += kBaCholBatch) {
+          double l[kBaCholBatch][kBaCholRows];
+#pragma unroll
+          for (int j = 0; j < kBaCholBatch; ++j)
+#pragma unroll
+            for (int q = 0; q < kBaCholRows; ++q)
+              l[j][q] = q < nq ? S[static_cast<int64_t>(m0 + m + j) * ld + row[q]] : 0.0;
+#pragma unroll
+          for (int j = 0; j < kBaCholBatch; ++j)
+#pragma unroll
+            for (int c = 0; c < 12; ++c) {
+              const double t = Ts[12 * (m + j) + c];
+#pragma unroll
+              for (int q = 0; q < kBaCholRows; ++q)
+                if (q < nq) acc[q][c] -= l[j][q] * t;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < kBaCholRows; ++q)
+          if (q < nq && base + q * kBaCholThreads + tid < R) {
+#pragma unroll
+            for (int c = 0; c < 12; ++c) S[static_cast<int64_t>(c0 + c) * ld + row[q]] = acc[q][c];
+          }
+      }
+    }
+    __syncthreads();
+    if (tid < 144) D[tid] = S[static_cast<int64_t>(c0 + tid % 12) * ld + c0 + tid / 12];
+    __syncthreads();
+    if (tid < 64) {
+      // the 12 x 12 factor in the first wave, lane i holding row i in registers (right-looking;
+      // L[c][j] travels from lane c by v_readlane).  A bad pivot poisons the rest with NaN and
+      // is reported, not branched on
+      double a[12];
+#pragma unroll
+      for (int c = 0; c < 12; ++c) a[c] = tid < 12 ? D[12 * tid + c] : 1.0;
+      bool ok = true;
+#pragma unroll
+      for (int j = 0; j < 12; ++j) {
+        const double d = ba_bcast(a[j], j);
+        ok = ok && d > 0.0;
+        const double root = sqrt(d), inv = 1.0 / root;
+        a[j] = tid == j ? root : a[j] * inv;
+#pragma unroll
+        for (int c = j + 1; c < 12; ++c) a[c] -= a[j] * ba_bcast(a[j], c);
+      }
+      if (tid < 12) {
+#pragma unroll
+        for (int c = 0; c < 12; ++c)
+          if (c <= tid) D[12 * tid + c] = a[c];
+      }
+      if (tid == 0 && !ok) bad = 1;
+    }
+    __syncthreads();
+    if (bad) break;
+    for (int i = c0 + 12 + tid; i < R; i += kBaCholThreads) {
+      // keep the 78 reads of D inside the loop: hoisted, they would sit in 156 VGPRs
+      asm volatile("" ::: "memory");
+      double x[12];
+#pragma unroll
+      for (int c = 0; c < 12; ++c) {
+        double s = S[static_cast<int64_t>(c0 + c) * ld + i];
+#pragma unroll
+        for (int t = 0; t < c; ++t) s -= x[t] * D[12 * c + t];
+        x[c] = s / D[13 * c];
+      }
+#pragma unroll
+      for (int c = 0; c < 12; ++c) S[static_cast<int64_t>(c0 + c) * ld + i] = x[c];
+    }
+    if (tid < 144 && tid % 12 <= tid / 12)
+      S[static_cast<int64_t>(c0 + tid % 12) * ld + c0 + tid / 12] = D[tid];
+  }
+  __syncthreads();
+  if (bad) {
+    for (int idx = tid; idx < N; idx += kBaCholThreads)
+      dc[12 * cam_of_slot[idx / 12] + idx % 12] = 0.0;
+    if (tid == 0) flag[0] = 1;
+    return;
+  }
+  // backward solve L^T x = y, block rows from the last
+  for (int idx = tid; idx < N; idx += kBaCholThreads)
+    ys[idx] = S[static_cast<int64_t>(idx) * ld + N];
+  for (int k = nb - 1; k >= 0; --k) {
+    const int c0 = 12 * k;
+    if (tid < 144 && tid % 12 <= tid / 12)
+      D[tid] = S[static_cast<int64_t>(c0 + tid % 12) * ld + c0 + tid / 12];
+    __syncthreads();
+    if (tid == 0) {
+      for (int c = 11; c >= 0; --c) {
+        double s = ys[c0 + c];
+        for (int t = c + 1; t < 12; ++t) s -= D[12 * t + c] * ys[c0 + t];
+        ys[c0 + c] = s / D[13 * c];
+      }
+    }
+    __syncthreads();
+    for (int i = tid; i < c0; i += kBaCholThreads) {
+      const double *l = S + static_cast<int64_t>(i) * ld + c0;
+      double s = ys[i];
+#pragma unroll
+      for (int c = 0; c < 12; ++c) s -= l[c] * ys[c0 + c];
+      ys[i] = s;
+    }
+  }
+  __syncthreads();
+  for (int idx = tid; idx < N; idx += kBaCholThreads)
+    dc[12 * cam_of_slot[idx / 12] + idx % 12] = ys[idx];
+}
+
+// Lanes [0, nP): dx_p = -V*^-1 (g_p + sum_i W_i^T dc_cam(i)), the trial point, and the point's
+// share lam dx^T diag(V) dx - dx^T g_p of the predicted reduction.  Lanes [0, 12 nC) also form
+// the trial cameras.  A point without observations and a camera outside the system are copied.
+__global__ __launch_bounds__(256) void k_ba_step(
+    const int32_t *__restrict__ pt_off, const int32_t *__restrict__ pt_obs,
+    const int32_t *__restrict__ ov, int nP, int nC, const int32_t *__restrict__ slot_of_cam,
+    const double *__restrict__ W, const double *__restrict__ V, const double *__restrict__ Vinv,
+    const double *__restrict__ gp, const double *__restrict__ dc, double lam,
+    const double *__restrict__ cams, const double *__restrict__ pts,
+    double *__restrict__ cams_n, double *__restrict__ pts_n, double *__restrict__ ppred) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < 12 * nC) cams_n[t] = slot_of_cam[t / 12] >= 0 ? cams[t] + dc[t] : cams[t];
+  if (t >= nP) return;
+  const int64_t p = t;
+  const int lo = pt_off[p], hi = pt_off[p + 1];
+  if (lo == hi) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) pts_n[3 * p + q] = pts[3 * p + q];
+    ppred[p] = 0.0;
+    return;
+  }
+  double g[3] = {gp[3 * p], gp[3 * p + 1], gp[3 * p + 2]};
+  for (int o = lo; o < hi; ++o) {
+    const int64_t i = pt_obs[o];
+    const double *w = W + 36 * i;
+    const double *d = dc + 12 * ov[i];
+#pragma unroll
+    for (int k = 0; k < 12; ++k)
+#pragma unroll
+      for (int q = 0; q < 3; ++q) g[q] += w[3 * k + q] * d[k];
+  }
+  const double *vi = Vinv + 6 * p;
+  const double dx[3] = {-(vi[0] * g[0] + vi[1] * g[1] + vi[2] * g[2]),
+                        -(vi[1] * g[0] + vi[3] * g[1] + vi[4] * g[2]),
+                        -(vi[2] * g[0] + vi[4] * g[1] + vi[5] * g[2])};
+  const double dv[3] = {V[6 * p], V[6 * p + 3], V[6 * p + 5]};
+  double s = 0.0;
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    pts_n[3 * p + q] = pts[3 * p + q] + dx[q];
+    s += lam * dx[q] * dv[q] * dx[q] - dx[q] * gp[3 * p + q];
+  }
+  ppred[p] = s;
+}
+
+__global__ __launch_bounds__(256) void k_ba_cost(
+    const double *__restrict__ cams, const double *__restrict__ pts,
+    const int32_t *__restrict__ ov, const int32_t *__restrict__ op,
+    const double *__restrict__ uv, int n, double *__restrict__ e) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double *c = cams + 12 * ov[i];
+  const double *p = pts + 3 * static_cast<int64_t>(op[i]);
+  const double x0 = p[0], x1 = p[1], x2 = p[2];
+  const double a = c[0] * x0 + c[1] * x1 + c[2] * x2 + c[3];
+  const double b = c[4] * x0 + c[5] * x1 + c[6] * x2 + c[7];
+  const double w = c[8] * x0 + c[9] * x1 + c[10] * x2 + c[11];
+  const double ru = uv[2 * i] - a / w, rv = uv[2 * i + 1] - b / w;
+  e[i] = ru * ru + rv * rv;
+}
+
+// Sum over the workgroup in a fixed order: each thread's strided partial, then a binary tree.
+__device__ __forceinline__ double ba_block_sum(double v, double *sh) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  sh[tid] = v;
+  __syncthreads();
+  for (int s = kBaFinalThreads / 2; s > 0; s >>= 1) {
+    if (tid < s) sh[tid] += sh[tid + s];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+// rec (pinned host memory): [0] cost = 0.5 sum e, [1] predicted reduction
+// 0.5 (lam (dc^T diag(U) dc + dx^T diag(V) dx) - dc^T g_c - dx^T g_p), [2] the failure flag
+// (cleared here for the next trial), [3] the trial's serial number.  nP = nC = 0: cost only.
+__global__ __launch_bounds__(kBaFinalThreads) void k_ba_final(
+    const double *__restrict__ e, int n, const double *__restrict__ ppred, int nP,
+    const double *__restrict__ dc, const double *__restrict__ U, const double *__restrict__ gc,
+    int nC, double lam, int32_t *__restrict__ flag, double serial, double *__restrict__ rec) {
+  __shared__ double sh[kBaFinalThreads];
+  const int tid = threadIdx.x;
+  double s = 0.0;
+  for (int i = tid; i < n; i += kBaFinalThreads) s += e[i];
+  const double cost = 0.5 * ba_block_sum(s, sh);
+  s = 0.0;
+  for (int p = tid; p < nP; p += kBaFinalThreads) s += ppred[p];
+  const double pp = ba_block_sum(s, sh);
+  s = 0.0;
+  for (int t = tid; t < 12 * nC; t += kBaFinalThreads) {
+    const double d = dc[t];
+    s += lam * d * U[144 * (t / 12) + 13 * (t % 12)] * d - d * gc[t];
+  }
+  const double pc = ba_block_sum(s, sh);
+  if (tid == 0) {
+    rec[0] = cost;
+    rec[1] = 0.5 * (pp + pc);
+    rec[2] = flag[0] ? 1.0 : 0.0;
+    rec[3] = serial;
+    flag[0] = 0;
+    __threadfence_system();
+  }
+}
+
+}  // namespace rsd
+
+using rs::fail;
+using rs::hip_fail;
+
+#define HIP_TRY(expr)                                 \
+  do {                                                \
+    hipError_t e_ = (expr);                           \
+    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
+  } while (0)
+
+namespace {
+
+enum { T_LIN, T_CAM, T_PSUM, T_POINT, T_SCHUR, T_CHOL, T_STEP, T_COST, T_SLOTS };
+static_assert(T_SLOTS == RS_BA_TIMING_SLOTS, "rs_ba_timing slots");
+
+// HIP events between the kernels of one batch (up to the next host wait), summed per kernel.
+struct Marks {
+  rs_ctx *c;
+  int used = 0;
+  int slot[RS_BA_EVENTS] = {};
+  hipError_t begin() {
+    used = 0;
+    return mark(-1);
+  }
+  hipError_t mark(int s) {
+    if (!c->ba_timing || used >= RS_BA_EVENTS) return hipSuccess;
+    if (!c->ba_ev[used]) {
+      hipError_t e = hipEventCreate(&c->ba_ev[used]);
+      if (e != hipSuccess) return e;
+    }
+    slot[used] = s;
+    return hipEventRecord(c->ba_ev[used++], c->stream);
+  }
+  hipError_t collect() {  // after the stream has been waited for
+    for (int k = 1; k < used; ++k) {
+      float ms = 0.f;
+      hipError_t e = hipEventElapsedTime(&ms, c->ba_ev[k - 1], c->ba_ev[k]);
+      if (e != hipSuccess) return e;
+      c->ba_ms[slot[k]] += ms;
+    }
+    used = 0;
+    return hipSuccess;
+  }
+};
+
+size_t al(size_t b) { return (b + 255) / 256 * 256; }
+
+unsigned blocks(int64_t n, int per) { return static_cast<unsigned>((n + per - 1) / per); }
+
+}  // namespace
+
+extern "C" int rs_ba_timing(rs_ctx *c, int32_t enable, double *ms, int64_t *trials) {
+  if (!c) return fail(RS_EINVAL, "null context");
+  if (ms)
+    for (int k = 0; k < RS_BA_TIMING_SLOTS; ++k) ms[k] = c->ba_ms[k];
+  if (trials) *trials = c->ba_trials;
+  c->ba_timing = enable ? 1 : 0;
+  return RS_OK;
+}
+
+extern "C" int rs_bundle_adjust(rs_ctx *c, double *cams, int64_t nC, double *pts, int64_t nP,
+                                const int32_t *obs_view, const int32_t *obs_point,
+                                const double *uv, int64_t n, int32_t max_iter, double ftol,
+                                rs_ba_info *info) {
+  if (!c || !cams || !pts || !obs_view || !obs_point || !uv || !info)
+    return fail(RS_EINVAL, "null pointer");
+  if (n <= 0) return fail(RS_EINVAL, "bundle adjustment needs at least one observation");
+  if (nC > RS_BA_MAX_CAMERAS) return fail(RS_EINVAL, "more cameras than RS_BA_MAX_CAMERAS");
+  if (n > (1 << 24) || max_iter < 0) return fail(RS_EINVAL, "bad sizes");
+  int st = rs::ba_check(nC, nP, obs_view, obs_point, n);
+  if (st) return st;
+
+  // ---- host, once: CSR by point and by camera (counting sort, stable), the free cameras
+  // (1.. with an observation) and the observation pairs of every camera block pair
+  std::vector<int32_t> pt_off(nP + 1, 0), pt_obs(n), cnt_cam(nC, 0), slot_of_cam(nC, -1);
+  for (int64_t i = 0; i < n; ++i) {
+    ++pt_off[obs_point[i] + 1];
+    ++cnt_cam[obs_view[i]];
+  }
+  for (int64_t p = 0; p < nP; ++p) pt_off[p + 1] += pt_off[p];
+  {
+    std::vector<int32_t> at(pt_off.begin(), pt_off.end() - 1);
+    for (int64_t i = 0; i < n; ++i) pt_obs[at[obs_point[i]]++] = static_cast<int32_t>(i);
+  }
+  std::vector<int32_t> cam_of_slot;
+  for (int64_t k = 1; k < nC; ++k)
+    if (cnt_cam[k] > 0) {
+      slot_of_cam[k] = static_cast<int32_t>(cam_of_slot.size());
+      cam_of_slot.push_back(static_cast<int32_t>(k));
+    }
+  const int nf = static_cast<int>(cam_of_slot.size());
+  const int N = 12 * nf, ld = N + 1;
+  std::vector<int32_t> cam_off(nf + 1, 0), cam_obs;
+  for (int s = 0; s < nf; ++s) cam_off[s + 1] = cam_off[s] + cnt_cam[cam_of_slot[s]];
+  cam_obs.resize(cam_off[nf] > 0 ? cam_off[nf] : 1);
+  {
+    std::vector<int32_t> at(cam_off.begin(), cam_off.end() - 1);
+    for (int64_t i = 0; i < n; ++i) {
+      const int s = slot_of_cam[obs_view[i]];
+      if (s >= 0) cam_obs[at[s]++] = static_cast<int32_t>(i);
+    }
+  }
+  const int64_t npair = static_cast<int64_t>(nf) * (nf + 1) / 2;
+  auto pair_index = [nf](int a, int b) {
+    return static_cast<int64_t>(a) * nf - static_cast<int64_t>(a) * (a - 1) / 2 + (b - a);
+  };
+  std::vector<int64_t> pair_off(npair + 1, 0);
+  std::vector<int32_t> ent;
+  if (nf > 0) {
+    for (int pass = 0; pass < 2; ++pass) {
+      std::vector<int64_t> at;
+      if (pass == 1) {
+        for (int64_t q = 0; q < npair; ++q) pair_off[q + 1] += pair_off[q];
+        if (pair_off[npair] > (int64_t(1) << 27))
+          return fail(RS_EINVAL, "too many co-visible observation pairs");
+        ent.resize(2 * static_cast<size_t>(pair_off[npair]) + 2);
+        at.assign(pair_off.begin(), pair_off.end() - 1);
+      }
+      for (int64_t p = 0; p < nP; ++p)
+        for (int oi = pt_off[p]; oi < pt_off[p + 1]; ++oi) {
+          const int i = pt_obs[oi], a = slot_of_cam[obs_view[i]];
+          if (a < 0) continue;
+          for (int oj = pt_off[p]; oj < pt_off[p + 1]; ++oj) {
+            const int j = pt_obs[oj], b = slot_of_cam[obs_view[j]];
+            if (b < a) continue;
+            const int64_t q = pair_index(a, b);
+            if (pass == 0) {
+              ++pair_off[q + 1];
+            } else {
+              ent[2 * at[q]] = i;
+              ent[2 * at[q] + 1] = j;
+              ++at[q];
+            }
+          }
+        }
+    }
+  } else {
+    ent.resize(2);
+  }
+
+  // ---- device buffers, one carve of the context scratch
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t D = sizeof(double), I = sizeof(int32_t);
+  const int64_t pp = nP > 0 ? nP : 1;
+  const size_t sizes[] = {
+      D * 12 * nC, D * 12 * nC, D * 3 * pp, D * 3 * pp,            // 0-3 cams, cams_n, pts, pts_n
+      I * n, I * n, D * 2 * n,                                     // 4-6 ov, op, uv
+      I * (nP + 1), I * n, I * (nf + 1), I * cam_obs.size(),       // 7-10 CSR
+      I * nC, I * (nf + 1), sizeof(int64_t) * (npair + 1), I * ent.size(),  // 11-14
+      D * 2 * n, D * 6 * n, D * 6 * n, D * 36 * n, D * 36 * n,     // 15-19 r, jcs, Jp, W, Y
+      D * 144 * nC, D * 12 * nC, D * 12 * nC,                      // 20-22 U, gc, dc
+      D * 6 * pp, D * 6 * pp, D * 3 * pp, D * pp,                  // 23-26 V, Vinv, gp, ppred
+      D * n, D * static_cast<size_t>(ld) * ld, 256};               // 27-29 e, S, flag
+  constexpr int kBufs = sizeof(sizes) / sizeof(sizes[0]);
+  size_t tot = 0;
+  for (size_t s : sizes) tot += al(s);
+  st = rs::ensure_scratch(c, tot + 256);
+  if (st) return st;
+  st = rs::ensure_pinned(c, 256);
+  if (st) return st;
+  char *buf[kBufs];
+  {
+    char *q = static_cast<char *>(c->scratch);
+    for (int k = 0; k < kBufs; ++k) {
+      buf[k] = q;
+      q += al(sizes[k]);
+    }
+  }
+  double *d_cams = reinterpret_cast<double *>(buf[0]), *d_cams_n = reinterpret_cast<double *>(buf[1]);
+  double *d_pts = reinterpret_cast<double *>(buf[2]), *d_pts_n = reinterpret_cast<double *>(buf[3]);
+  int32_t *d_ov = reinterpret_cast<int32_t *>(buf[4]), *d_op = reinterpret_cast<int32_t *>(buf[5]);
+  double *d_uv = reinterpret_cast<double *>(buf[6]);
+  int32_t *d_pt_off = reinterpret_cast<int32_t *>(buf[7]), *d_pt_obs = reinterpret_cast<int32_t *>(buf[8]);
+  int32_t *d_cam_off = reinterpret_cast<int32_t *>(buf[9]), *d_cam_obs = reinterpret_cast<int32_t *>(buf[10]);
+  int32_t *d_slot = reinterpret_cast<int32_t *>(buf[11]), *d_cos = reinterpret_cast<int32_t *>(buf[12]);
+  int64_t *d_pair_off = reinterpret_cast<int64_t *>(buf[13]);
+  int32_t *d_ent = reinterpret_cast<int32_t *>(buf[14]);
+  double *d_r = reinterpret_cast<double *>(buf[15]), *d_jcs = reinterpret_cast<double *>(buf[16]);
+  double *d_Jp = reinterpret_cast<double *>(buf[17]), *d_W = reinterpret_cast<double *>(buf[18]);
+  double *d_Y = reinterpret_cast<double *>(buf[19]), *d_U = reinterpret_cast<double *>(buf[20]);
+  double *d_gc = reinterpret_cast<double *>(buf[21]), *d_dc = reinterpret_cast<double *>(buf[22]);
+  double *d_V = reinterpret_cast<double *>(buf[23]), *d_Vinv = reinterpret_cast<double *>(buf[24]);
+  double *d_gp = reinterpret_cast<double *>(buf[25]), *d_ppred = reinterpret_cast<double *>(buf[26]);
+  double *d_e = reinterpret_cast<double *>(buf[27]), *d_S = reinterpret_cast<double *>(buf[28]);
+  int32_t *d_flag = reinterpret_cast<int32_t *>(buf[29]);
+  volatile double *rec = static_cast<volatile double *>(c->pinned);
+
+  hipStream_t s = c->stream;
+  auto up = [s](void *dst, const void *src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+  };
+  HIP_TRY(up(d_cams, cams, D * 12 * nC));
+  HIP_TRY(up(d_pts, pts, D * 3 * nP));
+  HIP_TRY(up(d_ov, obs_view, I * n));
+  HIP_TRY(up(d_op, obs_point, I * n));
+  HIP_TRY(up(d_uv, uv, D * 2 * n));
+  HIP_TRY(up(d_pt_off, pt_off.data(), I * (nP + 1)));
+  HIP_TRY(up(d_pt_obs, pt_obs.data(), I * n));
+  HIP_TRY(up(d_cam_off, cam_off.data(), I * (nf + 1)));
+  HIP_TRY(up(d_cam_obs, cam_obs.data(), I * cam_obs.size()));
+  HIP_TRY(up(d_slot, slot_of_cam.data(), I * nC));
+  HIP_TRY(up(d_cos, cam_of_slot.data(), I * nf));
+  HIP_TRY(up(d_pair_off, pair_off.data(), sizeof(int64_t) * (npair + 1)));
+  HIP_TRY(up(d_ent, ent.data(), I * ent.size()));
+  // cameras outside the system keep zero U, g_c and step for the whole call
+  HIP_TRY(hipMemsetAsync(d_U, 0, D * 144 * nC, s));
+  HIP_TRY(hipMemsetAsync(d_gc, 0, D * 12 * nC, s));
+  HIP_TRY(hipMemsetAsync(d_dc, 0, D * 12 * nC, s));
+  HIP_TRY(hipMemsetAsync(d_flag, 0, 256, s));
+
+  Marks mk{c};
+  if (c->ba_timing) {
+    for (double &v : c->ba_ms) v = 0.0;
+    c->ba_trials = 0;
+  }
+  const int ni = static_cast<int>(n), nPi = static_cast<int>(nP), nCi = static_cast<int>(nC);
+  double serial = 0.0;
+  // the cost at (cm, pt) into the record; waits for it
+  auto cost_at = [&](const double *cm, const double *pt, bool trial, double lam) -> int {
+    hipLaunchKernelGGL(rsd::k_ba_cost, dim3(blocks(n, 256)), dim3(256), 0, s, cm, pt, d_ov, d_op,
+                       d_uv, ni, d_e);
+    serial += 1.0;
+    hipLaunchKernelGGL(rsd::k_ba_final, dim3(1), dim3(rsd::kBaFinalThreads), 0, s, d_e, ni,
+                       d_ppred, trial ? nPi : 0, d_dc, d_U, d_gc, trial ? nCi : 0, lam, d_flag,
+                       serial, const_cast<double *>(rec));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(mk.mark(T_COST));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(mk.collect());
+    if (rec[3] != serial) return fail(RS_EDEVICE, "bundle adjustment: status record not written");
+    return RS_OK;
+  };
+
+  HIP_TRY(mk.begin());
+  st = cost_at(d_cams, d_pts, false, 0.0);
+  if (st) return st;
+  double cost = rec[0];
+  if (!std::isfinite(cost)) return fail(RS_EINVAL, "non-finite initial cost");
+  const double cost0 = cost;
+  double lam = 1e-3, nu = 2.0;
+  int32_t it = 0, rejected = 0, status = 0;
+  bool done = false;
+  for (it = 1; it <= max_iter && !done; ++it) {
+    HIP_TRY(mk.begin());
+    hipLaunchKernelGGL(rsd::k_ba_linearize, dim3(blocks(n, 256)), dim3(256), 0, s, d_cams, d_pts,
+                       d_ov, d_op, d_uv, ni, d_r, d_jcs, d_Jp, d_W);
+    HIP_TRY(mk.mark(T_LIN));
+    if (nf > 0) {
+      hipLaunchKernelGGL(rsd::k_ba_camera, dim3(nf), dim3(192), 0, s, d_cos, d_cam_off, d_cam_obs,
+                         d_jcs, d_r, d_U, d_gc);
+      HIP_TRY(mk.mark(T_CAM));
+    }
+    hipLaunchKernelGGL(rsd::k_ba_pointsum, dim3(blocks(pp, 256)), dim3(256), 0, s, d_pt_off,
+                       d_pt_obs, nPi, d_Jp, d_r, d_V, d_gp);
+    HIP_TRY(mk.mark(T_PSUM));
+    for (;;) {
+      hipLaunchKernelGGL(rsd::k_ba_point, dim3(blocks(n, 256)), dim3(256), 0, s, d_op, d_pt_off,
+                         d_pt_obs, ni, d_V, lam, d_W, d_Y, d_Vinv, d_flag);
+      HIP_TRY(mk.mark(T_POINT));
+      if (nf > 0) {
+        hipLaunchKernelGGL(rsd::k_ba_schur, dim3(static_cast<unsigned>(npair)), dim3(192), 0, s,
+                           nf, d_pair_off, d_ent, d_Y, d_W, d_U, d_gc, d_gp, d_op, d_cos,
+                           d_cam_off, d_cam_obs, lam, d_S, ld);
+        HIP_TRY(mk.mark(T_SCHUR));
+        hipLaunchKernelGGL(rsd::k_ba_chol, dim3(1), dim3(rsd::kBaCholThreads), 0, s, d_S, N,
+                           d_cos, d_dc, d_flag);
+        HIP_TRY(mk.mark(T_CHOL));
+      }
+      const int64_t lanes = nP > 12 * nC ? nP : 12 * nC;
+      hipLaunchKernelGGL(rsd::k_ba_step, dim3(blocks(lanes, 256)), dim3(256), 0, s, d_pt_off,
+                         d_pt_obs, d_ov, nPi, nCi, d_slot, d_W, d_V, d_Vinv, d_gp, d_dc, lam,
+                         d_cams, d_pts, d_cams_n, d_pts_n, d_ppred);
+      HIP_TRY(mk.mark(T_STEP));
+      st = cost_at(d_cams_n, d_pts_n, true, lam);
+      if (st) return st;
+      if (c->ba_timing) ++c->ba_trials;
+      const double cost_n = rec[0], pred = rec[1];
+      const bool failed = rec[2] != 0.0 || !std::isfinite(cost_n);
+      if (!failed && cost_n < cost && pred > 0.0) {
+        const double rho = (cost - cost_n) / pred;
+        const bool small = (cost - cost_n) <= ftol * cost;
+        std::swap(d_cams, d_cams_n);
+        std::swap(d_pts, d_pts_n);
+        cost = cost_n;
+        const double t = 2.0 * rho - 1.0;
+        lam *= std::fmax(1.0 / 3.0, 1.0 - t * t * t);
+        nu = 2.0;
+        if (small) {
+          status = 1;
+          done = true;
+        }
+        break;
+      }
+      ++rejected;
+      lam *= nu;
+      nu *= 2.0;
+      if (lam > 1e32) {
+        status = 2;
+        done = true;
+        break;
+      }
+      HIP_TRY(mk.begin());
+    }
+  }
+  it = done ? it - 1 : max_iter;
+
+  HIP_TRY(hipMemcpyAsync(cams, d_cams, D * 12 * nC, hipMemcpyDeviceToHost, s));
+  if (nP > 0) HIP_TRY(hipMemcpyAsync(pts, d_pts, D * 3 * nP, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  info->cost_init = cost0;
+  info->cost = cost;
+  info->lambda = lam;
+  info->iterations = it;
+  info->rejected = rejected;
+  info->status = status;
+  info->reserved = 0;
+  return RS_OK;
+}

@@ -6,6 +6,8 @@
 #include "rsamd.h"
 
 
+#define RS_BA_EVENTS 16  // one batch of rs_bundle_adjust kernels between two host waits
+
 struct rs_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -31,12 +33,20 @@ struct rs_ctx {
   double np_ms[RS_NP_TIMING_SLOTS] = {};
   double np_bytes[3] = {};
   int64_t np_segments = 0;
+  // rs_ba_timing: HIP events between the kernels of rs_bundle_adjust, the last timed call's
+  // sums per kernel (RS_BA_TIMING_SLOTS ms) and its number of trials
+  int ba_timing = 0;
+  hipEvent_t ba_ev[RS_BA_EVENTS] = {};
+  double ba_ms[RS_BA_TIMING_SLOTS] = {};
+  int64_t ba_trials = 0;
 };
 
 namespace rs {
 int hip_fail(hipError_t e, const char *what);
 int ensure_scratch(rs_ctx *c, size_t bytes);
 int ensure_pinned(rs_ctx *c, size_t bytes);
+// The size and index rules of the bundle-adjustment entry points (tables.hip).
+int ba_check(int64_t nC, int64_t nP, const int32_t *ov, const int32_t *op, int64_t n);
 void np_shard_free(rs_ctx *c);
 int np_preload();  // the parse kernels' code object onto the current device (rs_ctx_create)
 bool np_gpu_supported(int64_t n, int32_t k);  // within the GPU parse's population range

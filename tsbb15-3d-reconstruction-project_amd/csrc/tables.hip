@@ -278,7 +278,7 @@ extern "C" int rs_add_new_points(rs_ctx *c, const double *C1, const double *C2,
   return RS_OK;
 }
 
-static int ba_check(int64_t nC, int64_t nP, const int32_t *ov, const int32_t *op, int64_t n) {
+int rs::ba_check(int64_t nC, int64_t nP, const int32_t *ov, const int32_t *op, int64_t n) {
   if (nC < 1 || nP < 0 || n < 0 || n > (1 << 26) || nC > (1 << 20) || nP > (1 << 26))
     return fail(RS_EINVAL, "bad sizes");
   for (int64_t i = 0; i < n; ++i)
@@ -292,7 +292,7 @@ extern "C" int rs_ba_residuals(rs_ctx *c, const double *cams, int64_t nC, const 
                                const double *uv, int64_t n, double *r) {
   if (!c || !cams || !r || (nP > 0 && !pts) || (n > 0 && (!obs_view || !obs_point || !uv)))
     return fail(RS_EINVAL, "null pointer");
-  int st = ba_check(nC, nP, obs_view, obs_point, n);
+  int st = rs::ba_check(nC, nP, obs_view, obs_point, n);
   if (st) return st;
   if (n == 0) return RS_OK;
   HIP_TRY(hipSetDevice(c->device));
@@ -323,7 +323,7 @@ extern "C" int rs_ba_jacobian(rs_ctx *c, const double *cams, int64_t nC, const d
                               int64_t n, double *Jc, double *Jp) {
   if (!c || !cams || !Jc || !Jp || (nP > 0 && !pts) || (n > 0 && (!obs_view || !obs_point)))
     return fail(RS_EINVAL, "null pointer");
-  int st = ba_check(nC, nP, obs_view, obs_point, n);
+  int st = rs::ba_check(nC, nP, obs_view, obs_point, n);
   if (st) return st;
   if (n == 0) return RS_OK;
   HIP_TRY(hipSetDevice(c->device));

@@ -63,6 +63,16 @@ class GsInfo(C.Structure):
                 ("accepted", C.c_int32), ("status", C.c_int32), ("n", C.c_int32)]
 
 
+class BaInfo(C.Structure):
+    _fields_ = [("cost_init", C.c_double), ("cost", C.c_double), ("lam", C.c_double),
+                ("iterations", C.c_int32), ("rejected", C.c_int32), ("status", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+BA_MAX_CAMERAS = 128
+BA_KERNELS = ("k_ba_linearize", "k_ba_camera", "k_ba_pointsum", "k_ba_point", "k_ba_schur",
+              "k_ba_chol", "k_ba_step", "k_ba_cost+final")
+
 _SIGS = {
     "rs_last_error": (C.c_char_p, []),
     "rs_version": (C.c_int, []),
@@ -148,6 +158,9 @@ _SIGS = {
                                   C.c_int64, _dp]),
     "rs_ba_jacobian": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _i32p, _i32p,
                                  C.c_int64, _dp, _dp]),
+    "rs_bundle_adjust": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _i32p, _i32p, _dp,
+                                   C.c_int64, C.c_int32, C.c_double, C.POINTER(BaInfo)]),
+    "rs_ba_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp, _i64p]),
     "rs_np_shard_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.POINTER(C.c_void_p)]),
     "rs_np_shard_destroy": (C.c_int, [C.c_void_p]),
@@ -353,6 +366,14 @@ def pnp_timing(ctx, enable):
     a, b = C.c_double(0.0), C.c_double(0.0)
     check(lib().rs_pnp_timing(ctx.handle, int(enable), C.byref(a), C.byref(b)))
     return a.value, b.value
+
+
+def ba_timing(ctx, enable):
+    """Enable / disable HIP events between rs_bundle_adjust's kernels (rs_ba_timing); returns
+    the last timed call's ({kernel: summed device ms}, trials)."""
+    ms, trials = np.zeros(len(BA_KERNELS)), C.c_int64(0)
+    check(lib().rs_ba_timing(ctx.handle, int(enable), ptr(ms, C.c_double), C.byref(trials)))
+    return dict(zip(BA_KERNELS, ms.tolist())), trials.value
 
 
 NP_STEPS = ("jump", "stream_pass1", "entry", "track", "compose", "starts", "tuples", "result",

@@ -8,6 +8,8 @@ Array-level functions (HIP kernels of tables.hip):
                             gate |y1^T E y2| < 0.1 and optimal triangulation of the accepted
   * ``ba_residuals``        EpsilonBA of Tables.BundleAdjustment2 (tables.py:264-293)
   * ``ba_jacobian``         its Jacobian blocks (the nonzeros of tables.py:339-372)
+  * ``bundle_adjust``       that objective minimised on the GPU (ba.hip): Levenberg-Marquardt,
+                            points eliminated by a Schur complement, camera 0 fixed
 
 Table-level replacements for the reference's methods (they take a reference ``Tables``
 object -- anything with T_obs / T_views / T_points, addView / addPoint / addObs -- run the
@@ -15,6 +17,7 @@ arithmetic above on the GPU and do the same bookkeeping in the same order):
 
   * ``add_new_view(T, K, img_index, y1_hom, y2_hom, y1, y2)``      Tables.addNewView
   * ``add_new_points_table(T, A_y1_hom, A_y2_hom, v1, v2)``       Tables.addNewPoints
+  * ``BundleAdjustment2(T)``                                       Tables.BundleAdjustment2
 """
 from __future__ import annotations
 
@@ -122,6 +125,36 @@ def ba_jacobian(cams, pts, obs_view, obs_point, ctx=None):
     return Jc, Jp
 
 
+def bundle_adjust(cams, pts, obs_view, obs_point, uv, max_iter=200, ftol=1e-15, ctx=None):
+    """The objective of ``ba_residuals`` minimised over cameras 1.. (12 parameters each) and the
+    points: Levenberg-Marquardt with Marquardt damping and Nielsen's update, the points
+    eliminated by a Schur complement, all on the GPU in fp64 (rs_bundle_adjust).  Camera 0,
+    and every camera or point without an observation, comes back bit for bit unchanged.  At
+    most ``_ffi.BA_MAX_CAMERAS`` cameras.  The inputs are not modified.
+
+    Returns (cams (nC, 3, 4), pts (nP, 3), info) with info = dict(cost_init, cost, iterations,
+    status, rejected, lambda): costs are 0.5 |r|^2; status 1 = an accepted step gained
+    <= ftol * cost, 2 = damping above 1e32, 0 = max_iter linearisations."""
+    cams, pts, ov, op = _ba_args(cams, pts, obs_view, obs_point)
+    cams, pts = cams.copy(), pts.copy()
+    uv = _ffi.f64c(uv).reshape(-1, 2)
+    if len(uv) != len(ov):
+        raise ValueError('one (u, v) per observation')
+    if len(ov) == 0:
+        raise ValueError('bundle adjustment needs at least one observation')
+    if len(cams) == 0:
+        raise ValueError('bundle adjustment needs at least one camera')
+    info = _ffi.BaInfo()
+    i32 = _ffi.C.c_int32
+    _ffi.check(_ffi.lib().rs_bundle_adjust(
+        _ctx(ctx), _ffi.ptr(cams, _d), len(cams), _ffi.ptr(pts, _d), len(pts), _ffi.ptr(ov, i32),
+        _ffi.ptr(op, i32), _ffi.ptr(uv, _d), len(ov), int(max_iter), float(ftol),
+        _ffi.C.byref(info)))
+    return cams, pts, {"cost_init": info.cost_init, "cost": info.cost,
+                       "iterations": info.iterations, "status": info.status,
+                       "rejected": info.rejected, "lambda": info.lam}
+
+
 # ------------------------------------------------------------------------------------------
 # table-level replacements
 # ------------------------------------------------------------------------------------------
@@ -178,3 +211,24 @@ def add_new_points_table(T, A_y1_hom, A_y2_hom, view_index_1, view_index_2):
         T.addObs(A_y2_hom[i], view_index_2, point_index)
         counter += 1
     return counter
+
+
+def BundleAdjustment2(T, max_iter=200, ftol=1e-15, ctx=None):
+    """Tables.BundleAdjustment2 (tables.py:260-338) on the GPU: the cameras [R | t] of T_views,
+    the points of T_points and image_coordinates[:2] of T_obs, in table order, through
+    ``bundle_adjust`` instead of scipy's TRF, then the write-back of updateCameras3Dpoints2
+    (tables.py:384-390): every view gets a new pose of its own pose class built from the 3 x 4
+    result, every point its new coordinates.  Returns the info dict of ``bundle_adjust``."""
+    cams = np.array([_pose(v.camera_pose) for v in T.T_views]).reshape(-1, 3, 4)
+    pts = np.array([p.point for p in T.T_points], dtype=np.float64).reshape(-1, 3)
+    uv = np.array([np.asarray(o.image_coordinates, dtype=np.float64).ravel()[:2]
+                   for o in T.T_obs]).reshape(-1, 2)
+    ov = np.array([o.view_index for o in T.T_obs], dtype=np.int32)
+    op = np.array([o.point_3D_index for o in T.T_obs], dtype=np.int32)
+    new_pose, new_points, info = bundle_adjust(cams, pts, ov, op, uv, max_iter=max_iter,
+                                               ftol=ftol, ctx=ctx)
+    for i, v in enumerate(T.T_views):
+        v.camera_pose = type(v.camera_pose)(new_pose[i, :3, :3], new_pose[i, :, 3])
+    for i, p in enumerate(T.T_points):
+        p.point = new_points[i]
+    return info
