@@ -554,6 +554,58 @@ int rs_bundle_adjust(rs_ctx *ctx, double *cams, int64_t nC, double *pts, int64_t
 int rs_ba_timing(rs_ctx *ctx, int32_t enable, double *ms, int64_t *trials);
 
 /* ------------------------------------------------------------------------------------------
+ * The wash step (wash.hip): the two steps main.py names and leaves empty.  cams, pts,
+ * obs_view, obs_point and uv have the layout of rs_bundle_adjust.  A point's track is its
+ * observations in ascending observation index.
+ * ------------------------------------------------------------------------------------------ */
+#define RS_WASH_MAX_TRACK 128          /* observations of one point; = RS_BA_MAX_CAMERAS */
+
+/* N-view triangulation, the "Re-triangulate" of main.py:101-107 without its robustness (the
+ * reference has only the two-view tables.py:161-175): every point from all its observations.
+ * The start is the inhomogeneous linear solution of the 2m equations (u c3 - c1).[X;1] = 0,
+ * (v c3 - c2).[X;1] = 0 through the 3x3 normal equations and Cholesky; then Levenberg-Marquardt
+ * on X in R^3 (Marquardt diagonal damping, lambda0 = 1e-3, Nielsen's update, at most 20
+ * linearisations, stop when an accepted step gains <= 1e-15 cost or lambda > 1e32: the scheme
+ * of rs_bundle_adjust).  ok[j] = 0 (and pts[j] untouched) for a point with < 2 observations, a
+ * singular start or a non-finite result.  RS_EINVAL as rs_wash_points. */
+int rs_triangulate_nview(rs_ctx *ctx, const double *cams, int64_t nC, double *pts, int64_t nP,
+                         const int32_t *obs_view, const int32_t *obs_point, const double *uv,
+                         int64_t n, int32_t *ok);
+
+typedef struct rs_wash_info {
+  int64_t hypotheses;        /* valid two-view hypotheses scored */
+  int32_t obs_removed, points_removed, points_failed, reserved;
+} rs_wash_info;              /* 24 bytes */
+
+/* WASH1 (main.py:101-107, "Remove bad 3D points. Re-triangulate & Remove outliers") and WASH2
+ * (main.py:140-168, "remove either 3D points or observation"), per point and with t2 = thresh^2.
+ * Observation i is an inlier of X when e_i = |uv_i - proj(cams[view_i], X)|^2 <= t2 (ordered
+ * comparison: a NaN is never an inlier) and, if depth_sign != 0, the sign of the depth
+ * c3.[X;1] equals depth_sign.
+ *   1. every pair a < b of the track in two different views gives a hypothesis: the linear
+ *      triangulation of the two observations (above); a non-positive or NaN pivot or a
+ *      non-finite X makes it invalid.  Its score is (inliers over the whole track, sum of
+ *      their e_i in track order).
+ *   2. the winner is the valid hypothesis with >= 2 inliers that is best under the total order
+ *      larger count, smaller sum, smaller pair ordinal (a-major, b-minor).  None: the point fails.
+ *   3. twice: the Levenberg-Marquardt of rs_triangulate_nview over the current inlier set from
+ *      the current X, then every e_i and the inlier set again.  Fewer than 2 inliers before a
+ *      refit: the point fails.
+ *   4. err2[i] is the final e_i (NaN for every observation of a failed point).  A point is kept
+ *      when it did not fail, X is finite and it has >= min_views final inliers: point_keep[j]
+ *      = 1, pts[j] = X and obs_keep[i] = 1 exactly for its final inliers.  Every other point
+ *      keeps its input bits and all its observations get obs_keep = 0.
+ * info: points_failed counts the failures, points_removed every point not kept, obs_removed
+ * every obs_keep = 0.  A NaN in uv or in a camera is not an error.  RS_EINVAL: an index out of
+ * range, nC < 1, n < 1, n > 2^24, thresh not finite or <= 0, min_views < 2, depth_sign outside
+ * {-1, 0, 1}, a track longer than RS_WASH_MAX_TRACK.  The same inputs give bitwise the same
+ * outputs (no floating-point atomics; every sum in track order). */
+int rs_wash_points(rs_ctx *ctx, const double *cams, int64_t nC, double *pts, int64_t nP,
+                   const int32_t *obs_view, const int32_t *obs_point, const double *uv, int64_t n,
+                   double thresh, int32_t min_views, int32_t depth_sign,
+                   int32_t *obs_keep, int32_t *point_keep, double *err2, rs_wash_info *info);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU (RCCL over xGMI).  One process per GPU; the unique id travels out of band.
  * ---------------------------------------------------------------------------------------- */
 #define RS_COMM_ID_BYTES 128

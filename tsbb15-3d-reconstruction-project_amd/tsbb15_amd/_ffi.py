@@ -69,7 +69,14 @@ class BaInfo(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class WashInfo(C.Structure):
+    _fields_ = [("hypotheses", C.c_int64), ("obs_removed", C.c_int32),
+                ("points_removed", C.c_int32), ("points_failed", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 BA_MAX_CAMERAS = 128
+WASH_MAX_TRACK = 128
 BA_KERNELS = ("k_ba_linearize", "k_ba_camera", "k_ba_pointsum", "k_ba_point", "k_ba_schur",
               "k_ba_chol", "k_ba_step", "k_ba_cost+final")
 
@@ -161,6 +168,11 @@ _SIGS = {
     "rs_bundle_adjust": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _i32p, _i32p, _dp,
                                    C.c_int64, C.c_int32, C.c_double, C.POINTER(BaInfo)]),
     "rs_ba_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp, _i64p]),
+    "rs_triangulate_nview": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _i32p, _i32p,
+                                       _dp, C.c_int64, _i32p]),
+    "rs_wash_points": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _i32p, _i32p, _dp,
+                                 C.c_int64, C.c_double, C.c_int32, C.c_int32, _i32p, _i32p, _dp,
+                                 C.POINTER(WashInfo)]),
     "rs_np_shard_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.POINTER(C.c_void_p)]),
     "rs_np_shard_destroy": (C.c_int, [C.c_void_p]),

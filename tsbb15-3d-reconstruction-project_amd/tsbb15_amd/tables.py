@@ -10,6 +10,10 @@ Array-level functions (HIP kernels of tables.hip):
   * ``ba_jacobian``         its Jacobian blocks (the nonzeros of tables.py:339-372)
   * ``bundle_adjust``       that objective minimised on the GPU (ba.hip): Levenberg-Marquardt,
                             points eliminated by a Schur complement, camera 0 fixed
+  * ``triangulate_nview``   every point from all its observations (wash.hip)
+  * ``wash_points``         robust re-triangulation of every point from its own track and the
+                            outlier verdict on its observations: the WASH1 / WASH2 steps that
+                            main.py:101-107 and main.py:140-168 name and leave empty
 
 Table-level replacements for the reference's methods (they take a reference ``Tables``
 object -- anything with T_obs / T_views / T_points, addView / addPoint / addObs -- run the
@@ -18,6 +22,7 @@ arithmetic above on the GPU and do the same bookkeeping in the same order):
   * ``add_new_view(T, K, img_index, y1_hom, y2_hom, y1, y2)``      Tables.addNewView
   * ``add_new_points_table(T, A_y1_hom, A_y2_hom, v1, v2)``       Tables.addNewPoints
   * ``BundleAdjustment2(T)``                                       Tables.BundleAdjustment2
+  * ``wash(T, thresh)``                                            the wash step (no reference code)
 """
 from __future__ import annotations
 
@@ -155,6 +160,60 @@ def bundle_adjust(cams, pts, obs_view, obs_point, uv, max_iter=200, ftol=1e-15, 
                        "rejected": info.rejected, "lambda": info.lam}
 
 
+def _wash_args(cams, pts, obs_view, obs_point, uv):
+    cams, pts, ov, op = _ba_args(cams, pts, obs_view, obs_point)
+    uv = _ffi.f64c(uv).reshape(-1, 2)
+    if len(uv) != len(ov):
+        raise ValueError('one (u, v) per observation')
+    if len(ov) == 0:
+        raise ValueError('the wash needs at least one observation')
+    if len(cams) == 0:
+        raise ValueError('the wash needs at least one camera')
+    return cams, pts.copy(), ov, op, uv
+
+
+def triangulate_nview(cams, pts, obs_view, obs_point, uv, ctx=None):
+    """Every point from all its observations (rs_triangulate_nview): the linear solution of its
+    2m equations, then Levenberg-Marquardt on X, no robustness.  Returns (pts, ok (bool)); a
+    point with fewer than 2 observations, a singular start or a non-finite result has ok False
+    and keeps its input bits.  The inputs are not modified."""
+    cams, pts, ov, op, uv = _wash_args(cams, pts, obs_view, obs_point, uv)
+    ok = np.zeros(len(pts), dtype=np.int32)
+    i32 = _ffi.C.c_int32
+    _ffi.check(_ffi.lib().rs_triangulate_nview(
+        _ctx(ctx), _ffi.ptr(cams, _d), len(cams), _ffi.ptr(pts, _d), len(pts), _ffi.ptr(ov, i32),
+        _ffi.ptr(op, i32), _ffi.ptr(uv, _d), len(ov), _ffi.ptr(ok, i32)))
+    return pts, ok.astype(bool)
+
+
+def wash_points(cams, pts, obs_view, obs_point, uv, thresh, min_views=2, depth_sign=0, ctx=None):
+    """Robust re-triangulation of every point from its own track and the verdict on its
+    observations (rs_wash_points; the algorithm stands in include/rsamd.h): two-view hypotheses
+    from every pair of the track scored by their inliers within ``thresh`` (and, with
+    ``depth_sign`` = +-1, with that sign of the depth), two refits over the inliers.
+
+    Returns (pts, obs_keep (bool), point_keep (bool), err2, info): a kept point has its new
+    coordinates and at least ``min_views`` kept observations; every other point keeps its input
+    bits and loses all its observations.  err2 is the final squared error per observation, NaN
+    where the point failed.  info = dict(hypotheses, obs_removed, points_removed,
+    points_failed).  At most ``_ffi.WASH_MAX_TRACK`` observations per point.  The inputs are not
+    modified."""
+    cams, pts, ov, op, uv = _wash_args(cams, pts, obs_view, obs_point, uv)
+    obs_keep = np.zeros(len(ov), dtype=np.int32)
+    point_keep = np.zeros(len(pts), dtype=np.int32)
+    err2 = np.full(len(ov), np.nan)
+    info = _ffi.WashInfo()
+    i32 = _ffi.C.c_int32
+    _ffi.check(_ffi.lib().rs_wash_points(
+        _ctx(ctx), _ffi.ptr(cams, _d), len(cams), _ffi.ptr(pts, _d), len(pts), _ffi.ptr(ov, i32),
+        _ffi.ptr(op, i32), _ffi.ptr(uv, _d), len(ov), float(thresh), int(min_views),
+        int(depth_sign), _ffi.ptr(obs_keep, i32), _ffi.ptr(point_keep, i32), _ffi.ptr(err2, _d),
+        _ffi.C.byref(info)))
+    return pts, obs_keep.astype(bool), point_keep.astype(bool), err2, {
+        "hypotheses": info.hypotheses, "obs_removed": info.obs_removed,
+        "points_removed": info.points_removed, "points_failed": info.points_failed}
+
+
 # ------------------------------------------------------------------------------------------
 # table-level replacements
 # ------------------------------------------------------------------------------------------
@@ -232,3 +291,40 @@ def BundleAdjustment2(T, max_iter=200, ftol=1e-15, ctx=None):
     for i, p in enumerate(T.T_points):
         p.point = new_points[i]
     return info
+
+
+def wash(T, thresh, min_views=2, depth_sign=0, ctx=None):
+    """The wash step main.py names and leaves empty (WASH1 main.py:101-107, WASH2
+    main.py:140-168), for after BundleAdjustment2 and after addNewPoints: the arrays are
+    gathered as in ``BundleAdjustment2``, ``wash_points`` decides, and the table is rewritten.
+    Removed points and observations leave T_points / T_obs, the survivors keep their relative
+    order; kept points get their new coordinates; every point_3D_index and every
+    observations_index (views and points) is renumbered, removed entries dropped.  Element 0 of
+    an observations_index, the reference's spurious 0 (help_classes.py:26,61), stays a literal
+    0.  Views are never removed; one may be left without observations.
+
+    Returns the info dict of ``wash_points`` plus point_map and obs_map: the new index of every
+    old point / observation, -1 where removed."""
+    cams = np.array([_pose(v.camera_pose) for v in T.T_views]).reshape(-1, 3, 4)
+    pts = np.array([p.point for p in T.T_points], dtype=np.float64).reshape(-1, 3)
+    uv = np.array([np.asarray(o.image_coordinates, dtype=np.float64).ravel()[:2]
+                   for o in T.T_obs]).reshape(-1, 2)
+    ov = np.array([o.view_index for o in T.T_obs], dtype=np.int32)
+    op = np.array([o.point_3D_index for o in T.T_obs], dtype=np.int32)
+    new_points, obs_keep, point_keep, _, info = wash_points(
+        cams, pts, ov, op, uv, thresh, min_views=min_views, depth_sign=depth_sign, ctx=ctx)
+    point_map = np.where(point_keep, np.cumsum(point_keep) - 1, -1)
+    obs_map = np.where(obs_keep, np.cumsum(obs_keep) - 1, -1)
+    for j in np.flatnonzero(point_keep):
+        T.T_points[j].point = new_points[j]
+    for i in np.flatnonzero(obs_keep):
+        T.T_obs[i].point_3D_index = int(point_map[op[i]])
+    for rec in list(T.T_views) + [T.T_points[j] for j in np.flatnonzero(point_keep)]:
+        idx = np.asarray(rec.observations_index)
+        tail = obs_map[idx[1:].astype(np.int64)]
+        rec.observations_index = np.concatenate((idx[:1], tail[tail >= 0])).astype(idx.dtype)
+    T.T_obs = T.T_obs[obs_keep]                      # object arrays (tables.py:16-18)
+    T.T_points = T.T_points[point_keep]
+    out = dict(info)
+    out["point_map"], out["obs_map"] = point_map, obs_map
+    return out
