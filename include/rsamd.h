@@ -208,7 +208,12 @@ int rs_f8_plan_destroy(rs_f8_plan *plan);
 int rs_f8_plan_set_points(rs_f8_plan *plan, const double *p1, const double *p2);
 /* Enqueue one RANSAC run of H hypotheses: sample (mode), solve, count, select, re-score,
  * replay the fun.py:320-328 rule, extract inliers.  Philox mode draws hypothesis i from
- * counter (seed, hyp_offset + i); tuple mode reads host_tuples (H, 8) int32. */
+ * counter (seed, hyp_offset + i); tuple mode reads host_tuples (H, 8) int32.
+ * Ordering: runs issued back to back on one plan alternate between two HIP streams (the
+ * context's and one owned by the plan; RSAMD_OVERLAP=0: the context's only) and may execute
+ * concurrently.  Each run has its own buffer set, Philox counters and result slot, so results
+ * are per run and independent of that; rs_f8_plan_result (and the accessors) wait for every run
+ * in flight and return the last issued one. */
 int rs_f8_plan_run(rs_f8_plan *plan, int64_t H, int32_t mode, uint64_t seed, uint64_t hyp_offset,
                    const int32_t *host_tuples, double thresh);
 /* Parity-mode run: the next H tuples of the numpy legacy stream (key, pos) -- the
@@ -242,8 +247,14 @@ int rs_f8_plan_candidates(rs_f8_plan *plan, rs_f8_candidate *out, int64_t cap, i
 int rs_f8_plan_set_count_precision(rs_f8_plan *plan, int32_t fp64);
 int rs_f8_plan_counts(rs_f8_plan *plan, int32_t *counts, int64_t H);
 int rs_f8_plan_models(rs_f8_plan *plan, double *F_out, int64_t H);
-/* Device time (ms, HIP events on the plan's stream) of the counting kernel, the solve kernel
- * and the whole run: of the last run, or averaged over the last `last_n` runs (<= 64).  Runs
+/* Host waits for one stream lane taken outside rs_f8_plan_result and the other synchronising
+ * calls, since the plan was created: the parity entry points (rs_f8_plan_run_np*) wait for
+ * lane 1 before their parse, and a run that meets a buffer set still in use on the other lane
+ * waits for that lane.  Stays 0 in any sequence of Philox and host-tuple runs. */
+int rs_f8_plan_lane_waits(rs_f8_plan *plan, int64_t *waits);
+/* Device time (ms, HIP events on the run's stream lane; a run that records them runs its
+ * counting kernel alone, without the other lane's kernels beside it) of the counting kernel,
+ * the solve kernel and the whole run: of the last run, or averaged over the last `last_n` runs (<= 64).  Runs
  * may be issued back to back (each owns a result slot in pinned host memory: the header and
  * S_RANSAC, written by the run's last kernel); rs_f8_plan_result waits for the last. */
 int rs_f8_plan_kernel_ms(rs_f8_plan *plan, double *score_ms, double *solve_ms, double *total_ms);

@@ -2,24 +2,36 @@
 // hypotheses issued back to back.  Replaces the fun.getFFromLabCode hypothesis loop
 // (fun.py:298-328).
 //
-// Per-run buffer sets (kBufs) used in rotation.  By default everything runs on the context's
-// HIP stream: rs_f8_plan_run(k) enqueues
+// Per-run buffer sets (kBufs) used in rotation.  A run is a serial chain on one stream
+// ("lane"): rs_f8_plan_run(k) enqueues on its lane
 //
-//   k_f8_tail_solve  [selection tail of run k-1 | solve of run k]   (one launch)
+//   k_f8_tail_solve  [selection tail of the lane's previous run | solve of run k]  (one launch)
 //   k_f8_count32x    counts of run k (+ fused c*)
 //
-// and leaves run k's tail pending: it rides along with run k+1's solve, or is flushed alone
-// by rs_f8_plan_result / set_points / destroy.  The tail (candidates, reference statistics,
-// replay, S_RANSAC; latency bound, a few busy workgroups) and the solve (latency bound,
-// ~1.5 waves per SIMD) thus share the machine instead of running back to back, with no
-// cross-stream events (each event or wait is a packet the command processor retires
-// between kernels; r01: ~3.5 us each).
+// and leaves run k's tail pending on that lane: it rides along with the lane's next solve, or
+// is flushed alone by rs_f8_plan_result / set_points / destroy (plan_flush, the only place the
+// host waits).  The tail (candidates, reference statistics, replay, S_RANSAC; latency bound, a
+// few busy workgroups) and the solve (latency bound, ~1.5 waves per SIMD) thus share the
+// machine instead of running back to back.
 //
-// Optional overlap mode (RSAMD_OVERLAP=1, off by default: measured 2-4 % slower, DESIGN.md
-// "Next"): run k's solve on a side stream ss, its count on the context stream and its tail
-// on a third stream ts, chained by per-buffer-set events (ev_solve / ev_count / ev_tail); a
-// set's solve waits for the tail of the run that used the set kBufs runs back, and the
-// parity samplers wait for the set's last solve before they refill its tuples.
+// One lane (RSAMD_OVERLAP=0): every run on the context's stream, the tail of run k-1 with the
+// solve of run k.
+//
+// Two lanes (RSAMD_OVERLAP=1): lane 0 is the context's stream, lane 1 a non-blocking stream the
+// plan creates the first time a run is placed on it.  A run goes to lane 0 when nothing is in
+// flight, otherwise to the lane the previous run did not use, so consecutive runs execute
+// concurrently: while one lane's count drains, the other lane's solve and count workgroups
+// take the freed wave slots.  In a back-to-back sequence run k + 4 reuses buffer set and
+// pinned slot k % 4 on the lane of run k, and run k's tail rides with the solve of run k + 2,
+// so stream order alone protects them: there is no cross-stream event on the hot path (each
+// event or wait is a packet the command processor retires between kernels; r01: ~3.5 us
+// each).  Where the alternation is broken (the parity entry points run on lane 0 behind their
+// parse and drain lane 1 first), a run about to use a set whose last run went to the other
+// lane, with no host wait for that lane since, waits on the host for it (the set guard; never
+// in a Philox or host-tuple sequence, whatever the number of runs between two plan_flush
+// calls: rs_f8_plan_lane_waits counts these waits).  A run that records timing events runs its count
+// alone: its lane waits for the other lane's end before the first event, the other lane waits
+// for the last one.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,8 +51,10 @@ using rs::hip_fail;
 
 namespace {
 
-// Per-run device buffers; two sets alternate between consecutive runs.
+// Per-run device buffers; kBufs sets in rotation.
 struct RunBufs {
+  int lane = 0;                // the lane of the last run that used this set (set guard)
+  int64_t last_run = -1;       // ... and that run's index
   double *d_F = nullptr;       // 9 x ld SoA models (float64)
   float *d_F32 = nullptr;      // 9 x ld SoA models in the unit frame (fp32 counting)
   int *d_counts = nullptr;     // fast counts
@@ -64,7 +78,9 @@ struct RunBufs {
   bool copy_pending = false;
 };
 
-constexpr int kOverlapDefault = 0;  // rs_f8_plan::overlap unless RSAMD_OVERLAP is set
+// rs_f8_plan::overlap (two lanes) unless RSAMD_OVERLAP is set: two lanes measured 8-9 % ahead
+// of one in every interleaved bench run (profiles/lanes/ab.txt)
+constexpr int kOverlapDefault = 1;
 
 int env_int(const char *name, int dflt) {
   const char *v = std::getenv(name);
@@ -80,7 +96,9 @@ struct rs_f8_plan {
   double *d_p12 = nullptr;     // staging (2,n) p1 then (2,n) p2
   rsd::Pt *d_pts = nullptr;    // AoS float64 points
   float4 *d_pts32q = nullptr;  // the same, point-pair layout (k_f8_count32q)
-  static constexpr int kBufs = 3, kSlots = 4, kEvRing = 64;
+  // kBufs: with two lanes the sets of runs k and k-1 (solve / count) and of runs k-2 and k-3
+  // (their tails ride with those solves) are live at once
+  static constexpr int kBufs = 4, kSlots = 4, kEvRing = 64, kLanes = 2;
   RunBufs buf[kBufs];
   // Each run's tail writes its result header into its own pinned slot (through the host
   // mapping) and S_RANSAC into its buffer set's HBM result; rs_f8_plan_result waits for the
@@ -93,16 +111,23 @@ struct rs_f8_plan {
   bool timed[kEvRing] = {};          // whether run r % kEvRing recorded its events
   int64_t runs = 0, last_H = 0;
   bool pending = false;              // stream work not yet waited for
-  bool tail_pending = false;         // the last run's tail is not enqueued yet
-  // Overlap mode (RSAMD_OVERLAP=1; kOverlapDefault otherwise): run k's solve on ss, its
-  // count on the context stream, its tail on ts, chained by events, so the next run's solve and
-  // this run's tail fill the CUs the counting kernel's drain leaves idle.  A buffer set's solve
-  // waits for the tail of the run that used the set before (kBufs runs back).
+  // Two lanes (RSAMD_OVERLAP=1; kOverlapDefault otherwise): consecutive runs alternate between
+  // the context's stream (lane 0) and lane1, each lane a serial chain tail+solve -> count, so
+  // one lane's solve and count fill the wave slots the other lane's count leaves idle.
   bool overlap = kOverlapDefault != 0;
-  hipStream_t ss = nullptr, ts = nullptr;
-  hipEvent_t ev_solve[kBufs] = {}, ev_count[kBufs] = {}, ev_tail[kBufs] = {};
-  hipEvent_t ev_np = nullptr;  // parity mode: the parse queued before the solve (overlap)
-  rsd::TailArgs tail{};              // ... its arguments
+  hipStream_t lane1 = nullptr;       // created when the first run is placed on it
+  int last_lane = 0;                 // the lane of the last issued run
+  bool busy[kLanes] = {};            // the lane has work the host has not waited for
+  bool tail_pending[kLanes] = {};    // the lane's last run's tail is not enqueued yet
+  rsd::TailArgs tail[kLanes] = {};   // ... its arguments
+  // set guard: runs issued when the host last waited for the lane (every run of the lane below
+  // that index is complete), and how often a run had to wait on the host for the other lane
+  int64_t synced[kLanes] = {};
+  int64_t lane_waits = 0;
+  // timed runs count alone: ev_end marks the other lane's end before the run's first timing
+  // event; excl[l] is the timed run's last event, which lane l waits for before its next launch
+  hipEvent_t ev_end[kEvRing] = {};
+  hipEvent_t excl[kLanes] = {};
   // counting kernel: fp32 point-pair kernel with the float64 guard re-test (default), or the
   // plain float64 kernel (rs_f8_plan_set_count_precision; both give identical counts)
   rsd::Frame frame{1.0, 0.0, 0.0, 0.0, 0.0};
@@ -155,14 +180,9 @@ static void plan_free(rs_f8_plan *p) {
     if (b.h_tuples) (void)hipHostFree(b.h_tuples);
     if (b.ev_copy) (void)hipEventDestroy(b.ev_copy);
   }
-  for (int k = 0; k < rs_f8_plan::kBufs; ++k) {
-    if (p->ev_solve[k]) (void)hipEventDestroy(p->ev_solve[k]);
-    if (p->ev_count[k]) (void)hipEventDestroy(p->ev_count[k]);
-    if (p->ev_tail[k]) (void)hipEventDestroy(p->ev_tail[k]);
-  }
-  if (p->ev_np) (void)hipEventDestroy(p->ev_np);
-  if (p->ss) (void)hipStreamDestroy(p->ss);
-  if (p->ts) (void)hipStreamDestroy(p->ts);
+  for (auto &e : p->ev_end)
+    if (e) (void)hipEventDestroy(e);
+  if (p->lane1) (void)hipStreamDestroy(p->lane1);
   for (auto &h : p->h_slot)
     if (h) (void)hipHostFree(h);
   for (auto &h : p->h_inl)
@@ -249,18 +269,10 @@ extern "C" int rs_f8_plan_create(rs_ctx *c, int64_t n, int64_t max_hyp, rs_f8_pl
     for (auto &ev : r)
       if (e == hipSuccess) e = hipEventCreate(&ev);
   p->overlap = env_int("RSAMD_OVERLAP", kOverlapDefault) != 0;
-  if (p->overlap) {
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->ss, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->ts, hipStreamNonBlocking);
-    for (int k = 0; k < rs_f8_plan::kBufs; ++k) {
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_solve[k], hipEventDisableTiming);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_count[k], hipEventDisableTiming);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_tail[k], hipEventDisableTiming);
-    }
-  }
   p->nospec = env_int("RSAMD_NOSPEC", 0) != 0;
   p->ts_path = std::getenv("RSAMD_TSTAMP");
   if (p->ts_path) {
+    p->overlap = false;  // one device-global timeline buffer: one counting launch at a time
     const size_t tsb = sizeof(uint64_t) * rsd::kCountTsWords * (static_cast<size_t>(p->q_waves) * 64 + 1024);
     if (hipMalloc(&p->d_ts, tsb) == hipSuccess) {
       (void)hipMemset(p->d_ts, 0, tsb);
@@ -321,18 +333,69 @@ static int plan_retarget(rs_f8_plan *p, int64_t n) {
   return RS_OK;
 }
 
-// Enqueue the pending tail alone (no next run to ride along with), then wait for the stream.
+static hipStream_t lane_stream(const rs_f8_plan *p, int lane) {
+  return lane == 0 ? p->ctx->stream : p->lane1;
+}
+
+// Lane 1, and the events that mark a lane's end for the timed runs, at the first run placed on
+// it: a stream costs 15-30 ms to create, which single-run callers (rs_f8_ransac_np) never pay
+static hipError_t ensure_lane1(rs_f8_plan *p) {
+  if (p->lane1) return hipSuccess;
+  hipError_t e = hipStreamCreateWithFlags(&p->lane1, hipStreamNonBlocking);
+  for (auto &ev : p->ev_end)
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+  if (e != hipSuccess) {  // all or nothing: a later run tries again from scratch
+    for (auto &ev : p->ev_end) {
+      if (ev) (void)hipEventDestroy(ev);
+      ev = nullptr;
+    }
+    if (p->lane1) (void)hipStreamDestroy(p->lane1);
+    p->lane1 = nullptr;
+  }
+  return e;
+}
+
+// The last event of a timed run on the other lane, if this lane has not waited for it yet
+static hipError_t lane_excl_wait(rs_f8_plan *p, int lane) {
+  hipError_t e = hipSuccess;
+  if (p->excl[lane] && lane_stream(p, lane))
+    e = hipStreamWaitEvent(lane_stream(p, lane), p->excl[lane], 0);
+  p->excl[lane] = nullptr;
+  return e;
+}
+
+// The lane's pending tail in a launch of its own (no next solve to ride along with)
+static hipError_t lane_tail_alone(rs_f8_plan *p, int lane) {
+  if (!p->tail_pending[lane]) return hipSuccess;
+  hipError_t e = lane_excl_wait(p, lane);
+  if (e == hipSuccess)
+    e = rsd::launch_f8_tail_solve(&p->tail[lane], nullptr, lane_stream(p, lane));
+  p->tail_pending[lane] = false;
+  return e;
+}
+
+// Host wait for one lane, its pending tail included (the set guard and the parity entry points)
+static hipError_t lane_drain(rs_f8_plan *p, int lane) {
+  if (!p->busy[lane]) return hipSuccess;
+  hipError_t e = lane_tail_alone(p, lane);
+  if (e == hipSuccess) e = hipStreamSynchronize(lane_stream(p, lane));
+  p->busy[lane] = false;
+  p->synced[lane] = p->runs;
+  ++p->lane_waits;
+  return e;
+}
+
+// Enqueue both lanes' pending tails alone, then wait for both streams.
 static int plan_flush(rs_f8_plan *p) {
   HIP_TRY(hipSetDevice(p->ctx->device));
-  if (p->tail_pending) {
-    HIP_TRY(rsd::launch_f8_tail_solve(&p->tail, nullptr, p->ctx->stream));
-    p->tail_pending = false;
-  }
-  if (p->overlap) {
-    HIP_TRY(hipStreamSynchronize(p->ss));
-    HIP_TRY(hipStreamSynchronize(p->ts));
-  }
+  for (int l = 0; l < rs_f8_plan::kLanes; ++l) HIP_TRY(lane_tail_alone(p, l));
+  if (p->busy[1]) HIP_TRY(hipStreamSynchronize(p->lane1));
   HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+  for (int l = 0; l < rs_f8_plan::kLanes; ++l) {
+    p->busy[l] = false;
+    p->excl[l] = nullptr;
+    p->synced[l] = p->runs;
+  }
   p->pending = false;
   return RS_OK;
 }
@@ -399,11 +462,30 @@ static int plan_run(rs_f8_plan *p, int64_t H, int32_t mode, uint64_t seed, uint6
   p->timed[p->runs % rs_f8_plan::kEvRing] = tl >= 1;
   const int slot = static_cast<int>(p->runs % rs_f8_plan::kSlots);
   const bool fp32 = p->use_fp32 && p->fp32_ok;
-  hipStream_t ms = c->stream;
-  const int bi = static_cast<int>(p->runs % rs_f8_plan::kBufs);
-  // the solve's stream: ss in overlap mode, after the tail of this buffer set's previous run
-  hipStream_t sv = p->overlap ? p->ss : ms;
-  if (p->overlap) HIP_TRY(hipStreamWaitEvent(sv, p->ev_tail[bi], 0));
+  // lane choice: lane 0 when nothing is in flight, else the lane the previous run did not use;
+  // device tuples were written on the context stream, so their run follows them on lane 0
+  // (its entry point has drained lane 1 before the parse)
+  int lane = 0;
+  if (dev_tuples)
+    HIP_TRY(lane_drain(p, 1));
+  else if (p->overlap && p->pending)
+    lane = 1 - p->last_lane;
+  const int other = 1 - lane;
+  if (lane == 1) HIP_TRY(ensure_lane1(p));
+  hipStream_t ms = lane_stream(p, lane);
+  // set guard: the set's last run went to the other lane and the host has not waited for that
+  // lane since, so it may still be in flight there.  Taken only after a parity entry point broke
+  // the alternation: in a Philox or host-tuple sequence the set's last run either used this
+  // lane (stream order covers it) or preceded a plan_flush, after which lane and set parity may
+  // differ from the recorded ones without any work left to wait for
+  if (b.lane != lane && b.last_run >= p->synced[b.lane]) HIP_TRY(lane_drain(p, b.lane));
+  b.lane = lane;
+  b.last_run = p->runs;
+  HIP_TRY(lane_excl_wait(p, lane));
+  // a timed run counts alone: its lane waits here for the other lane's current end, and the
+  // other lane waits for the run's last event before its next launch
+  const bool excl = tl >= 1 && p->busy[other];
+  hipEvent_t ev_end = excl ? p->ev_end[p->runs % rs_f8_plan::kEvRing] : nullptr;
 
   if (mode == RS_SAMPLER_TUPLES && !dev_tuples) {
     // stage through the set's pinned buffer: the copy no longer reads caller memory after
@@ -422,12 +504,13 @@ static int plan_run(rs_f8_plan *p, int64_t H, int32_t mode, uint64_t seed, uint6
     if (!b.ev_copy) HIP_TRY(hipEventCreateWithFlags(&b.ev_copy, hipEventDisableTiming));
     std::memcpy(b.h_tuples, host_tuples, sizeof(int) * 8 * H);
     HIP_TRY(hipMemcpyAsync(b.d_tuples, b.h_tuples, sizeof(int) * 8 * H, hipMemcpyHostToDevice,
-                           sv));
-    HIP_TRY(hipEventRecord(b.ev_copy, sv));
+                           ms));
+    HIP_TRY(hipEventRecord(b.ev_copy, ms));
     b.copy_pending = true;
   }
-  // [tail of the previous run | solve of this run]: buffer set b was last read by run k-2,
-  // whose tail is complete (stream order)
+  // [tail of the lane's previous run | solve of this run]: buffer set b was last used kBufs
+  // runs back, on this lane (or on one drained above), and that run's tail precedes this
+  // launch in stream order
   rsd::SolveArgs sa{};
   sa.pts = p->d_pts;
   sa.n = n;
@@ -450,16 +533,21 @@ static int plan_run(rs_f8_plan *p, int64_t H, int32_t mode, uint64_t seed, uint6
     sa.gDe = gb.De;
     sa.gDn = gb.Dn;
   }
-  if (tl >= 2) HIP_TRY(hipEventRecord(ev[2], sv));
-  HIP_TRY(rsd::launch_f8_tail_solve(p->tail_pending ? &p->tail : nullptr, &sa, sv, p->tail_cus));
-  p->tail_pending = false;
-  if (tl >= 2) HIP_TRY(hipEventRecord(ev[3], sv));
-  if (p->overlap) {
-    HIP_TRY(hipEventRecord(p->ev_solve[bi], sv));
-    HIP_TRY(hipStreamWaitEvent(ms, p->ev_solve[bi], 0));
+  if (excl && tl >= 2) {
+    HIP_TRY(hipEventRecord(ev_end, lane_stream(p, other)));
+    HIP_TRY(hipStreamWaitEvent(ms, ev_end, 0));
   }
+  if (tl >= 2) HIP_TRY(hipEventRecord(ev[2], ms));
+  HIP_TRY(rsd::launch_f8_tail_solve(p->tail_pending[lane] ? &p->tail[lane] : nullptr, &sa, ms,
+                                    p->tail_cus));
+  p->tail_pending[lane] = false;
+  if (tl >= 2) HIP_TRY(hipEventRecord(ev[3], ms));
 
   // counts of this run
+  if (excl && tl == 1) {
+    HIP_TRY(hipEventRecord(ev_end, lane_stream(p, other)));
+    HIP_TRY(hipStreamWaitEvent(ms, ev_end, 0));
+  }
   if (tl >= 1) HIP_TRY(hipEventRecord(ev[0], ms));
   if (fp32) {
     // fused c*: the chunk that completes a hypothesis group folds its max into status[0]
@@ -473,9 +561,10 @@ static int plan_run(rs_f8_plan *p, int64_t H, int32_t mode, uint64_t seed, uint6
     HIP_TRY(rsd::launch_f8_max(b.d_counts, h, b.d_status, ms));
   }
   if (tl >= 1) HIP_TRY(hipEventRecord(ev[1], ms));
+  if (tl >= 1 && p->overlap) p->excl[other] = ev[1];
 
-  // this run's tail rides along with the next run's solve (or plan_flush)
-  rsd::TailArgs &ta = p->tail;
+  // this run's tail rides along with the lane's next solve (or plan_flush)
+  rsd::TailArgs &ta = p->tail[lane];
   ta = rsd::TailArgs{};
   ta.pts = p->d_pts;
   ta.n = n;
@@ -497,15 +586,9 @@ static int plan_run(rs_f8_plan *p, int64_t H, int32_t mode, uint64_t seed, uint6
   ta.res = b.d_res;
   ta.hres = p->h_slot_dev[slot];
   ta.hinl = p->h_inl_dev[slot];
-  if (p->overlap) {
-    // the tail on ts right after this run's count; the next run's count does not wait for it
-    HIP_TRY(hipEventRecord(p->ev_count[bi], ms));
-    HIP_TRY(hipStreamWaitEvent(p->ts, p->ev_count[bi], 0));
-    HIP_TRY(rsd::launch_f8_tail_solve(&ta, nullptr, p->ts, p->tail_cus));
-    HIP_TRY(hipEventRecord(p->ev_tail[bi], p->ts));
-  } else {
-    p->tail_pending = true;
-  }
+  p->tail_pending[lane] = true;
+  p->busy[lane] = true;
+  p->last_lane = lane;
   ++p->runs;
   p->last_H = H;
   p->pending = true;
@@ -519,8 +602,8 @@ extern "C" int rs_f8_plan_run(rs_f8_plan *p, int64_t H, int32_t mode, uint64_t s
 
 // Parity mode with the numpy stream sampled on the GPU (np_sampler.hip) straight into the
 // tuple buffer of the run about to be issued; advances (key, pos).  The sampler is synchronous
-// on the context stream, and that buffer set was last read by run k-2's solve, which precedes
-// it in stream order.  Populations beyond the GPU parse's range (and RSAMD_NP_HOST, a test
+// on the context stream, and that buffer set was last read by the solve of run k-kBufs, which
+// precedes it in stream order on lane 0 or ran on lane 1, drained here.  Populations beyond the GPU parse's range (and RSAMD_NP_HOST, a test
 // hook) go through the host replay.
 extern "C" int rs_f8_plan_run_np_slice(rs_f8_plan *p, int64_t H, int64_t start, int64_t count,
                                        uint32_t *key, int32_t *pos, double thresh) {
@@ -530,7 +613,10 @@ extern "C" int rs_f8_plan_run_np_slice(rs_f8_plan *p, int64_t H, int64_t start, 
   if (count > p->max_hyp) return fail(RS_EINVAL, "hypothesis count out of plan range");
   int st;
   if (rs::np_gpu_supported(p->n, 8) && std::getenv("RSAMD_NP_HOST") == nullptr) {
-    if (p->overlap) HIP_TRY(hipEventSynchronize(p->ev_solve[p->runs % rs_f8_plan::kBufs]));
+    // the parse writes the run's tuples on the context stream: lane 1 is drained first (its
+    // last run may have used this set), the run follows the parse on lane 0
+    HIP_TRY(hipSetDevice(p->ctx->device));
+    HIP_TRY(lane_drain(p, 1));
     if (start == 0 && count == H && std::getenv("RSAMD_NP_SYNC") == nullptr) {
       // the whole draw in one segment: the run is queued behind the parse before the host
       // waits for the parse's outcome (no host gap between them); should the parse ask to be
@@ -540,16 +626,10 @@ extern "C" int rs_f8_plan_run_np_slice(rs_f8_plan *p, int64_t H, int64_t start, 
       if ((st = rs::np_choice_enqueue(p->ctx, key, *pos, p->n, 8, H, b.d_tuples, &queued)))
         return st;
       if (queued) {
-        if (p->overlap) {  // the solve's stream reads the tuples after the parse
-          if (!p->ev_np) HIP_TRY(hipEventCreateWithFlags(&p->ev_np, hipEventDisableTiming));
-          HIP_TRY(hipEventRecord(p->ev_np, p->ctx->stream));
-          HIP_TRY(hipStreamWaitEvent(p->ss, p->ev_np, 0));
-        }
         const int run_st = plan_run(p, count, RS_SAMPLER_TUPLES, 0, 0, nullptr, thresh, true);
         bool rerun = false;
         if ((st = rs::np_choice_finish(p->ctx, key, pos, &rerun))) return st;
         if (run_st || !rerun) return run_st;
-        if (p->overlap) HIP_TRY(hipEventSynchronize(p->ev_solve[p->runs % rs_f8_plan::kBufs]));
       }
     }
     RunBufs &b = p->buf[p->runs % rs_f8_plan::kBufs];
@@ -574,7 +654,8 @@ extern "C" int rs_f8_plan_run_np_shard(rs_f8_plan *p, rs_np_shard *sh, int64_t b
   const int64_t count = hi - base;
   if (count > p->max_hyp) return fail(RS_EINVAL, "hypothesis count out of plan range");
   RunBufs &b = p->buf[p->runs % rs_f8_plan::kBufs];
-  if (p->overlap) HIP_TRY(hipEventSynchronize(p->ev_solve[p->runs % rs_f8_plan::kBufs]));
+  HIP_TRY(hipSetDevice(p->ctx->device));
+  HIP_TRY(lane_drain(p, 1));  // the tuples are written on the context stream (lane 0)
   int st;
   if ((st = rs::np_shard_tuples_device(sh, base, hi, next_start, final_idx,
                                        count > 0 ? b.d_tuples : nullptr, key_out, pos_out)))
@@ -622,17 +703,9 @@ extern "C" int rs_f8_plan_result(rs_f8_plan *p, rs_f8_result *out, int64_t *inli
   if (n_inliers) *n_inliers = r->n_inliers;
   const int64_t k = std::min<int64_t>(cap, r->n_inliers);
   if (inliers && k > 0) {
-    if (const int *h = p->h_inl[(p->runs - 1) % rs_f8_plan::kSlots]) {  // written by the tail
-      for (int64_t i = 0; i < k; ++i) inliers[i] = h[i];
-    } else if (r->inl_row >= 0) {   // the winner's select block kept it (int32 row)
-      std::vector<int32_t> row(static_cast<size_t>(k));
-      HIP_TRY(hipMemcpy(row.data(), p->last().d_spec + r->inl_row * p->n, sizeof(int32_t) * k,
-                        hipMemcpyDeviceToHost));
-      for (int64_t i = 0; i < k; ++i) inliers[i] = row[static_cast<size_t>(i)];
-    } else {
-      HIP_TRY(hipMemcpy(inliers, p->last().d_res->inliers, sizeof(int64_t) * k,
-                        hipMemcpyDeviceToHost));
-    }
+    const int *h = p->h_inl[(p->runs - 1) % rs_f8_plan::kSlots];  // written by the tail
+    if (!h) return fail(RS_EINVAL, "the plan's buffers are gone (a failed retarget)");
+    for (int64_t i = 0; i < k; ++i) inliers[i] = h[i];
   }
   return RS_OK;
 }
@@ -754,6 +827,12 @@ extern "C" int rs_f8_plan_set_timing(rs_f8_plan *p, int32_t level, int32_t every
   if (level < 0 || level > 2 || every < 1) return fail(RS_EINVAL, "bad timing level / period");
   p->timing = level;
   p->timing_every = every;
+  return RS_OK;
+}
+
+extern "C" int rs_f8_plan_lane_waits(rs_f8_plan *p, int64_t *waits) {
+  if (!p || !waits) return fail(RS_EINVAL, "null pointer");
+  *waits = p->lane_waits;
   return RS_OK;
 }
 

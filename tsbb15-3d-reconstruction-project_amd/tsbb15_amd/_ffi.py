@@ -121,6 +121,7 @@ _SIGS = {
     "rs_f8_plan_kernel_ms": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     "rs_f8_plan_kernel_avg": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp, _dp]),
     "rs_f8_plan_set_timing": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "rs_f8_plan_lane_waits": (C.c_int, [C.c_void_p, _i64p]),
     "rs_f8_plan_set_count_precision": (C.c_int, [C.c_void_p, C.c_int32]),
     "rs_f8_ransac_np": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64, _u32p, _i32p,
                                   C.c_double, C.POINTER(F8Result), _i64p, C.c_int64, _i64p]),
@@ -208,7 +209,15 @@ def lib():
                         "__graft_entry__.build()); there is no CPU fallback")
                 L = C.CDLL(LIB_PATH)
                 for name, (res, args) in _SIGS.items():
-                    fn = getattr(L, name)
+                    try:
+                        fn = getattr(L, name)
+                    except AttributeError:
+                        # an A/B library built from an earlier commit (RSAMD_LIB) may lack the
+                        # newest entry points; calling one still raises.  The product library
+                        # must export them all
+                        if "RSAMD_LIB" in os.environ:
+                            continue
+                        raise
                     fn.restype = res
                     fn.argtypes = args
                 _lib = L
@@ -625,6 +634,13 @@ class F8Plan:
         """HIP timing events per run: level 0 none, 1 counting kernel, 2 also solve / run;
         recorded on every ``every``-th run (each event is a marker packet between kernels)."""
         check(lib().rs_f8_plan_set_timing(self._h, int(level), int(every)))
+
+    def lane_waits(self):
+        """Host waits for one stream lane outside result() and the other synchronising calls
+        (0 in any sequence of Philox and host-tuple runs)."""
+        k = C.c_int64(0)
+        check(lib().rs_f8_plan_lane_waits(self._h, C.byref(k)))
+        return k.value
 
     def kernel_ms(self, last_n=1):
         """Device times of the last run, or averaged over the last ``last_n`` runs."""
