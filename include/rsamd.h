@@ -558,7 +558,25 @@ int rs_bundle_adjust(rs_ctx *ctx, double *cams, int64_t nC, double *pts, int64_t
                      const int32_t *obs_view, const int32_t *obs_point, const double *uv,
                      int64_t n, int32_t max_iter, double ftol, rs_ba_info *info);
 
-/* HIP events between the kernels of the next rs_bundle_adjust calls (enable != 0).  Returns the
+/* Bundle adjustment over rigid poses: the objective, LM rules, Schur structure, layouts, limits,
+ * rs_ba_info and determinism of rs_bundle_adjust, with 6 local coordinates per camera in place
+ * of 12 free entries.  Camera k is [R | t]; the update delta = (omega, tau) acts on the left,
+ *   R+ = Exp(omega) R,  t+ = Exp(omega) t + tau   (so Xc+ = Exp(omega) Xc + tau),
+ * Exp = I + A K + B K^2 with K = [omega]x, A = sin th / th, B = (sin(th/2) / (th/2))^2 / 2
+ * (their series below th^2 = 1e-12).  With Xc = (x, y, z), a = x/z, b = y/z, iz = 1/z:
+ *   d r / d delta = -[[-ab, 1+a^2, -b, iz, 0, -a iz], [-(1+b^2), ab, a, 0, iz, -b iz]].
+ * R is never re-orthonormalised: Exp(omega) R keeps R^T R = I to rounding.  Only the global
+ * scale remains as gauge; it is left to the damping.  The free cameras are cameras 1.. with an
+ * observation; camera 0, unobserved cameras and unobserved points come back bit for bit and are
+ * not looked at.  RS_EINVAL as rs_bundle_adjust, and for a free camera whose R has
+ * max |R^T R - I| > 1e-6 or det R <= 0 (the message names the camera).  cams go in and come
+ * out as (nC, 3, 4).  rs_ba_timing covers this call with the same 8 slots. */
+int rs_bundle_adjust_rigid(rs_ctx *ctx, double *cams, int64_t nC, double *pts, int64_t nP,
+                           const int32_t *obs_view, const int32_t *obs_point, const double *uv,
+                           int64_t n, int32_t max_iter, double ftol, rs_ba_info *info);
+
+/* HIP events between the kernels of the next rs_bundle_adjust / rs_bundle_adjust_rigid calls
+ * (enable != 0; the rigid call's linearisation counts in the k_ba_linearize slot).  Returns the
  * last timed call's device ms summed per kernel -- k_ba_linearize, k_ba_camera, k_ba_pointsum,
  * k_ba_point, k_ba_schur, k_ba_chol, k_ba_step, k_ba_cost + k_ba_final -- and its trials. */
 #define RS_BA_TIMING_SLOTS 8

@@ -7,6 +7,12 @@ frame; point j is seen by 2 + j % 35 consecutive views starting at view j % 36; 
 shuffled; uv = exact projection + `--noise` N(0, 1); the start perturbs cameras 1.. and the
 points by `--sigma` N(0, 1).
 
+`--rigid` times tsbb15_amd.tables.bundle_adjust_rigid (rs_bundle_adjust_rigid) on the same
+table instead, the start turned into rotations by tests/ba_rigid_fixture.rigid_start
+(Exp(sigma n) R, t + sigma n, X + sigma n), against tests/ba_rigid_ref.py, and writes
+profiles/ba_rigid_bench.json.  The two problems take different LM paths: compare the time per
+trial as well as per call.
+
 GPU figures: the wall time of whole calls (host clock around the synchronous call: upload, host
 CSR build, LM loop, download), and, from a separate call with rs_ba_timing on, the device time
 per kernel summed over the call (HIP events between the kernels).  Needs a GPU; there is no
@@ -21,12 +27,13 @@ import time
 import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (REPO, os.path.join(REPO, "tsbb15-3d-reconstruction-project_amd")):
+for p in (REPO, os.path.join(REPO, "tests"),
+          os.path.join(REPO, "tsbb15-3d-reconstruction-project_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
 
-def dino_problem(nC=36, nP=676, noise=1e-4, sigma=1e-3, seed=0):
+def dino_problem(nC=36, nP=676, noise=1e-4, sigma=1e-3, seed=0, rigid=False):
     z = np.load(os.path.join(REPO, "tests", "golden", "dino_pnp_kat.npz"))
     R, t, X = z["R"][:nC], z["t"][:nC], z["points3d"][:nP]
     cams = np.empty((nC, 3, 4))
@@ -43,6 +50,10 @@ def dino_problem(nC=36, nP=676, noise=1e-4, sigma=1e-3, seed=0):
     xh = np.hstack([pts[op], np.ones((len(op), 1))])
     y = np.einsum('nij,nj->ni', cams[ov], xh)
     uv = y[:, :2] / y[:, 2:3] + noise * rng.standard_normal((len(ov), 2))
+    if rigid:
+        import ba_rigid_fixture as rf
+        cams0, pts0 = rf.rigid_start({"cams": cams, "pts": pts}, sigma, seed=seed)
+        return cams0, pts0, ov, op, uv
     cams0, pts0 = cams.copy(), pts.copy()
     cams0[1:] += sigma * rng.standard_normal(cams0[1:].shape)
     pts0 += sigma * rng.standard_normal(pts0.shape)
@@ -56,30 +67,40 @@ def main():
     ap.add_argument("--noise", type=float, default=1e-4)
     ap.add_argument("--sigma", type=float, default=1e-3)
     ap.add_argument("--no-oracle", action="store_true", help="skip the CPU oracle run")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ba_bench.json"))
+    ap.add_argument("--rigid", action="store_true",
+                    help="time bundle_adjust_rigid from a rigid start")
+    ap.add_argument("--out", default=None,
+                    help="default profiles/ba_bench.json, profiles/ba_rigid_bench.json with --rigid")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(REPO, "profiles", "ba_rigid_bench.json" if a.rigid else "ba_bench.json")
 
     from tsbb15_amd import _ffi
     from tsbb15_amd import tables as gt
     if _ffi.device_count() < 1:
         raise SystemExit("bench_ba: no GPU visible")
     ctx = _ffi.default_context()
-    cams0, pts0, ov, op, uv = dino_problem(noise=a.noise, sigma=a.sigma)
+    cams0, pts0, ov, op, uv = dino_problem(noise=a.noise, sigma=a.sigma, rigid=a.rigid)
+    adjust = gt.bundle_adjust_rigid if a.rigid else gt.bundle_adjust
     res = {"problem": {"cameras": len(cams0), "points": len(pts0), "observations": len(ov),
-                       "reduced_system": 12 * (len(cams0) - 1), "noise": a.noise,
-                       "sigma": a.sigma, "max_iter": a.max_iter}}
+                       "reduced_system": (6 if a.rigid else 12) * (len(cams0) - 1),
+                       "noise": a.noise, "sigma": a.sigma, "max_iter": a.max_iter,
+                       "entry": adjust.__name__}}
     print(f"bench_ba: {res['problem']}", flush=True)
 
-    gt.bundle_adjust(cams0, pts0, ov, op, uv, max_iter=a.max_iter, ctx=ctx)      # warm-up
+    adjust(cams0, pts0, ov, op, uv, max_iter=a.max_iter, ctx=ctx)      # warm-up
     wall = []
     for _ in range(a.repeats):
         t0 = time.perf_counter()
-        c1, p1, info = gt.bundle_adjust(cams0, pts0, ov, op, uv, max_iter=a.max_iter, ctx=ctx)
+        c1, p1, info = adjust(cams0, pts0, ov, op, uv, max_iter=a.max_iter, ctx=ctx)
         wall.append((time.perf_counter() - t0) * 1e3)
     _ffi.ba_timing(ctx, True)
-    c2, p2, info2 = gt.bundle_adjust(cams0, pts0, ov, op, uv, max_iter=a.max_iter, ctx=ctx)
+    c2, p2, info2 = adjust(cams0, pts0, ov, op, uv, max_iter=a.max_iter, ctx=ctx)
     ms, trials = _ffi.ba_timing(ctx, False)
     assert c2.tobytes() == c1.tobytes() and p2.tobytes() == p1.tobytes() and info2 == info
+    if a.rigid:
+        R = c1[:, :, :3]
+        res["max_RtR_minus_I"] = float(np.abs(np.einsum('kji,kjl->kil', R, R) - np.eye(3)).max())
     res["gpu"] = {"info": info, "trials": trials, "wall_ms": [round(w, 3) for w in wall],
                   "wall_ms_median": round(float(np.median(wall)), 3),
                   "wall_ms_per_trial": round(float(np.median(wall)) / max(trials, 1), 4),
@@ -91,10 +112,14 @@ def main():
     print(f"bench_ba: gpu {res['gpu']}", flush=True)
 
     if not a.no_oracle:
-        from oracle import tables_ref as tr
+        if a.rigid:
+            import ba_rigid_ref as tr
+            lm = tr.bundle_adjust_rigid_lm
+        else:
+            from oracle import tables_ref as tr
+            lm = tr.bundle_adjust_lm
         t0 = time.perf_counter()
-        _, _, iref = tr.bundle_adjust_lm(cams0, pts0, ov, op, uv[:, 0], uv[:, 1],
-                                         max_iter=a.max_iter)
+        _, _, iref = lm(cams0, pts0, ov, op, uv[:, 0], uv[:, 1], max_iter=a.max_iter)
         sec = time.perf_counter() - t0
         res["oracle_cpu"] = {"info": iref, "seconds": round(sec, 2),
                              "cost_rel_diff": abs(info["cost"] - iref["cost"]) / iref["cost"]}

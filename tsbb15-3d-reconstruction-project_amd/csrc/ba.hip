@@ -25,6 +25,14 @@
 //   k_ba_cost        lane per observation: squared trial residual
 //   k_ba_final       one workgroup: cost and predicted reduction by fixed-order reductions,
 //                    the status record into pinned host memory
+//
+// Rigid cameras (rs_bundle_adjust_rigid).  The same loop over 6 local coordinates per camera,
+// delta = (omega, tau) with R+ = Exp(omega) R, t+ = Exp(omega) t + tau.  The camera block width
+// is the template parameter D of k_ba_camera, k_ba_point, k_ba_schur, k_ba_chol, k_ba_step and
+// k_ba_final: D = 12 is the code above, unchanged; D = 6 linearises with k_ba_linearize_rigid
+// (3 generators a, b, 1/z per observation), runs k_ba_camera and k_ba_schur in one wave per
+// block (36 + 6 workers), pads the reduced system to whole 12-wide block columns with an
+// identity diagonal and a zero right-hand side, and retracts in k_ba_step.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -54,6 +62,53 @@ __device__ __forceinline__ double ba_jc(const double *j6, int row, int k) {
   if (grp == 2) return g * j6[4 + row];
   return grp == row ? -g : 0.0;
 }
+
+// Rigid cameras: entry f = 6 row + k of the 2 x 6 Jc = d r / d (omega, tau) at delta = 0, from
+// j3 = (a, b, iz) of Xc = R X + t = (x, y, z), a = x / z, b = y / z, iz = 1 / z:
+// Jc[0] = [ab, -(1 + a^2), b, -iz, 0, a iz], Jc[1] = [1 + b^2, -ab, -a, 0, -iz, b iz].
+__device__ __forceinline__ double ba_jc6(const double *j3, int f) {
+  const double a = j3[0], b = j3[1], iz = j3[2];
+  switch (f) {
+    case 0: return a * b;
+    case 1: return -(1.0 + a * a);
+    case 2: return b;
+    case 3: return -iz;
+    case 5: return a * iz;
+    case 6: return 1.0 + b * b;
+    case 7: return -(a * b);
+    case 8: return -a;
+    case 10: return -iz;
+    case 11: return b * iz;
+    default: return 0.0;
+  }
+}
+
+// E = Exp(w) = I + A K + B K^2 of K = [w]x: A = sin t / t, B = (sin(t/2) / (t/2))^2 / 2 (no
+// 1 - cos cancellation), by their series below t^2 = 1e-12.  K^2 = w w^T - t^2 I.
+__device__ __forceinline__ void ba_exp_so3(const double *w, double *E) {
+  const double t2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+  double A, B;
+  if (t2 < 1e-12) {
+    A = 1.0 - t2 / 6.0;
+    B = 0.5 - t2 / 24.0;
+  } else {
+    const double t = sqrt(t2), h = 0.5 * t, sh = sin(h) / h;
+    A = sin(t) / t;
+    B = 0.5 * sh * sh;
+  }
+  E[0] = 1.0 + B * (w[0] * w[0] - t2);
+  E[1] = B * (w[0] * w[1]) - A * w[2];
+  E[2] = B * (w[0] * w[2]) + A * w[1];
+  E[3] = B * (w[0] * w[1]) + A * w[2];
+  E[4] = 1.0 + B * (w[1] * w[1] - t2);
+  E[5] = B * (w[1] * w[2]) - A * w[0];
+  E[6] = B * (w[0] * w[2]) - A * w[1];
+  E[7] = B * (w[1] * w[2]) + A * w[0];
+  E[8] = 1.0 + B * (w[2] * w[2] - t2);
+}
+
+// Threads of a k_ba_camera / k_ba_schur workgroup: D * D + D workers, in whole waves.
+constexpr int ba_block_threads(int D) { return D == 12 ? 192 : 64; }
 
 // v of lane `lane` (wave-uniform) in every lane.
 __device__ __forceinline__ double ba_bcast(double v, int lane) {
@@ -139,44 +194,105 @@ __global__ __launch_bounds__(256) void k_ba_linearize(
     }
 }
 
+// Rigid cameras: r, the 3 generators (a, b, iz), Jp = -Pi R (the arithmetic of k_ba_linearize:
+// with nC == 1 both paths give the same bits) and W = Jc^T Jp (6 x 3).
+__global__ __launch_bounds__(256) void k_ba_linearize_rigid(
+    const double *__restrict__ cams, const double *__restrict__ pts,
+    const int32_t *__restrict__ ov, const int32_t *__restrict__ op,
+    const double *__restrict__ uv, int n, double *__restrict__ r, double *__restrict__ jcs,
+    double *__restrict__ Jp, double *__restrict__ W) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double *c = cams + 12 * ov[i];
+  const double *p = pts + 3 * op[i];
+  const double xh[4] = {p[0], p[1], p[2], 1.0};
+  const double a = c[0] * xh[0] + c[1] * xh[1] + c[2] * xh[2] + c[3];
+  const double b = c[4] * xh[0] + c[5] * xh[1] + c[6] * xh[2] + c[7];
+  const double w = c[8] * xh[0] + c[9] * xh[1] + c[10] * xh[2] + c[11];
+  const double iw = 1.0 / w, iw2 = iw * iw;
+  const double aw = a / w, bw = b / w;
+  r[2 * i] = uv[2 * i] - aw;
+  r[2 * i + 1] = uv[2 * i + 1] - bw;
+  double j0[3], j1[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    j0[k] = -(c[k] * w - a * c[8 + k]) * iw2;
+    j1[k] = -(c[4 + k] * w - b * c[8 + k]) * iw2;
+  }
+  double *j3 = jcs + 3 * static_cast<int64_t>(i);
+  j3[0] = aw;
+  j3[1] = bw;
+  j3[2] = iw;
+  double *jp = Jp + 6 * static_cast<int64_t>(i);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    jp[k] = j0[k];
+    jp[3 + k] = j1[k];
+  }
+  const double g[3] = {aw, bw, iw};
+  double *wi = W + 18 * static_cast<int64_t>(i);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const double c0 = ba_jc6(g, k), c1 = ba_jc6(g, 6 + k);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) wi[3 * k + q] = c0 * j0[q] + c1 * j1[q];
+  }
+}
+
 // U_c = sum Jc^T Jc and g_c = sum Jc^T r over the camera's observations, in CSR order.  The
 // row is staged through LDS in tiles (generators and residual of each observation, gathered
-// by all threads); every thread then walks the tile in order for its own entry.
-__global__ __launch_bounds__(192) void k_ba_camera(
+// by all threads); every thread then walks the tile in order for its own entry.  D = 6 stages
+// the 2 x 6 Jc itself (each entry formed once from the 3 generators) and runs in one wave.
+template <int D>
+__global__ __launch_bounds__(ba_block_threads(D)) void k_ba_camera(
     const int32_t *__restrict__ cam_of_slot, const int32_t *__restrict__ cam_off,
     const int32_t *__restrict__ cam_obs, const double *__restrict__ jcs,
     const double *__restrict__ r, double *__restrict__ U, double *__restrict__ gc) {
-  __shared__ double sj[kBaCamTile * 8];
+  constexpr int DD = D * D, NT = ba_block_threads(D), F = D == 12 ? 8 : 14;
+  __shared__ double sj[kBaCamTile * F];
   const int slot = blockIdx.x, tid = threadIdx.x;
   const int cam = cam_of_slot[slot];
   const int lo = cam_off[slot], hi = cam_off[slot + 1];
-  const int rr = tid < 144 ? tid / 12 : tid - 144, cc = tid % 12;
+  const int rr = tid < DD ? tid / D : tid - DD, cc = tid % D;
   double s = 0.0;
   for (int base = lo; base < hi; base += kBaCamTile) {
     const int cnt = min(kBaCamTile, hi - base);
     __syncthreads();
-    for (int idx = tid; idx < cnt * 8; idx += 192) {
-      const int64_t i = cam_obs[base + idx / 8];
-      const int f = idx % 8;
-      sj[idx] = f < 6 ? jcs[6 * i + f] : r[2 * i + f - 6];
+    for (int idx = tid; idx < cnt * F; idx += NT) {
+      const int64_t i = cam_obs[base + idx / F];
+      const int f = idx % F;
+      if constexpr (D == 12)
+        sj[idx] = f < 6 ? jcs[6 * i + f] : r[2 * i + f - 6];
+      else
+        sj[idx] = f < 12 ? ba_jc6(jcs + 3 * i, f) : r[2 * i + f - 12];
     }
     __syncthreads();
-    if (tid < 144) {
+    if (tid < DD) {
       for (int o = 0; o < cnt; ++o) {
-        const double *j6 = sj + 8 * o;
-        s += ba_jc(j6, 0, rr) * ba_jc(j6, 0, cc) + ba_jc(j6, 1, rr) * ba_jc(j6, 1, cc);
+        if constexpr (D == 12) {
+          const double *j6 = sj + 8 * o;
+          s += ba_jc(j6, 0, rr) * ba_jc(j6, 0, cc) + ba_jc(j6, 1, rr) * ba_jc(j6, 1, cc);
+        } else {
+          const double *j = sj + 14 * o;
+          s += j[rr] * j[cc] + j[6 + rr] * j[6 + cc];
+        }
       }
-    } else if (tid < 156) {
+    } else if (tid < DD + D) {
       for (int o = 0; o < cnt; ++o) {
-        const double *j6 = sj + 8 * o;
-        s += ba_jc(j6, 0, rr) * j6[6] + ba_jc(j6, 1, rr) * j6[7];
+        if constexpr (D == 12) {
+          const double *j6 = sj + 8 * o;
+          s += ba_jc(j6, 0, rr) * j6[6] + ba_jc(j6, 1, rr) * j6[7];
+        } else {
+          const double *j = sj + 14 * o;
+          s += j[rr] * j[12] + j[6 + rr] * j[13];
+        }
       }
     }
   }
-  if (tid < 144)
-    U[144 * cam + tid] = s;
-  else if (tid < 156)
-    gc[12 * cam + rr] = s;
+  if (tid < DD)
+    U[DD * cam + tid] = s;
+  else if (tid < DD + D)
+    gc[D * cam + rr] = s;
 }
 
 // V_p = sum Jp^T Jp (00 01 02 11 12 22) and g_p = sum Jp^T r over the point's observations.
@@ -207,7 +323,8 @@ __global__ __launch_bounds__(256) void k_ba_pointsum(
 }
 
 // Y_i = W_i V*^-1 of the observation's point; the first observation of each point also keeps
-// V*^-1 for k_ba_step and reports a non-positive pivot.
+// V*^-1 for k_ba_step and reports a non-positive pivot.  W_i and Y_i are D x 3.
+template <int D>
 __global__ __launch_bounds__(256) void k_ba_point(
     const int32_t *__restrict__ op, const int32_t *__restrict__ pt_off,
     const int32_t *__restrict__ pt_obs, int n, const double *__restrict__ V, double lam,
@@ -223,10 +340,10 @@ __global__ __launch_bounds__(256) void k_ba_point(
     for (int q = 0; q < 6; ++q) Vinv[6 * p + q] = vi[q];
     if (!ok) flag[0] = 1;
   }
-  const double *w = W + 36 * static_cast<int64_t>(i);
-  double *y = Y + 36 * static_cast<int64_t>(i);
+  const double *w = W + 3 * D * static_cast<int64_t>(i);
+  double *y = Y + 3 * D * static_cast<int64_t>(i);
 #pragma unroll
-  for (int k = 0; k < 12; ++k) {
+  for (int k = 0; k < D; ++k) {
     const double w0 = w[3 * k], w1 = w[3 * k + 1], w2 = w[3 * k + 2];
     y[3 * k] = w0 * vi[0] + w1 * vi[1] + w2 * vi[2];
     y[3 * k + 1] = w0 * vi[1] + w1 * vi[3] + w2 * vi[4];
@@ -237,8 +354,11 @@ __global__ __launch_bounds__(256) void k_ba_point(
 // The reduced system, lower triangle, element (i, m), i >= m, at S[m * ld + i]; row N (ld =
 // N + 1) is the right-hand side -g_c + sum_i Y_i g_p.  Block pair `blockIdx.x` in the order
 // (0,0) (0,1) .. (0,nf-1) (1,1) ..; its (i, j) observation pairs ent[pair_off[.] ..] are sorted
-// by point.
-__global__ __launch_bounds__(192) void k_ba_schur(
+// by point.  D = 6 runs in one wave; ld - 1 may then exceed 6 nf (the system padded to whole
+// block columns of k_ba_chol): the first workgroup writes the pad, an identity diagonal and a
+// zero right-hand side.
+template <int D>
+__global__ __launch_bounds__(ba_block_threads(D)) void k_ba_schur(
     int nf, const int64_t *__restrict__ pair_off, const int32_t *__restrict__ ent,
     const double *__restrict__ Y, const double *__restrict__ W, const double *__restrict__ U,
     const double *__restrict__ gc, const double *__restrict__ gp,
@@ -252,58 +372,67 @@ __global__ __launch_bounds__(192) void k_ba_schur(
   }
   const int b = a + rest, tid = threadIdx.x;
   const int N = ld - 1;
-  __shared__ double sy[kBaSchurTile * 36], sw[kBaSchurTile * 36];
-  const int rr = tid / 12, cc = tid % 12;
+  constexpr int DD = D * D, D3 = 3 * D, NT = ba_block_threads(D);
+  __shared__ double sy[kBaSchurTile * D3], sw[kBaSchurTile * D3];
+  const int rr = tid / D, cc = tid % D;
+  if constexpr (D != 12) {
+    if (blockIdx.x == 0)
+      for (int i = D * nf; i < N; ++i) {
+        // row and column i of the symmetric matrix, and its right-hand side (column N)
+        for (int m = tid; m <= N; m += NT) S[static_cast<int64_t>(i) * ld + m] = m == i ? 1.0 : 0.0;
+        for (int m = tid; m < i; m += NT) S[static_cast<int64_t>(m) * ld + i] = 0.0;
+      }
+  }
   double s = 0.0;
   const int64_t lo = pair_off[blockIdx.x], hi = pair_off[blockIdx.x + 1];
   for (int64_t e0 = lo; e0 < hi; e0 += kBaSchurTile) {
     const int cnt = static_cast<int>(hi - e0 < kBaSchurTile ? hi - e0 : kBaSchurTile);
     __syncthreads();
-    for (int idx = tid; idx < cnt * 36; idx += 192) {
-      const int64_t e = e0 + idx / 36;
-      const int f = idx % 36;
-      sy[idx] = Y[36 * static_cast<int64_t>(ent[2 * e]) + f];
-      sw[idx] = W[36 * static_cast<int64_t>(ent[2 * e + 1]) + f];
+    for (int idx = tid; idx < cnt * D3; idx += NT) {
+      const int64_t e = e0 + idx / D3;
+      const int f = idx % D3;
+      sy[idx] = Y[D3 * static_cast<int64_t>(ent[2 * e]) + f];
+      sw[idx] = W[D3 * static_cast<int64_t>(ent[2 * e + 1]) + f];
     }
     __syncthreads();
-    if (tid < 144) {
+    if (tid < DD) {
       for (int e = 0; e < cnt; ++e) {
-        const double *y = sy + 36 * e + 3 * rr;
-        const double *w = sw + 36 * e + 3 * cc;
+        const double *y = sy + D3 * e + 3 * rr;
+        const double *w = sw + D3 * e + 3 * cc;
         s += y[0] * w[0] + y[1] * w[1] + y[2] * w[2];
       }
     }
   }
-  if (tid < 144) {
+  if (tid < DD) {
     double u = 0.0;
     if (a == b) {
-      u = U[144 * cam_of_slot[a] + tid];
+      u = U[DD * cam_of_slot[a] + tid];
       if (rr == cc) u += lam * u;
     }
-    // element (12a + rr, 12b + cc) = element (12b + cc, 12a + rr) of the lower triangle
-    S[static_cast<int64_t>(12 * a + rr) * ld + 12 * b + cc] = u - s;
+    // element (D a + rr, D b + cc) = element (D b + cc, D a + rr) of the lower triangle
+    S[static_cast<int64_t>(D * a + rr) * ld + D * b + cc] = u - s;
   }
   if (a != b) return;
   // right-hand side of block row a: the camera's row staged the same way (Y_i, g_p of its point)
-  const int k = tid - 144;
-  double t = tid >= 144 && tid < 156 ? -gc[12 * cam_of_slot[a] + k] : 0.0;
+  const int k = tid - DD;
+  double t = tid >= DD && tid < DD + D ? -gc[D * cam_of_slot[a] + k] : 0.0;
   for (int o0 = cam_off[a]; o0 < cam_off[a + 1]; o0 += kBaSchurTile) {
     const int cnt = min(kBaSchurTile, cam_off[a + 1] - o0);
     __syncthreads();
-    for (int idx = tid; idx < cnt * 36; idx += 192)
-      sy[idx] = Y[36 * static_cast<int64_t>(cam_obs[o0 + idx / 36]) + idx % 36];
-    for (int idx = tid; idx < cnt * 3; idx += 192)
+    for (int idx = tid; idx < cnt * D3; idx += NT)
+      sy[idx] = Y[D3 * static_cast<int64_t>(cam_obs[o0 + idx / D3]) + idx % D3];
+    for (int idx = tid; idx < cnt * 3; idx += NT)
       sw[idx] = gp[3 * static_cast<int64_t>(op[cam_obs[o0 + idx / 3]]) + idx % 3];
     __syncthreads();
-    if (tid >= 144 && tid < 156) {
+    if (tid >= DD && tid < DD + D) {
       for (int o = 0; o < cnt; ++o) {
-        const double *y = sy + 36 * o + 3 * k;
+        const double *y = sy + D3 * o + 3 * k;
         const double *g = sw + 3 * o;
         t += y[0] * g[0] + y[1] * g[1] + y[2] * g[2];
       }
     }
   }
-  if (tid >= 144 && tid < 156) S[static_cast<int64_t>(12 * a + k) * ld + N] = t;
+  if (tid >= DD && tid < DD + D) S[static_cast<int64_t>(D * a + k) * ld + N] = t;
 }
 
 // Cholesky of S (N = 12 nf) and both triangular solves in one workgroup.  Left-looking by 12-wide
@@ -315,52 +444,59 @@ __global__ __launch_bounds__(192) void k_ba_schur(
 // side is row N of the matrix, so the factorisation leaves y = L^-1 rhs there.  dc (nC, 12) gets
 // the camera steps (rows of cameras outside the system stay zero); on a non-positive pivot it
 // gets zeros and the flag.
+// Template: DC is the camera block width of dc, BW the block-column width (every 12 of the text
+// above).  N is a multiple of BW; rows [nreal, N) are an identity pad (k_ba_schur) whose solution
+// is zero and is not written anywhere.  A pad row has zeros left of its diagonal, so it changes
+// no sum of a real row.
+template <int DC, int BW>
 __global__ __launch_bounds__(kBaCholThreads) void k_ba_chol(
-    double *__restrict__ S, int N, const int32_t *__restrict__ cam_of_slot,
+    double *__restrict__ S, int N, int nreal, const int32_t *__restrict__ cam_of_slot,
     double *__restrict__ dc, int32_t *__restrict__ flag) {
-  __shared__ double Ts[kBaCholTile * 12];
-  __shared__ double D[144];
+  constexpr int BB = BW * BW, NB = BW == 12 ? kBaCholBatch : BW;
+  static_assert(kBaCholTile % BW == 0 && kBaCholTile % NB == 0 && BW % NB == 0, "tile shapes");
+  __shared__ double Ts[kBaCholTile * BW];
+  __shared__ double D[BB];
   __shared__ double ys[12 * kBaMaxFree];
   __shared__ int bad;
-  const int tid = threadIdx.x, ld = N + 1, R = N + 1, nb = N / 12;
+  const int tid = threadIdx.x, ld = N + 1, R = N + 1, nb = N / BW;
   if (tid == 0) bad = 0;
   __syncthreads();
   for (int k = 0; k < nb; ++k) {
-    const int c0 = 12 * k;
+    const int c0 = BW * k;
     for (int m0 = 0; m0 < c0; m0 += kBaCholTile) {
       const int mc = min(kBaCholTile, c0 - m0);
       __syncthreads();
-      for (int idx = tid; idx < mc * 12; idx += kBaCholThreads)
-        Ts[idx] = S[static_cast<int64_t>(m0 + idx / 12) * ld + c0 + idx % 12];
+      for (int idx = tid; idx < mc * BW; idx += kBaCholThreads)
+        Ts[idx] = S[static_cast<int64_t>(m0 + idx / BW) * ld + c0 + idx % BW];
       __syncthreads();
       for (int base = c0; base < R; base += kBaCholThreads * kBaCholRows) {
         // rows base + q * blockDim + tid, q < nq (uniform); a lane past the last row works on
         // row R - 1 and stores nothing
         const int nq = min(kBaCholRows, (R - base + kBaCholThreads - 1) / kBaCholThreads);
-        double acc[kBaCholRows][12];
+        double acc[kBaCholRows][BW];
         int row[kBaCholRows];
 #pragma unroll
         for (int q = 0; q < kBaCholRows; ++q) {
           row[q] = min(base + q * kBaCholThreads + tid, R - 1);
           if (q < nq) {
 #pragma unroll
-            for (int c = 0; c < 12; ++c) acc[q][c] = S[static_cast<int64_t>(c0 + c) * ld + row[q]];
+            for (int c = 0; c < BW; ++c) acc[q][c] = S[static_cast<int64_t>(c0 + c) * ld + row[q]];
           }
         }
-        // kBaCholBatch columns at a time: their L entries are all requested before the first is
-        // used (one memory latency per batch, not per column); mc is a multiple of 12
-        for (int m = 0; m < mc; m += kBaCholBatch) {
-          double l[kBaCholBatch][kBaCholRows];
+        // NB columns at a time: their L entries are all requested before the first is
+        // used (one memory latency per batch, not per column); mc is a multiple of BW
+        for (int m = 0; m < mc; m += NB) {
+          double l[NB][kBaCholRows];
 #pragma unroll
-          for (int j = 0; j < kBaCholBatch; ++j)
+          for (int j = 0; j < NB; ++j)
 #pragma unroll
             for (int q = 0; q < kBaCholRows; ++q)
               l[j][q] = q < nq ? S[static_cast<int64_t>(m0 + m + j) * ld + row[q]] : 0.0;
 #pragma unroll
-          for (int j = 0; j < kBaCholBatch; ++j)
+          for (int j = 0; j < NB; ++j)
 #pragma unroll
-            for (int c = 0; c < 12; ++c) {
-              const double t = Ts[12 * (m + j) + c];
+            for (int c = 0; c < BW; ++c) {
+              const double t = Ts[BW * (m + j) + c];
 #pragma unroll
               for (int q = 0; q < kBaCholRows; ++q)
                 if (q < nq) acc[q][c] -= l[j][q] * t;
@@ -370,60 +506,60 @@ __global__ __launch_bounds__(kBaCholThreads) void k_ba_chol(
         for (int q = 0; q < kBaCholRows; ++q)
           if (q < nq && base + q * kBaCholThreads + tid < R) {
 #pragma unroll
-            for (int c = 0; c < 12; ++c) S[static_cast<int64_t>(c0 + c) * ld + row[q]] = acc[q][c];
+            for (int c = 0; c < BW; ++c) S[static_cast<int64_t>(c0 + c) * ld + row[q]] = acc[q][c];
           }
       }
     }
     __syncthreads();
-    if (tid < 144) D[tid] = S[static_cast<int64_t>(c0 + tid % 12) * ld + c0 + tid / 12];
+    if (tid < BB) D[tid] = S[static_cast<int64_t>(c0 + tid % BW) * ld + c0 + tid / BW];
     __syncthreads();
     if (tid < 64) {
-      // the 12 x 12 factor in the first wave, lane i holding row i in registers (right-looking;
+      // the BW x BW factor in the first wave, lane i holding row i in registers (right-looking;
       // L[c][j] travels from lane c by v_readlane).  A bad pivot poisons the rest with NaN and
       // is reported, not branched on
-      double a[12];
+      double a[BW];
 #pragma unroll
-      for (int c = 0; c < 12; ++c) a[c] = tid < 12 ? D[12 * tid + c] : 1.0;
+      for (int c = 0; c < BW; ++c) a[c] = tid < BW ? D[BW * tid + c] : 1.0;
       bool ok = true;
 #pragma unroll
-      for (int j = 0; j < 12; ++j) {
+      for (int j = 0; j < BW; ++j) {
         const double d = ba_bcast(a[j], j);
         ok = ok && d > 0.0;
         const double root = sqrt(d), inv = 1.0 / root;
         a[j] = tid == j ? root : a[j] * inv;
 #pragma unroll
-        for (int c = j + 1; c < 12; ++c) a[c] -= a[j] * ba_bcast(a[j], c);
+        for (int c = j + 1; c < BW; ++c) a[c] -= a[j] * ba_bcast(a[j], c);
       }
-      if (tid < 12) {
+      if (tid < BW) {
 #pragma unroll
-        for (int c = 0; c < 12; ++c)
-          if (c <= tid) D[12 * tid + c] = a[c];
+        for (int c = 0; c < BW; ++c)
+          if (c <= tid) D[BW * tid + c] = a[c];
       }
       if (tid == 0 && !ok) bad = 1;
     }
     __syncthreads();
     if (bad) break;
-    for (int i = c0 + 12 + tid; i < R; i += kBaCholThreads) {
+    for (int i = c0 + BW + tid; i < R; i += kBaCholThreads) {
       // keep the 78 reads of D inside the loop: hoisted, they would sit in 156 VGPRs
       asm volatile("" ::: "memory");
-      double x[12];
+      double x[BW];
 #pragma unroll
-      for (int c = 0; c < 12; ++c) {
+      for (int c = 0; c < BW; ++c) {
         double s = S[static_cast<int64_t>(c0 + c) * ld + i];
 #pragma unroll
-        for (int t = 0; t < c; ++t) s -= x[t] * D[12 * c + t];
-        x[c] = s / D[13 * c];
+        for (int t = 0; t < c; ++t) s -= x[t] * D[BW * c + t];
+        x[c] = s / D[(BW + 1) * c];
       }
 #pragma unroll
-      for (int c = 0; c < 12; ++c) S[static_cast<int64_t>(c0 + c) * ld + i] = x[c];
+      for (int c = 0; c < BW; ++c) S[static_cast<int64_t>(c0 + c) * ld + i] = x[c];
     }
-    if (tid < 144 && tid % 12 <= tid / 12)
-      S[static_cast<int64_t>(c0 + tid % 12) * ld + c0 + tid / 12] = D[tid];
+    if (tid < BB && tid % BW <= tid / BW)
+      S[static_cast<int64_t>(c0 + tid % BW) * ld + c0 + tid / BW] = D[tid];
   }
   __syncthreads();
   if (bad) {
-    for (int idx = tid; idx < N; idx += kBaCholThreads)
-      dc[12 * cam_of_slot[idx / 12] + idx % 12] = 0.0;
+    for (int idx = tid; idx < nreal; idx += kBaCholThreads)
+      dc[DC * cam_of_slot[idx / DC] + idx % DC] = 0.0;
     if (tid == 0) flag[0] = 1;
     return;
   }
@@ -431,15 +567,15 @@ __global__ __launch_bounds__(kBaCholThreads) void k_ba_chol(
   for (int idx = tid; idx < N; idx += kBaCholThreads)
     ys[idx] = S[static_cast<int64_t>(idx) * ld + N];
   for (int k = nb - 1; k >= 0; --k) {
-    const int c0 = 12 * k;
-    if (tid < 144 && tid % 12 <= tid / 12)
-      D[tid] = S[static_cast<int64_t>(c0 + tid % 12) * ld + c0 + tid / 12];
+    const int c0 = BW * k;
+    if (tid < BB && tid % BW <= tid / BW)
+      D[tid] = S[static_cast<int64_t>(c0 + tid % BW) * ld + c0 + tid / BW];
     __syncthreads();
     if (tid == 0) {
-      for (int c = 11; c >= 0; --c) {
+      for (int c = BW - 1; c >= 0; --c) {
         double s = ys[c0 + c];
-        for (int t = c + 1; t < 12; ++t) s -= D[12 * t + c] * ys[c0 + t];
-        ys[c0 + c] = s / D[13 * c];
+        for (int t = c + 1; t < BW; ++t) s -= D[BW * t + c] * ys[c0 + t];
+        ys[c0 + c] = s / D[(BW + 1) * c];
       }
     }
     __syncthreads();
@@ -447,18 +583,20 @@ __global__ __launch_bounds__(kBaCholThreads) void k_ba_chol(
       const double *l = S + static_cast<int64_t>(i) * ld + c0;
       double s = ys[i];
 #pragma unroll
-      for (int c = 0; c < 12; ++c) s -= l[c] * ys[c0 + c];
+      for (int c = 0; c < BW; ++c) s -= l[c] * ys[c0 + c];
       ys[i] = s;
     }
   }
   __syncthreads();
-  for (int idx = tid; idx < N; idx += kBaCholThreads)
-    dc[12 * cam_of_slot[idx / 12] + idx % 12] = ys[idx];
+  for (int idx = tid; idx < nreal; idx += kBaCholThreads)
+    dc[DC * cam_of_slot[idx / DC] + idx % DC] = ys[idx];
 }
 
 // Lanes [0, nP): dx_p = -V*^-1 (g_p + sum_i W_i^T dc_cam(i)), the trial point, and the point's
 // share lam dx^T diag(V) dx - dx^T g_p of the predicted reduction.  Lanes [0, 12 nC) also form
 // the trial cameras.  A point without observations and a camera outside the system are copied.
+// D = 6: lanes [0, nC) retract, one camera each: [R | t] <- Exp(omega) [R | t] + [0 | tau].
+template <int D>
 __global__ __launch_bounds__(256) void k_ba_step(
     const int32_t *__restrict__ pt_off, const int32_t *__restrict__ pt_obs,
     const int32_t *__restrict__ ov, int nP, int nC, const int32_t *__restrict__ slot_of_cam,
@@ -467,7 +605,29 @@ __global__ __launch_bounds__(256) void k_ba_step(
     const double *__restrict__ cams, const double *__restrict__ pts,
     double *__restrict__ cams_n, double *__restrict__ pts_n, double *__restrict__ ppred) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < 12 * nC) cams_n[t] = slot_of_cam[t / 12] >= 0 ? cams[t] + dc[t] : cams[t];
+  if constexpr (D == 12) {
+    if (t < 12 * nC) cams_n[t] = slot_of_cam[t / 12] >= 0 ? cams[t] + dc[t] : cams[t];
+  } else {
+    if (t < nC) {
+      const double *c = cams + 12 * t;
+      double *cn = cams_n + 12 * t;
+      if (slot_of_cam[t] >= 0) {
+        const double *d = dc + 6 * t;
+        double E[9];
+        ba_exp_so3(d, E);
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const double v = E[3 * i] * c[j] + E[3 * i + 1] * c[4 + j] + E[3 * i + 2] * c[8 + j];
+            cn[4 * i + j] = j == 3 ? v + d[3 + i] : v;
+          }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 12; ++q) cn[q] = c[q];
+      }
+    }
+  }
   if (t >= nP) return;
   const int64_t p = t;
   const int lo = pt_off[p], hi = pt_off[p + 1];
@@ -480,10 +640,10 @@ __global__ __launch_bounds__(256) void k_ba_step(
   double g[3] = {gp[3 * p], gp[3 * p + 1], gp[3 * p + 2]};
   for (int o = lo; o < hi; ++o) {
     const int64_t i = pt_obs[o];
-    const double *w = W + 36 * i;
-    const double *d = dc + 12 * ov[i];
+    const double *w = W + 3 * D * i;
+    const double *d = dc + D * ov[i];
 #pragma unroll
-    for (int k = 0; k < 12; ++k)
+    for (int k = 0; k < D; ++k)
 #pragma unroll
       for (int q = 0; q < 3; ++q) g[q] += w[3 * k + q] * d[k];
   }
@@ -533,6 +693,7 @@ __device__ __forceinline__ double ba_block_sum(double v, double *sh) {
 // rec (pinned host memory): [0] cost = 0.5 sum e, [1] predicted reduction
 // 0.5 (lam (dc^T diag(U) dc + dx^T diag(V) dx) - dc^T g_c - dx^T g_p), [2] the failure flag
 // (cleared here for the next trial), [3] the trial's serial number.  nP = nC = 0: cost only.
+template <int D>
 __global__ __launch_bounds__(kBaFinalThreads) void k_ba_final(
     const double *__restrict__ e, int n, const double *__restrict__ ppred, int nP,
     const double *__restrict__ dc, const double *__restrict__ U, const double *__restrict__ gc,
@@ -546,9 +707,9 @@ __global__ __launch_bounds__(kBaFinalThreads) void k_ba_final(
   for (int p = tid; p < nP; p += kBaFinalThreads) s += ppred[p];
   const double pp = ba_block_sum(s, sh);
   s = 0.0;
-  for (int t = tid; t < 12 * nC; t += kBaFinalThreads) {
+  for (int t = tid; t < D * nC; t += kBaFinalThreads) {
     const double d = dc[t];
-    s += lam * d * U[144 * (t / 12) + 13 * (t % 12)] * d - d * gc[t];
+    s += lam * d * U[D * D * (t / D) + (D + 1) * (t % D)] * d - d * gc[t];
   }
   const double pc = ba_block_sum(s, sh);
   if (tid == 0) {
@@ -622,10 +783,35 @@ extern "C" int rs_ba_timing(rs_ctx *c, int32_t enable, double *ms, int64_t *tria
   return RS_OK;
 }
 
-extern "C" int rs_bundle_adjust(rs_ctx *c, double *cams, int64_t nC, double *pts, int64_t nP,
-                                const int32_t *obs_view, const int32_t *obs_point,
-                                const double *uv, int64_t n, int32_t max_iter, double ftol,
-                                rs_ba_info *info) {
+namespace {
+
+// Block-column width of the rigid (D = 6) reduced system: 12 pads 6 nf up to a multiple of 12
+// with an identity diagonal, 6 factorises 6-wide block columns (DESIGN.md section 10 has the
+// measurement behind the default).
+#ifndef RS_BA_RIGID_BW
+#define RS_BA_RIGID_BW 12
+#endif
+
+// R of a free rigid camera must be a rotation: max |R^T R - I| <= 1e-6 and det R > 0.
+bool ba_is_rotation(const double *c) {
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double g = c[i] * c[j] + c[4 + i] * c[4 + j] + c[8 + i] * c[8 + j] - (i == j ? 1.0 : 0.0);
+      if (!(std::fabs(g) <= 1e-6)) return false;  // NaN too
+    }
+  const double det = c[0] * (c[5] * c[10] - c[6] * c[9]) - c[1] * (c[4] * c[10] - c[6] * c[8]) +
+                     c[2] * (c[4] * c[9] - c[5] * c[8]);
+  return det > 0.0;
+}
+
+// The LM loop of both entry points; D = 12: cameras as 12 free entries, D = 6: rigid.
+template <int D>
+int ba_run(rs_ctx *c, double *cams, int64_t nC, double *pts, int64_t nP, const int32_t *obs_view,
+           const int32_t *obs_point, const double *uv, int64_t n, int32_t max_iter, double ftol,
+           rs_ba_info *info) {
+  constexpr int BW = D == 12 ? 12 : RS_BA_RIGID_BW, DD = D * D, D3 = 3 * D, NG = D / 2;
+  constexpr int NT = rsd::ba_block_threads(D);
+  static_assert(BW == 12 || BW == 6, "block-column width");
   if (!c || !cams || !pts || !obs_view || !obs_point || !uv || !info)
     return fail(RS_EINVAL, "null pointer");
   if (n <= 0) return fail(RS_EINVAL, "bundle adjustment needs at least one observation");
@@ -653,7 +839,15 @@ extern "C" int rs_bundle_adjust(rs_ctx *c, double *cams, int64_t nC, double *pts
       cam_of_slot.push_back(static_cast<int32_t>(k));
     }
   const int nf = static_cast<int>(cam_of_slot.size());
-  const int N = 12 * nf, ld = N + 1;
+  if constexpr (D == 6) {
+    for (int32_t k : cam_of_slot)
+      if (!ba_is_rotation(cams + 12 * k)) {
+        rs::set_error("camera %d is not a rigid pose: max |R^T R - I| > 1e-6 or det R <= 0", k);
+        return RS_EINVAL;
+      }
+  }
+  // N: the reduced system with its pad to whole block columns
+  const int nreal = D * nf, N = (nreal + BW - 1) / BW * BW, ld = N + 1;
   std::vector<int32_t> cam_off(nf + 1, 0), cam_obs;
   for (int s = 0; s < nf; ++s) cam_off[s + 1] = cam_off[s] + cnt_cam[cam_of_slot[s]];
   cam_obs.resize(cam_off[nf] > 0 ? cam_off[nf] : 1);
@@ -704,17 +898,17 @@ extern "C" int rs_bundle_adjust(rs_ctx *c, double *cams, int64_t nC, double *pts
 
   // ---- device buffers, one carve of the context scratch
   HIP_TRY(hipSetDevice(c->device));
-  const size_t D = sizeof(double), I = sizeof(int32_t);
+  const size_t F8 = sizeof(double), I = sizeof(int32_t);
   const int64_t pp = nP > 0 ? nP : 1;
   const size_t sizes[] = {
-      D * 12 * nC, D * 12 * nC, D * 3 * pp, D * 3 * pp,            // 0-3 cams, cams_n, pts, pts_n
-      I * n, I * n, D * 2 * n,                                     // 4-6 ov, op, uv
+      F8 * 12 * nC, F8 * 12 * nC, F8 * 3 * pp, F8 * 3 * pp,            // 0-3 cams, cams_n, pts, pts_n
+      I * n, I * n, F8 * 2 * n,                                     // 4-6 ov, op, uv
       I * (nP + 1), I * n, I * (nf + 1), I * cam_obs.size(),       // 7-10 CSR
       I * nC, I * (nf + 1), sizeof(int64_t) * (npair + 1), I * ent.size(),  // 11-14
-      D * 2 * n, D * 6 * n, D * 6 * n, D * 36 * n, D * 36 * n,     // 15-19 r, jcs, Jp, W, Y
-      D * 144 * nC, D * 12 * nC, D * 12 * nC,                      // 20-22 U, gc, dc
-      D * 6 * pp, D * 6 * pp, D * 3 * pp, D * pp,                  // 23-26 V, Vinv, gp, ppred
-      D * n, D * static_cast<size_t>(ld) * ld, 256};               // 27-29 e, S, flag
+      F8 * 2 * n, F8 * NG * n, F8 * 6 * n, F8 * D3 * n, F8 * D3 * n,   // 15-19 r, jcs, Jp, W, Y
+      F8 * DD * nC, F8 * D * nC, F8 * D * nC,                         // 20-22 U, gc, dc
+      F8 * 6 * pp, F8 * 6 * pp, F8 * 3 * pp, F8 * pp,                  // 23-26 V, Vinv, gp, ppred
+      F8 * n, F8 * static_cast<size_t>(ld) * ld, 256};               // 27-29 e, S, flag
   constexpr int kBufs = sizeof(sizes) / sizeof(sizes[0]);
   size_t tot = 0;
   for (size_t s : sizes) tot += al(s);
@@ -753,11 +947,11 @@ extern "C" int rs_bundle_adjust(rs_ctx *c, double *cams, int64_t nC, double *pts
   auto up = [s](void *dst, const void *src, size_t bytes) {
     return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
   };
-  HIP_TRY(up(d_cams, cams, D * 12 * nC));
-  HIP_TRY(up(d_pts, pts, D * 3 * nP));
+  HIP_TRY(up(d_cams, cams, F8 * 12 * nC));
+  HIP_TRY(up(d_pts, pts, F8 * 3 * nP));
   HIP_TRY(up(d_ov, obs_view, I * n));
   HIP_TRY(up(d_op, obs_point, I * n));
-  HIP_TRY(up(d_uv, uv, D * 2 * n));
+  HIP_TRY(up(d_uv, uv, F8 * 2 * n));
   HIP_TRY(up(d_pt_off, pt_off.data(), I * (nP + 1)));
   HIP_TRY(up(d_pt_obs, pt_obs.data(), I * n));
   HIP_TRY(up(d_cam_off, cam_off.data(), I * (nf + 1)));
@@ -767,9 +961,9 @@ extern "C" int rs_bundle_adjust(rs_ctx *c, double *cams, int64_t nC, double *pts
   HIP_TRY(up(d_pair_off, pair_off.data(), sizeof(int64_t) * (npair + 1)));
   HIP_TRY(up(d_ent, ent.data(), I * ent.size()));
   // cameras outside the system keep zero U, g_c and step for the whole call
-  HIP_TRY(hipMemsetAsync(d_U, 0, D * 144 * nC, s));
-  HIP_TRY(hipMemsetAsync(d_gc, 0, D * 12 * nC, s));
-  HIP_TRY(hipMemsetAsync(d_dc, 0, D * 12 * nC, s));
+  HIP_TRY(hipMemsetAsync(d_U, 0, F8 * DD * nC, s));
+  HIP_TRY(hipMemsetAsync(d_gc, 0, F8 * D * nC, s));
+  HIP_TRY(hipMemsetAsync(d_dc, 0, F8 * D * nC, s));
   HIP_TRY(hipMemsetAsync(d_flag, 0, 256, s));
 
   Marks mk{c};
@@ -784,7 +978,7 @@ extern "C" int rs_bundle_adjust(rs_ctx *c, double *cams, int64_t nC, double *pts
     hipLaunchKernelGGL(rsd::k_ba_cost, dim3(blocks(n, 256)), dim3(256), 0, s, cm, pt, d_ov, d_op,
                        d_uv, ni, d_e);
     serial += 1.0;
-    hipLaunchKernelGGL(rsd::k_ba_final, dim3(1), dim3(rsd::kBaFinalThreads), 0, s, d_e, ni,
+    hipLaunchKernelGGL(rsd::k_ba_final<D>, dim3(1), dim3(rsd::kBaFinalThreads), 0, s, d_e, ni,
                        d_ppred, trial ? nPi : 0, d_dc, d_U, d_gc, trial ? nCi : 0, lam, d_flag,
                        serial, const_cast<double *>(rec));
     HIP_TRY(hipGetLastError());
@@ -806,11 +1000,12 @@ extern "C" int rs_bundle_adjust(rs_ctx *c, double *cams, int64_t nC, double *pts
   bool done = false;
   for (it = 1; it <= max_iter && !done; ++it) {
     HIP_TRY(mk.begin());
-    hipLaunchKernelGGL(rsd::k_ba_linearize, dim3(blocks(n, 256)), dim3(256), 0, s, d_cams, d_pts,
-                       d_ov, d_op, d_uv, ni, d_r, d_jcs, d_Jp, d_W);
+    hipLaunchKernelGGL(D == 12 ? rsd::k_ba_linearize : rsd::k_ba_linearize_rigid,
+                       dim3(blocks(n, 256)), dim3(256), 0, s, d_cams, d_pts, d_ov, d_op, d_uv, ni,
+                       d_r, d_jcs, d_Jp, d_W);
     HIP_TRY(mk.mark(T_LIN));
     if (nf > 0) {
-      hipLaunchKernelGGL(rsd::k_ba_camera, dim3(nf), dim3(192), 0, s, d_cos, d_cam_off, d_cam_obs,
+      hipLaunchKernelGGL(rsd::k_ba_camera<D>, dim3(nf), dim3(NT), 0, s, d_cos, d_cam_off, d_cam_obs,
                          d_jcs, d_r, d_U, d_gc);
       HIP_TRY(mk.mark(T_CAM));
     }
@@ -818,20 +1013,20 @@ extern "C" int rs_bundle_adjust(rs_ctx *c, double *cams, int64_t nC, double *pts
                        d_pt_obs, nPi, d_Jp, d_r, d_V, d_gp);
     HIP_TRY(mk.mark(T_PSUM));
     for (;;) {
-      hipLaunchKernelGGL(rsd::k_ba_point, dim3(blocks(n, 256)), dim3(256), 0, s, d_op, d_pt_off,
+      hipLaunchKernelGGL(rsd::k_ba_point<D>, dim3(blocks(n, 256)), dim3(256), 0, s, d_op, d_pt_off,
                          d_pt_obs, ni, d_V, lam, d_W, d_Y, d_Vinv, d_flag);
       HIP_TRY(mk.mark(T_POINT));
       if (nf > 0) {
-        hipLaunchKernelGGL(rsd::k_ba_schur, dim3(static_cast<unsigned>(npair)), dim3(192), 0, s,
+        hipLaunchKernelGGL(rsd::k_ba_schur<D>, dim3(static_cast<unsigned>(npair)), dim3(NT), 0, s,
                            nf, d_pair_off, d_ent, d_Y, d_W, d_U, d_gc, d_gp, d_op, d_cos,
                            d_cam_off, d_cam_obs, lam, d_S, ld);
         HIP_TRY(mk.mark(T_SCHUR));
-        hipLaunchKernelGGL(rsd::k_ba_chol, dim3(1), dim3(rsd::kBaCholThreads), 0, s, d_S, N,
-                           d_cos, d_dc, d_flag);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(rsd::k_ba_chol<D, BW>), dim3(1),
+                           dim3(rsd::kBaCholThreads), 0, s, d_S, N, nreal, d_cos, d_dc, d_flag);
         HIP_TRY(mk.mark(T_CHOL));
       }
-      const int64_t lanes = nP > 12 * nC ? nP : 12 * nC;
-      hipLaunchKernelGGL(rsd::k_ba_step, dim3(blocks(lanes, 256)), dim3(256), 0, s, d_pt_off,
+      const int64_t clanes = D == 12 ? 12 * nC : nC, lanes = nP > clanes ? nP : clanes;
+      hipLaunchKernelGGL(rsd::k_ba_step<D>, dim3(blocks(lanes, 256)), dim3(256), 0, s, d_pt_off,
                          d_pt_obs, d_ov, nPi, nCi, d_slot, d_W, d_V, d_Vinv, d_gp, d_dc, lam,
                          d_cams, d_pts, d_cams_n, d_pts_n, d_ppred);
       HIP_TRY(mk.mark(T_STEP));
@@ -868,8 +1063,8 @@ extern "C" int rs_bundle_adjust(rs_ctx *c, double *cams, int64_t nC, double *pts
   }
   it = done ? it - 1 : max_iter;
 
-  HIP_TRY(hipMemcpyAsync(cams, d_cams, D * 12 * nC, hipMemcpyDeviceToHost, s));
-  if (nP > 0) HIP_TRY(hipMemcpyAsync(pts, d_pts, D * 3 * nP, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(cams, d_cams, F8 * 12 * nC, hipMemcpyDeviceToHost, s));
+  if (nP > 0) HIP_TRY(hipMemcpyAsync(pts, d_pts, F8 * 3 * nP, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   info->cost_init = cost0;
   info->cost = cost;
@@ -879,4 +1074,20 @@ extern "C" int rs_bundle_adjust(rs_ctx *c, double *cams, int64_t nC, double *pts
   info->status = status;
   info->reserved = 0;
   return RS_OK;
+}
+
+}  // namespace
+
+extern "C" int rs_bundle_adjust(rs_ctx *c, double *cams, int64_t nC, double *pts, int64_t nP,
+                                const int32_t *obs_view, const int32_t *obs_point,
+                                const double *uv, int64_t n, int32_t max_iter, double ftol,
+                                rs_ba_info *info) {
+  return ba_run<12>(c, cams, nC, pts, nP, obs_view, obs_point, uv, n, max_iter, ftol, info);
+}
+
+extern "C" int rs_bundle_adjust_rigid(rs_ctx *c, double *cams, int64_t nC, double *pts,
+                                      int64_t nP, const int32_t *obs_view,
+                                      const int32_t *obs_point, const double *uv, int64_t n,
+                                      int32_t max_iter, double ftol, rs_ba_info *info) {
+  return ba_run<6>(c, cams, nC, pts, nP, obs_view, obs_point, uv, n, max_iter, ftol, info);
 }

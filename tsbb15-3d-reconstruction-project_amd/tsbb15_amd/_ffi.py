@@ -168,6 +168,9 @@ _SIGS = {
                                  C.c_int64, _dp, _dp]),
     "rs_bundle_adjust": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _i32p, _i32p, _dp,
                                    C.c_int64, C.c_int32, C.c_double, C.POINTER(BaInfo)]),
+    "rs_bundle_adjust_rigid": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _i32p, _i32p,
+                                         _dp, C.c_int64, C.c_int32, C.c_double,
+                                         C.POINTER(BaInfo)]),
     "rs_ba_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp, _i64p]),
     "rs_triangulate_nview": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _i32p, _i32p,
                                        _dp, C.c_int64, _i32p]),

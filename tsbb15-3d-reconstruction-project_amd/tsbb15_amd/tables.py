@@ -10,6 +10,11 @@ Array-level functions (HIP kernels of tables.hip):
   * ``ba_jacobian``         its Jacobian blocks (the nonzeros of tables.py:339-372)
   * ``bundle_adjust``       that objective minimised on the GPU (ba.hip): Levenberg-Marquardt,
                             points eliminated by a Schur complement, camera 0 fixed
+  * ``bundle_adjust_rigid`` the same objective over rigid poses: 6 local coordinates per camera,
+                            R+ = Exp(omega) R, t+ = Exp(omega) t + tau, so every R stays a
+                            rotation (ba.hip, rs_bundle_adjust_rigid)
+  * ``nearest_rotations``   host helper: the nearest rotation to every 3 x 3 block of (nC, 3, 4)
+                            cameras, for tables that came through the 12-parameter adjustment
   * ``triangulate_nview``   every point from all its observations (wash.hip)
   * ``wash_points``         robust re-triangulation of every point from its own track and the
                             outlier verdict on its observations: the WASH1 / WASH2 steps that
@@ -22,6 +27,8 @@ arithmetic above on the GPU and do the same bookkeeping in the same order):
   * ``add_new_view(T, K, img_index, y1_hom, y2_hom, y1, y2)``      Tables.addNewView
   * ``add_new_points_table(T, A_y1_hom, A_y2_hom, v1, v2)``       Tables.addNewPoints
   * ``BundleAdjustment2(T)``                                       Tables.BundleAdjustment2
+  * ``BundleAdjustmentRigid(T)``                                   the same write-back around
+                                                                   ``bundle_adjust_rigid``
   * ``wash(T, thresh)``                                            the wash step (no reference code)
 """
 from __future__ import annotations
@@ -140,6 +147,11 @@ def bundle_adjust(cams, pts, obs_view, obs_point, uv, max_iter=200, ftol=1e-15, 
     Returns (cams (nC, 3, 4), pts (nP, 3), info) with info = dict(cost_init, cost, iterations,
     status, rejected, lambda): costs are 0.5 |r|^2; status 1 = an accepted step gained
     <= ftol * cost, 2 = damping above 1e32, 0 = max_iter linearisations."""
+    return _bundle_adjust("rs_bundle_adjust", cams, pts, obs_view, obs_point, uv, max_iter, ftol,
+                          ctx)
+
+
+def _bundle_adjust(entry, cams, pts, obs_view, obs_point, uv, max_iter, ftol, ctx):
     cams, pts, ov, op = _ba_args(cams, pts, obs_view, obs_point)
     cams, pts = cams.copy(), pts.copy()
     uv = _ffi.f64c(uv).reshape(-1, 2)
@@ -151,13 +163,38 @@ def bundle_adjust(cams, pts, obs_view, obs_point, uv, max_iter=200, ftol=1e-15, 
         raise ValueError('bundle adjustment needs at least one camera')
     info = _ffi.BaInfo()
     i32 = _ffi.C.c_int32
-    _ffi.check(_ffi.lib().rs_bundle_adjust(
+    _ffi.check(getattr(_ffi.lib(), entry)(
         _ctx(ctx), _ffi.ptr(cams, _d), len(cams), _ffi.ptr(pts, _d), len(pts), _ffi.ptr(ov, i32),
         _ffi.ptr(op, i32), _ffi.ptr(uv, _d), len(ov), int(max_iter), float(ftol),
         _ffi.C.byref(info)))
     return cams, pts, {"cost_init": info.cost_init, "cost": info.cost,
                        "iterations": info.iterations, "status": info.status,
                        "rejected": info.rejected, "lambda": info.lam}
+
+
+def bundle_adjust_rigid(cams, pts, obs_view, obs_point, uv, max_iter=200, ftol=1e-15, ctx=None):
+    """``bundle_adjust`` over rigid poses (rs_bundle_adjust_rigid): the same objective, LM rules
+    and return value, but camera k = [R | t] moves by 6 local coordinates (omega, tau),
+    R+ = Exp(omega) R, t+ = Exp(omega) t + tau, so every R comes back a rotation (to rounding;
+    nothing is re-orthonormalised) and the reconstruction stays metric up to its global scale.
+
+    Every free camera (1.. with an observation) must hold a rotation: max |R^T R - I| <= 1e-6
+    and det R > 0, else ValueError names the camera -- ``nearest_rotations`` repairs cameras
+    that came through the 12-parameter ``bundle_adjust``.  Camera 0, and every camera or point
+    without an observation, comes back bit for bit unchanged.  The inputs are not modified."""
+    return _bundle_adjust("rs_bundle_adjust_rigid", cams, pts, obs_view, obs_point, uv, max_iter,
+                          ftol, ctx)
+
+
+def nearest_rotations(cams):
+    """(nC, 3, 4) cameras with every 3 x 3 block replaced by its nearest rotation in the
+    Frobenius norm (the polar factor U diag(1, 1, det(U V^T)) V^T of its SVD, det +1); t is left
+    alone.  Host numpy.  The input is not modified."""
+    out = np.array(cams, dtype=np.float64).reshape(-1, 3, 4)
+    for M in out:
+        U, _, Vt = np.linalg.svd(M[:, :3])
+        M[:, :3] = U @ np.diag([1.0, 1.0, np.linalg.det(U @ Vt)]) @ Vt
+    return out
 
 
 def _wash_args(cams, pts, obs_view, obs_point, uv):
@@ -278,14 +315,25 @@ def BundleAdjustment2(T, max_iter=200, ftol=1e-15, ctx=None):
     ``bundle_adjust`` instead of scipy's TRF, then the write-back of updateCameras3Dpoints2
     (tables.py:384-390): every view gets a new pose of its own pose class built from the 3 x 4
     result, every point its new coordinates.  Returns the info dict of ``bundle_adjust``."""
+    return _adjust_table(bundle_adjust, T, max_iter, ftol, ctx)
+
+
+def BundleAdjustmentRigid(T, max_iter=200, ftol=1e-15, ctx=None):
+    """``BundleAdjustment2`` with ``bundle_adjust_rigid`` in place of ``bundle_adjust``: the same
+    gathering and write-back, every view's R stays a rotation.  The poses of the table must be
+    rotations already (ValueError otherwise; see ``nearest_rotations``)."""
+    return _adjust_table(bundle_adjust_rigid, T, max_iter, ftol, ctx)
+
+
+def _adjust_table(adjust, T, max_iter, ftol, ctx):
     cams = np.array([_pose(v.camera_pose) for v in T.T_views]).reshape(-1, 3, 4)
     pts = np.array([p.point for p in T.T_points], dtype=np.float64).reshape(-1, 3)
     uv = np.array([np.asarray(o.image_coordinates, dtype=np.float64).ravel()[:2]
                    for o in T.T_obs]).reshape(-1, 2)
     ov = np.array([o.view_index for o in T.T_obs], dtype=np.int32)
     op = np.array([o.point_3D_index for o in T.T_obs], dtype=np.int32)
-    new_pose, new_points, info = bundle_adjust(cams, pts, ov, op, uv, max_iter=max_iter,
-                                               ftol=ftol, ctx=ctx)
+    new_pose, new_points, info = adjust(cams, pts, ov, op, uv, max_iter=max_iter, ftol=ftol,
+                                        ctx=ctx)
     for i, v in enumerate(T.T_views):
         v.camera_pose = type(v.camera_pose)(new_pose[i, :3, :3], new_pose[i, :, 3])
     for i, p in enumerate(T.T_points):
