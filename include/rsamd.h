@@ -252,6 +252,13 @@ int rs_f8_plan_models(rs_f8_plan *plan, double *F_out, int64_t H);
  * lane 1 before their parse, and a run that meets a buffer set still in use on the other lane
  * waits for that lane.  Stays 0 in any sequence of Philox and host-tuple runs. */
 int rs_f8_plan_lane_waits(rs_f8_plan *plan, int64_t *waits);
+/* The pruned count of the last run (fp32 counting, RSAMD_PRUNE=1): out = {L, K, survivors,
+ * npad}.  L is the best full count among the first RSAMD_PRUNE_SAMPLE hypothesis groups, K the
+ * number of points every other hypothesis was counted over before the hopeless ones (those that
+ * could no longer reach L - 1) were dropped, survivors the hypotheses counted to the end.  A
+ * run that was not pruned reports K = npad and no survivors.  Results are those of the
+ * unpruned count in every field; rs_f8_plan_counts recounts after a pruned run. */
+int rs_f8_plan_prune_stats(rs_f8_plan *plan, int64_t out[4]);
 /* Device time (ms, HIP events on the run's stream lane; a run that records them runs its
  * counting kernel alone, without the other lane's kernels beside it) of the counting kernel,
  * the solve kernel and the whole run: of the last run, or averaged over the last `last_n` runs (<= 64).  Runs

@@ -50,6 +50,8 @@ struct SolveArgs {
   int *gdone;    // per-group finish counters zeroed (fused c*)
   float4 *G4;    // per-hypothesis decision constants (k_f8_count32q), may be null
   double gT, gDe, gDn;  // their inputs: (t/s)^2 and the fp32 error bounds of e and m
+  int *pw;       // pruned count: the run's kPruneWords words zeroed, may be null
+  int *gdone_b;  // ... and the rest stage's per-group finish counters
 };
 
 // One run's selection tail (candidates, reference statistics, replay, S_RANSAC).
@@ -106,6 +108,33 @@ hipError_t launch_f8_count32q(const float4 *ptsq, const Pt *pts, int n, int H,
                               const Count32qShape &sh, const GuardW &g, int *counts,
                               hipStream_t s, int *gdone, int *status, const float4 *G4,
                               const int *Hdev = nullptr);
+// Pruned count (derivation above k_f8_count32q): after a full count of the first g_first
+// hypothesis groups has left L in status[0], the prefix stage counts the other groups over the
+// points [0, K) only, K from L on the device, and lists the hypotheses that can still reach
+// L - 1 (surv); the rest stage counts those over [K, npad) through the list.  Per-run words:
+constexpr int kPruneWords = 4;  // [0] cA (max prefix count), [1] survivors, [2] K, [3] L
+struct PruneArgs {
+  int *pw;       // the run's words
+  int *surv;     // survivor hypothesis ids (ld ints)
+  int *gdone_b;  // the rest stage's per-group finish counters
+  int g_first;   // hypothesis groups counted in full by the sample stage
+  int margin;    // m: K = roundup8(n - L + m)
+  int min_skip;  // fewer points than this to skip: K = npad, nothing is pruned
+};
+// sh: the shape of the groups past g_first over the whole window (the prefix stage cuts its
+// slices from K on the device); H is the run's hypothesis count
+hipError_t launch_f8_count32q_prefix(const float4 *ptsq, const Pt *pts, int n, int H,
+                                     const float *F32soa, const double *Fsoa, int64_t ld,
+                                     const Count32qShape &sh, const GuardW &g, int *counts,
+                                     hipStream_t s, int *gdone, int *status, const float4 *G4,
+                                     const PruneArgs &pa);
+// waves: the resident waves the grid is sized for (the survivor count is on the device), at
+// most the grid of `bound`, the shape of all H hypotheses the prefix stage counted
+hipError_t launch_f8_count32q_rest(const float4 *ptsq, const Pt *pts, int n, int H,
+                                   const float *F32soa, const double *Fsoa, int64_t ld, int waves,
+                                   const Count32qShape &bound, const GuardW &g, int *counts,
+                                   hipStream_t s, int *status, const float4 *G4,
+                                   const PruneArgs &pa);
 hipError_t launch_f8_count(const Pt *pts, int n, int H, const double *Fsoa, int64_t ld,
                            int chunk, double thr2, int *counts, hipStream_t s,
                            const int *Hdev = nullptr, const int *Hmap = nullptr);

@@ -66,6 +66,13 @@ __device__ __forceinline__ void solve_one(const SolveArgs &a, int h) {
     for (int k = 0; k < 4; ++k) status[k] = 0;
   }
   if (gdone && (h & 63) == 0) gdone[h >> 6] = 0;  // fused c*: per-group finish counters
+  if (a.pw) {  // the pruned count's words and the rest stage's finish counters
+    if (h == 0) {
+#pragma unroll
+      for (int k = 0; k < kPruneWords; ++k) a.pw[k] = 0;
+    }
+    if ((h & 63) == 0) a.gdone_b[h >> 6] = 0;
+  }
   int idx[8];
   if (mode == RSD_SAMPLER_PHILOX) {
     floyd_sample<8>(seed, hyp_offset + static_cast<uint64_t>(h), n, idx);
@@ -225,6 +232,54 @@ __global__ __launch_bounds__(256) void k_f8_count(const Pt *__restrict__ pts, in
 // running alone), and static slices over 75 % of the plane with the rest claimed in 32-128-point
 // chunks from per-XCD heads (431-570 us: tens of thousands of returning device-scope atomics on
 // eight words serialise).
+//
+// Pruned count (the plan's fp32 path, RSAMD_PRUNE; MODE below).  How the kernel runs has nothing
+// left to give, so it does less: the selection tail reads only c* = status[0] and the
+// hypotheses with count >= max(c* - 1, 1).  A hypothesis with c_K inliers among the first K
+// points ends with at most c_K + (n - K); with L the full count of any hypothesis of the run
+// (L <= c*), c_K + (n - K) < L - 1 means it cannot be a candidate, and its other n - K points
+// need not be scored.  This is exact, no statistical bail-out; it can engage once K > n - c*,
+// and at C2 the mean count is ~90 of 2000, so almost every hypothesis is hopeless.  Three
+// launches in stream order, every decision on the device:
+//   sample  (kCountWhole) the first G0 = 32 groups of 64 over all points; status[0] = L
+//   prefix  (kCountPrefix) the other groups over [0, K), K = roundup8(n - L + m), m =
+//           max(16, n / 30), the same in every wave since this stage writes its group maxima
+//           to a word of its own (pw[0]) and never to status[0]; K = npad (the whole count,
+//           nobody dropped) when fewer than n / 8 points would be skipped or L <= 1.  The last
+//           finisher of a group (group_done_win) has its 64 final prefix counts in its lanes
+//           and lists the survivors, count + (n - K) >= L - 1: a ballot, one returning atomic
+//           per group on the run's survivor word (~1 550 per C2 launch, spread over it; no
+//           compaction launch), ids in any order
+//   rest    (kCountRest) the survivors over [K, npad) through that list, the survivor count
+//           read on the device as Hdev is; counts land at counts[surv[j]], completed groups
+//           fold their full counts' maxima into status[0], and the first thread folds pw[0]
+//           (a prefix count never exceeds the full count, so pw[0] <= c*) before the
+//           empty-plane return: status[0] is exactly c* before the tail
+// Every candidate survives (its full count >= c* - 1 >= L - 1), so the tail sees the counts
+// it would have seen; dropped hypotheses keep prefix counts below L - 1 - (n - K) < c* - 1.
+// Shards and slices prune against their local L <= local c* <= global c*.
+// Measured (profiles/prune/ab.txt, one box, interleaved with the parent commit's library, G0 =
+// 16 and m = n / 20): a float64 model of the rule on the CPU predicted 0.48 of the counting
+// work at C2 (K ~ 860, 8.5 % survivors) and 0.81 at C5.  C2, kernel trace of the bench (two
+// lanes, so each launch shares the machine; shortest launches in brackets): sample 12.6 us
+// (9.5), prefix 75.5 us (49.0), rest 27.4 us (19.9) against 146.8 us (94.9) for the single
+// launch; the run's count between its timing events, alone on the machine, 91.0-93.9 us
+// against the parent's 98.4-100.8 us in the same rounds (0.93), and the bench value
+// 1.203-1.227e9 against 0.949-0.973e9 hypotheses/s (1.26 x).  The prefix costs what the model
+// says plus its drain (49 us for 0.43 of the plane); the rest of the difference to 0.48 is the
+// two extra launches, whose ~10 us each of launch, ramp and drain buy 1 % and 8 % of the
+// plane.  Alone on the machine that is most of the gain lost; with two lanes the other lane's
+// kernels fill those gaps, which is where the bench value gains.  C5 (1e6 hypotheses, K ~
+// 8 000, long launches): 3.89-3.95 ms per run against 4.68-4.85 ms (0.82, the model's figure).
+// Sweep at C2 (two rounds each): m = 50 / 75 / 100 / 150 / 200 gave 90.0-90.7 / 90.7-90.9 /
+// 92.4-93.2 / 94.1-95.3 / 95.6-96.3 us, G0 = 8 / 16 / 32 gave 93.3-93.8 / 91.1-92.6 /
+// 88.8-89.6 us; hence m = n / 30 and G0 = 32.  With these defaults (session B of the record,
+// five interleaved rounds): count 87.1-88.1 us against the parent's 99.4-99.9 us (0.88), bench
+// value 1.266-1.280e9 against 0.962-0.974e9 hypotheses/s (1.31 x; the first defaults in the same
+// session 1.232-1.244e9), trace sample 12.8 us (9.4), prefix 71.7 us (47.9), rest 27.7 us
+// (20.2), C5 3.81-3.83 ms against 4.71-4.77 ms (0.81).  RSAMD_PRUNE=0 stays inside the parent's
+// range in both sessions.  n / 8 as the least skip worth pruning for never bound at C2 or C5
+// (both prune, both gain) and stays as first set.
 // ----------------------------------------------------------------------------------------
 
 // The float64 test of k_f8_count (pixel units) for one (hypothesis, point).
@@ -255,6 +310,42 @@ __device__ __forceinline__ void group_done_max(int *counts, int *gdone, int *sta
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
   if ((threadIdx.x & 63) == 0 && v > 0) atomicMax(&status[0], v);
+}
+
+// Stages of the pruned count (k_f8_count32q's MODE): the whole window, the prefix [0, K) of the
+// groups past the sample, the rest [K, npad) of the survivors.
+constexpr int kCountWhole = 0, kCountPrefix = 1, kCountRest = 2;
+
+// group_done_max of a windowed stage: gd counts the window's `target` points of the group, the
+// lane's final count is counts[hc] (valid lanes), and the group's max goes to cword.  The
+// prefix stage (rest >= 0: points past the window) also lists its survivors, the lanes whose
+// count + rest can still reach L - 1: one ballot and one returning atomic on the run's
+// survivor word per group, ids in any order.
+template <int MODE>
+__device__ __forceinline__ void group_done_win(const int *counts, int *gd, int *cword, int len,
+                                               int target, int hc, bool valid, int h, int rest,
+                                               int L, int *nsurv, int *surv) {
+  wait_vmem();
+  const int lane = threadIdx.x & 63;
+  int last = 0;
+  if (lane == 0) last = (atomicAdd(gd, len) + len == target) ? 1 : 0;
+  last = __shfl(last, 0);
+  if (!last) return;
+  const int c = valid ? ld_agent(&counts[hc]) : 0;
+  int v = c;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
+  if (lane == 0 && v > 0) atomicMax(cword, v);
+  if constexpr (MODE == kCountPrefix) {
+    if (rest < 0) return;  // K = npad: the prefix was the whole count
+    const bool keep = valid && c + rest >= L - 1;
+    const unsigned long long bal = __ballot(keep);
+    if (bal == 0ull) return;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(nsurv, __popcll(bal));
+    base = __shfl(base, 0);
+    if (keep) surv[base + __popcll(bal & ((1ull << lane) - 1ull))] = h;
+  }
 }
 
 #ifndef RSAMD_COUNT_LDS
@@ -325,7 +416,7 @@ __device__ __forceinline__ void pair_terms(f2q P01, f2q P23, f2q P45, f2q P67, f
 // set by the plan only under RSAMD_TSTAMP, for the launch-shape analysis.
 __device__ uint64_t *g_count_ts = nullptr;
 
-template <int BT>
+template <int BT, int MODE>
 __global__ __launch_bounds__(BT) void k_f8_count32q(const float4 *__restrict__ ptsq,
                                                      const Pt *__restrict__ pts, int n, int H,
                                                      const float *__restrict__ F32soa,
@@ -335,7 +426,8 @@ __global__ __launch_bounds__(BT) void k_f8_count32q(const float4 *__restrict__ p
                                                      int *__restrict__ gdone,
                                                      int *__restrict__ status,
                                                      const float4 *__restrict__ G4,
-                                                     const int *__restrict__ Hdev) {
+                                                     const int *__restrict__ Hdev,
+                                                     PruneArgs pa) {
 #pragma clang fp contract(off)
   typedef float f2 __attribute__((ext_vector_type(2)));
   const int lane = threadIdx.x & 63;
@@ -348,7 +440,52 @@ __global__ __launch_bounds__(BT) void k_f8_count32q(const float4 *__restrict__ p
   const int bslot = xc * xq + min(xc, xr) + (bx >> 3);
   const int64_t w = wave_uniform(bslot * (BT / 64) + (threadIdx.x >> 6));
   const int npad = (n + 7) / 8 * 8;
-  if (Hdev) {
+  // the stage's point window (win points: [0, K) or [K, npad)) and first hypothesis hoff: the
+  // pointers are moved there once, so the slice loop below is the same in every stage with win
+  // for npad; rest / Lq: the prefix stage's points past the window (-1: none skipped) and L
+  int win = npad, hoff = 0, rest = -1, Lq = 0;
+  if constexpr (MODE == kCountPrefix) {
+    // K from L = status[0], the sample stage's best full count, which no wave of this launch
+    // writes (the group maxima go to pw[0]): every wave computes the same K
+    Lq = status[0];
+    int K = max(8, (n - Lq + pa.margin + 7) / 8 * 8);
+    if (Lq <= 1 || K > npad - pa.min_skip) K = npad;  // too little to skip: the whole count
+    if (bx == 0 && threadIdx.x == 0) {
+      pa.pw[2] = K;
+      pa.pw[3] = Lq;
+    }
+    win = K;
+    if (K < npad) rest = n - K;
+    hoff = pa.g_first * 64;
+    H -= hoff;
+    F32soa += hoff;
+    Fsoa += hoff;
+    G4 += hoff;
+    counts += hoff;
+    gdone += pa.g_first;
+    const int64_t tot = static_cast<int64_t>((H + 63) >> 6) * win;
+    const int64_t Wd = max<int64_t>(1, min<int64_t>(static_cast<int64_t>(nb) * (BT / 64), tot / 64));
+    per_wave = ((tot + Wd - 1) / Wd + 7) / 8 * 8;
+  }
+  if constexpr (MODE == kCountRest) {
+    // c*: the prefix stage's maximum (a prefix count never exceeds the full count; the true
+    // maximum of its groups when K = npad) joins the sample's before the empty-plane return
+    if (bx == 0 && threadIdx.x == 0) {
+      const int ca = pa.pw[0];
+      if (ca > 0) atomicMax(&status[0], ca);
+    }
+    const int K = pa.pw[2];
+    H = min(H, pa.pw[1]);  // the survivors
+    win = npad - K;
+    const int64_t tot = static_cast<int64_t>((H + 63) >> 6) * win;
+    if (tot == 0) return;  // uniform over the grid, before any barrier
+    ptsq += K;
+    pts += K;
+    gdone = pa.gdone_b;
+    const int64_t Wd = max<int64_t>(1, min<int64_t>(static_cast<int64_t>(nb) * (BT / 64), tot / 64));
+    per_wave = ((tot + Wd - 1) / Wd + 7) / 8 * 8;
+  }
+  if (MODE == kCountWhole && Hdev) {
     // the hypothesis count on the device (at most H, the bound the grid was sized for): the
     // slice length from it as count32q_shape would, so no host round trip before the launch
     H = min(H, *Hdev);
@@ -357,7 +494,7 @@ __global__ __launch_bounds__(BT) void k_f8_count32q(const float4 *__restrict__ p
     const int64_t Wd = max<int64_t>(1, min<int64_t>(static_cast<int64_t>(nb) * (BT / 64), tot / 64));
     per_wave = ((tot + Wd - 1) / Wd + 7) / 8 * 8;
   }
-  const int64_t total = static_cast<int64_t>((H + 63) >> 6) * npad;
+  const int64_t total = static_cast<int64_t>((H + 63) >> 6) * win;
   int64_t pos = w * per_wave;
   const int64_t end = min(total, pos + per_wave);
 #if RSAMD_COUNT_LDS
@@ -370,7 +507,7 @@ __global__ __launch_bounds__(BT) void k_f8_count32q(const float4 *__restrict__ p
   __shared__ int s_cnt[kCountGrpSlots * 64];
   __shared__ int s_len[kCountGrpSlots];
   __shared__ int s_fin;
-  const int g0 = static_cast<int>(min(total - 1, bslot * (BT / 64) * per_wave) / npad);
+  const int g0 = static_cast<int>(min(total - 1, bslot * (BT / 64) * per_wave) / win);
   for (int x = threadIdx.x; x < kCountGrpSlots * 64; x += BT) s_cnt[x] = 0;
   if (threadIdx.x < kCountGrpSlots) s_len[threadIdx.x] = 0;
   if (threadIdx.x == 0) s_fin = 0;
@@ -381,12 +518,13 @@ __global__ __launch_bounds__(BT) void k_f8_count32q(const float4 *__restrict__ p
   const uint64_t c_start = ts ? __builtin_amdgcn_s_memtime() : 0ull;  // shader clock
   int n_retest = 0;  // re-test branches taken (timeline diagnostics)
   while (pos < end) {
-    const int grp = static_cast<int>(pos / npad);
-    const int p0 = static_cast<int>(pos - static_cast<int64_t>(grp) * npad);
-    const int p1 = static_cast<int>(min(static_cast<int64_t>(npad), p0 + (end - pos)));
+    const int grp = static_cast<int>(pos / win);
+    const int p0 = static_cast<int>(pos - static_cast<int64_t>(grp) * win);
+    const int p1 = static_cast<int>(min(static_cast<int64_t>(win), p0 + (end - pos)));
     pos += p1 - p0;
     const int h = grp * 64 + lane;
-    const int hl = h < H ? h : H - 1;
+    int hl = h < H ? h : H - 1;
+    if constexpr (MODE == kCountRest) hl = pa.surv[hl];  // the survivor's hypothesis
     float f[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) f[k] = F32soa[k * ld + hl];
@@ -441,8 +579,14 @@ __global__ __launch_bounds__(BT) void k_f8_count32q(const float4 *__restrict__ p
       continue;
     }
 #endif
-    if (h < H) atomicAdd(&counts[h], cnt);
-    if (gdone) group_done_max(counts, gdone, status, grp, p1 - p0, npad, h, H);
+    if constexpr (MODE == kCountWhole) {
+      if (h < H) atomicAdd(&counts[h], cnt);
+      if (gdone) group_done_max(counts, gdone, status, grp, p1 - p0, npad, h, H);
+    } else {
+      if (h < H) atomicAdd(&counts[hl], cnt);
+      group_done_win<MODE>(counts, &gdone[grp], MODE == kCountPrefix ? &pa.pw[0] : &status[0],
+                           p1 - p0, win, hl, h < H, h + hoff, rest, Lq, &pa.pw[1], pa.surv);
+    }
   }
 #if RSAMD_COUNT_LDS
   {
@@ -460,8 +604,16 @@ __global__ __launch_bounds__(BT) void k_f8_count32q(const float4 *__restrict__ p
         const int grp = g0 + k, h = grp * 64 + lane;
         const int c = __hip_atomic_load(&s_cnt[k * 64 + lane], __ATOMIC_RELAXED,
                                         __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (h < H) atomicAdd(&counts[h], c);
-        if (gdone) group_done_max(counts, gdone, status, grp, len, npad, h, H);
+        if constexpr (MODE == kCountWhole) {
+          if (h < H) atomicAdd(&counts[h], c);
+          if (gdone) group_done_max(counts, gdone, status, grp, len, npad, h, H);
+        } else {
+          int hc = h < H ? h : H - 1;
+          if constexpr (MODE == kCountRest) hc = pa.surv[hc];
+          if (h < H) atomicAdd(&counts[hc], c);
+          group_done_win<MODE>(counts, &gdone[grp], MODE == kCountPrefix ? &pa.pw[0] : &status[0],
+                               len, win, hc, h < H, h + hoff, rest, Lq, &pa.pw[1], pa.surv);
+        }
       }
     }
   }
@@ -1135,9 +1287,33 @@ hipError_t launch_f8_count32q(const float4 *ptsq, const Pt *pts, int n, int H,
                               const Count32qShape &sh, const GuardW &g, int *counts,
                               hipStream_t s, int *gdone, int *status, const float4 *G4,
                               const int *Hdev) {
-  hipLaunchKernelGGL((k_f8_count32q<kCountBT>), dim3(static_cast<unsigned>(sh.blocks)), dim3(kCountBT), 0,
-                     s, ptsq, pts, n, H, F32soa, Fsoa, ld, sh.per_wave, g, counts, gdone, status,
-                     G4, Hdev);
+  hipLaunchKernelGGL((k_f8_count32q<kCountBT, kCountWhole>), dim3(static_cast<unsigned>(sh.blocks)),
+                     dim3(kCountBT), 0, s, ptsq, pts, n, H, F32soa, Fsoa, ld, sh.per_wave, g, counts,
+                     gdone, status, G4, Hdev, PruneArgs{});
+  return hipGetLastError();
+}
+
+hipError_t launch_f8_count32q_prefix(const float4 *ptsq, const Pt *pts, int n, int H,
+                                     const float *F32soa, const double *Fsoa, int64_t ld,
+                                     const Count32qShape &sh, const GuardW &g, int *counts,
+                                     hipStream_t s, int *gdone, int *status, const float4 *G4,
+                                     const PruneArgs &pa) {
+  hipLaunchKernelGGL((k_f8_count32q<kCountBT, kCountPrefix>), dim3(static_cast<unsigned>(sh.blocks)),
+                     dim3(kCountBT), 0, s, ptsq, pts, n, H, F32soa, Fsoa, ld, sh.per_wave, g, counts,
+                     gdone, status, G4, nullptr, pa);
+  return hipGetLastError();
+}
+
+hipError_t launch_f8_count32q_rest(const float4 *ptsq, const Pt *pts, int n, int H,
+                                   const float *F32soa, const double *Fsoa, int64_t ld, int waves,
+                                   const Count32qShape &bound, const GuardW &g, int *counts,
+                                   hipStream_t s, int *status, const float4 *G4,
+                                   const PruneArgs &pa) {
+  const int64_t blocks = std::max<int64_t>(
+      1, std::min<int64_t>(bound.blocks, (waves + kCountBT / 64 - 1) / (kCountBT / 64)));
+  hipLaunchKernelGGL((k_f8_count32q<kCountBT, kCountRest>), dim3(static_cast<unsigned>(blocks)),
+                     dim3(kCountBT), 0, s, ptsq, pts, n, H, F32soa, Fsoa, ld, int64_t{0}, g, counts,
+                     nullptr, status, G4, nullptr, pa);
   return hipGetLastError();
 }
 

@@ -6,7 +6,10 @@
 // ("lane"): rs_f8_plan_run(k) enqueues on its lane
 //
 //   k_f8_tail_solve  [selection tail of the lane's previous run | solve of run k]  (one launch)
-//   k_f8_count32x    counts of run k (+ fused c*)
+//   k_f8_count32x    counts of run k (+ fused c*): one launch, or with the pruned count
+//                    (RSAMD_PRUNE=1, the fp32 path) three in a row on the same lane -- sample,
+//                    prefix, rest (f8_kernels.hip above k_f8_count32q) -- with no host decision
+//                    and no event between them
 //
 // and leaves run k's tail pending on that lane: it rides along with the lane's next solve, or
 // is flushed alone by rs_f8_plan_result / set_points / destroy (plan_flush, the only place the
@@ -69,6 +72,13 @@ struct RunBufs {
   rsd::F8DevResult *d_res = nullptr;
   int *d_gdone = nullptr;      // per-group finish counters (fused c* in k_f8_count32x)
   float4 *d_G4 = nullptr;      // per-hypothesis decision constants (k_f8_count32q)
+  // pruned count: the run's words (rsd::kPruneWords), the survivor list, the rest stage's
+  // per-group finish counters; staged: the set's last run went through the three stages
+  int *d_pw = nullptr;
+  int *d_surv = nullptr;
+  int *d_gdone_b = nullptr;
+  bool staged = false;
+  double thresh = 0.0;         // the last run's threshold (rs_f8_plan_counts' recount)
   // host tuples (parity mode fed from the host) are staged in a pinned buffer owned by the
   // set, so the caller's array may go away as soon as rs_f8_plan_run returns; ev_copy marks
   // the end of the H2D copy that last read it (waited for before the buffer is refilled)
@@ -81,6 +91,13 @@ struct RunBufs {
 // rs_f8_plan::overlap (two lanes) unless RSAMD_OVERLAP is set: two lanes measured 8-9 % ahead
 // of one in every interleaved bench run (profiles/lanes/ab.txt)
 constexpr int kOverlapDefault = 1;
+// rs_f8_plan::prune and the sample size unless RSAMD_PRUNE / RSAMD_PRUNE_SAMPLE are set; the
+// margin and the least number of skipped points worth pruning for come from n
+// (profiles/prune/ab.txt)
+constexpr int kPruneDefault = 1;
+constexpr int kPruneSampleDefault = 32;
+constexpr int kPruneMarginDiv = 30;   // m = max(16, n / 30)
+constexpr int kPruneMinSkipDiv = 8;   // prune only when at least n / 8 points are skipped
 
 int env_int(const char *name, int dflt) {
   const char *v = std::getenv(name);
@@ -140,6 +157,15 @@ struct rs_f8_plan {
   int q_waves = 6144;         // resident waves of the fp32 kernel (RSAMD_WAVES)
   int q_slices = 0;           // slices per resident wave (RSAMD_QSLICES; 0: count32q_shape)
   int tail_cus = 256;         // CUs shared by the tail + solve launch
+  // Pruned count (fp32 path; derivation above k_f8_count32q): a full count of the first
+  // prune_sample groups, the prefix [0, K) of the others, the rest of the survivors.
+  // RSAMD_PRUNE=0: the single whole-window launch.  Margin / min-skip below 0: from n
+  // (prune_params)
+  int prune = kPruneDefault;                // RSAMD_PRUNE
+  int prune_sample = kPruneSampleDefault;   // RSAMD_PRUNE_SAMPLE: hypothesis groups of the sample
+  int prune_margin = -1;                    // RSAMD_PRUNE_MARGIN: m of K = roundup8(n - L + m)
+  int prune_min_skip = -1;                  // RSAMD_PRUNE_MINSKIP: prune only if >= this many points go
+  int *d_full = nullptr;      // rs_f8_plan_counts after a pruned run: the full counts (ld ints)
   int nospec = 0;             // RSAMD_NOSPEC=1 (test hook): the replay extracts S_RANSAC itself
   uint64_t *d_ts = nullptr;   // RSAMD_TSTAMP=<file>: wave timeline of the counting kernel
   const char *ts_path = nullptr;
@@ -157,6 +183,7 @@ static void plan_free(rs_f8_plan *p) {
   (void)hipFree(p->d_p12);
   (void)hipFree(p->d_pts);
   (void)hipFree(p->d_pts32q);
+  (void)hipFree(p->d_full);
   if (p->d_ts) {
     (void)rsd::set_count_timeline(nullptr);
     (void)hipFree(p->d_ts);
@@ -177,6 +204,9 @@ static void plan_free(rs_f8_plan *p) {
     (void)hipFree(b.d_res);
     (void)hipFree(b.d_gdone);
     (void)hipFree(b.d_G4);
+    (void)hipFree(b.d_pw);
+    (void)hipFree(b.d_surv);
+    (void)hipFree(b.d_gdone_b);
     if (b.h_tuples) (void)hipHostFree(b.h_tuples);
     if (b.ev_copy) (void)hipEventDestroy(b.ev_copy);
   }
@@ -256,6 +286,9 @@ extern "C" int rs_f8_plan_create(rs_ctx *c, int64_t n, int64_t max_hyp, rs_f8_pl
     ALLOC(b.d_res, res_bytes);
     ALLOC(b.d_gdone, sizeof(int) * (p->ld / 64));
     ALLOC(b.d_G4, sizeof(float4) * p->ld);
+    ALLOC(b.d_pw, sizeof(int) * rsd::kPruneWords);
+    ALLOC(b.d_surv, sizeof(int) * p->ld);
+    ALLOC(b.d_gdone_b, sizeof(int) * (p->ld / 64));
   }
 #undef ALLOC
   for (int k = 0; k < rs_f8_plan::kSlots; ++k) {
@@ -270,9 +303,14 @@ extern "C" int rs_f8_plan_create(rs_ctx *c, int64_t n, int64_t max_hyp, rs_f8_pl
       if (e == hipSuccess) e = hipEventCreate(&ev);
   p->overlap = env_int("RSAMD_OVERLAP", kOverlapDefault) != 0;
   p->nospec = env_int("RSAMD_NOSPEC", 0) != 0;
+  p->prune = env_int("RSAMD_PRUNE", kPruneDefault) != 0;
+  p->prune_sample = std::max(1, env_int("RSAMD_PRUNE_SAMPLE", kPruneSampleDefault));
+  p->prune_margin = env_int("RSAMD_PRUNE_MARGIN", -1);
+  p->prune_min_skip = env_int("RSAMD_PRUNE_MINSKIP", -1);
   p->ts_path = std::getenv("RSAMD_TSTAMP");
   if (p->ts_path) {
     p->overlap = false;  // one device-global timeline buffer: one counting launch at a time
+    p->prune = 0;        // ... and one launch per run
     const size_t tsb = sizeof(uint64_t) * rsd::kCountTsWords * (static_cast<size_t>(p->q_waves) * 64 + 1024);
     if (hipMalloc(&p->d_ts, tsb) == hipSuccess) {
       (void)hipMemset(p->d_ts, 0, tsb);
@@ -438,6 +476,20 @@ static int choose_chunk(const rs_f8_plan *p, int64_t H) {
   return static_cast<int>((p->n + nchunks - 1) / nchunks);
 }
 
+// The pruned count's arguments for buffer set b: the margin m = max(16, n / 30) and the least
+// skip n / 8 (at least one block of 8 points) unless the environment gave them
+static rsd::PruneArgs prune_args(const rs_f8_plan *p, const RunBufs &b) {
+  const int n = static_cast<int>(p->n);
+  rsd::PruneArgs pa{};
+  pa.pw = b.d_pw;
+  pa.surv = b.d_surv;
+  pa.gdone_b = b.d_gdone_b;
+  pa.g_first = std::min(p->prune_sample, 1 << 24);
+  pa.margin = p->prune_margin >= 0 ? std::min(p->prune_margin, n) : std::max(16, n / kPruneMarginDiv);
+  pa.min_skip = std::max(8, p->prune_min_skip >= 0 ? p->prune_min_skip : n / kPruneMinSkipDiv);
+  return pa;
+}
+
 // One run.  dev_tuples: tuple mode with the tuples already written (in range, by the GPU
 // parity stream) into the buffer set this run uses, so there is no host copy or check.
 static int plan_run(rs_f8_plan *p, int64_t H, int32_t mode, uint64_t seed, uint64_t hyp_offset,
@@ -533,6 +585,15 @@ static int plan_run(rs_f8_plan *p, int64_t H, int32_t mode, uint64_t seed, uint6
     sa.gDe = gb.De;
     sa.gDn = gb.Dn;
   }
+  // the pruned count's stages, when the run has hypotheses past the sample
+  const int h0 = static_cast<int>(std::min<int64_t>(H, 64LL * std::min(p->prune_sample, 1 << 24)));
+  const bool staged = fp32 && p->prune && h0 < h;
+  b.staged = staged;
+  b.thresh = thresh;
+  if (staged) {
+    sa.pw = b.d_pw;
+    sa.gdone_b = b.d_gdone_b;
+  }
   if (excl && tl >= 2) {
     HIP_TRY(hipEventRecord(ev_end, lane_stream(p, other)));
     HIP_TRY(hipStreamWaitEvent(ms, ev_end, 0));
@@ -549,7 +610,21 @@ static int plan_run(rs_f8_plan *p, int64_t H, int32_t mode, uint64_t seed, uint6
     HIP_TRY(hipStreamWaitEvent(ms, ev_end, 0));
   }
   if (tl >= 1) HIP_TRY(hipEventRecord(ev[0], ms));
-  if (fp32) {
+  if (staged) {
+    // sample (whole window, c* of its groups = L in status[0]) -> prefix [0, K) of the other
+    // groups, K from L on the device, survivors listed -> rest [K, npad) of the survivors;
+    // all three in stream order on this lane, no host decision
+    const rsd::GuardW gw{thresh * thresh};
+    const rsd::Count32qShape sh0 = rsd::count32q_shape(n, h0, p->q_waves, p->q_slices);
+    HIP_TRY(rsd::launch_f8_count32q(p->d_pts32q, p->d_pts, n, h0, b.d_F32, b.d_F, p->ld, sh0, gw,
+                                    b.d_counts, ms, b.d_gdone, b.d_status, b.d_G4));
+    const rsd::PruneArgs pa = prune_args(p, b);
+    const rsd::Count32qShape sh1 = rsd::count32q_shape(n, h - h0, p->q_waves, p->q_slices);
+    HIP_TRY(rsd::launch_f8_count32q_prefix(p->d_pts32q, p->d_pts, n, h, b.d_F32, b.d_F, p->ld, sh1,
+                                           gw, b.d_counts, ms, b.d_gdone, b.d_status, b.d_G4, pa));
+    HIP_TRY(rsd::launch_f8_count32q_rest(p->d_pts32q, p->d_pts, n, h - h0, b.d_F32, b.d_F, p->ld,
+                                         p->q_waves, sh1, gw, b.d_counts, ms, b.d_status, b.d_G4, pa));
+  } else if (fp32) {
     // fused c*: the chunk that completes a hypothesis group folds its max into status[0]
     const rsd::Count32qShape sh = rsd::count32q_shape(n, h, p->q_waves, p->q_slices);
     HIP_TRY(rsd::launch_f8_count32q(p->d_pts32q, p->d_pts, n, h, b.d_F32, b.d_F, p->ld, sh,
@@ -764,7 +839,51 @@ extern "C" int rs_f8_plan_counts(rs_f8_plan *p, int32_t *counts, int64_t H) {
   int st = plan_wait(p);
   if (st) return st;
   if (H > p->last_H) return fail(RS_EINVAL, "H exceeds the last run");
-  HIP_TRY(hipMemcpy(counts, p->last().d_counts, sizeof(int) * H, hipMemcpyDeviceToHost));
+  const RunBufs &b = p->last();
+  const int *src = b.d_counts;
+  int pw[rsd::kPruneWords] = {};
+  if (b.staged) HIP_TRY(hipMemcpy(pw, b.d_pw, sizeof(pw), hipMemcpyDeviceToHost));
+  const int n = static_cast<int>(p->n);
+  if (b.staged && pw[2] < (n + 7) / 8 * 8) {
+    // a pruned run leaves prefix counts for the hypotheses it dropped: the full counts come
+    // from the whole-window kernel over the run's models, still in the buffer set (a
+    // diagnostic accessor; nothing else is in flight after plan_wait)
+    HIP_TRY(hipSetDevice(p->ctx->device));
+    if (!p->d_full) HIP_TRY(hipMalloc(&p->d_full, sizeof(int) * p->ld));
+    hipStream_t s = p->ctx->stream;
+    const int h = static_cast<int>(p->last_H);
+    HIP_TRY(hipMemsetAsync(p->d_full, 0, sizeof(int) * p->ld, s));
+    const rsd::Count32qShape sh = rsd::count32q_shape(n, h, p->q_waves, p->q_slices);
+    HIP_TRY(rsd::launch_f8_count32q(p->d_pts32q, p->d_pts, n, h, b.d_F32, b.d_F, p->ld, sh,
+                                    rsd::GuardW{b.thresh * b.thresh}, p->d_full, s, nullptr,
+                                    nullptr, b.d_G4));
+    HIP_TRY(hipStreamSynchronize(s));
+    src = p->d_full;
+  }
+  HIP_TRY(hipMemcpy(counts, src, sizeof(int) * H, hipMemcpyDeviceToHost));
+  return RS_OK;
+}
+
+extern "C" int rs_f8_plan_prune_stats(rs_f8_plan *p, int64_t *out) {
+  if (!p || !out) return fail(RS_EINVAL, "null pointer");
+  int st = plan_wait(p);
+  if (st) return st;
+  const RunBufs &b = p->last();
+  const int64_t npad = (p->n + 7) / 8 * 8;
+  if (b.staged) {
+    int pw[rsd::kPruneWords] = {};
+    HIP_TRY(hipMemcpy(pw, b.d_pw, sizeof(pw), hipMemcpyDeviceToHost));
+    out[0] = pw[3];
+    out[1] = pw[2];
+    out[2] = pw[1];
+  } else {  // one whole-window launch: its c*, nothing skipped, nobody past a sample
+    int cmax = 0;
+    HIP_TRY(hipMemcpy(&cmax, b.d_status, sizeof(int), hipMemcpyDeviceToHost));
+    out[0] = cmax;
+    out[1] = npad;
+    out[2] = 0;
+  }
+  out[3] = npad;
   return RS_OK;
 }
 

@@ -122,6 +122,7 @@ _SIGS = {
     "rs_f8_plan_kernel_avg": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp, _dp]),
     "rs_f8_plan_set_timing": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "rs_f8_plan_lane_waits": (C.c_int, [C.c_void_p, _i64p]),
+    "rs_f8_plan_prune_stats": (C.c_int, [C.c_void_p, _i64p]),
     "rs_f8_plan_set_count_precision": (C.c_int, [C.c_void_p, C.c_int32]),
     "rs_f8_ransac_np": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64, _u32p, _i32p,
                                   C.c_double, C.POINTER(F8Result), _i64p, C.c_int64, _i64p]),
@@ -644,6 +645,13 @@ class F8Plan:
         k = C.c_int64(0)
         check(lib().rs_f8_plan_lane_waits(self._h, C.byref(k)))
         return k.value
+
+    def prune_stats(self):
+        """The pruned count of the last run: L (best full count of the sample), K (points
+        counted before the hopeless hypotheses were dropped), survivors, npad."""
+        out = (C.c_int64 * 4)()
+        check(lib().rs_f8_plan_prune_stats(self._h, out))
+        return {"L": out[0], "K": out[1], "survivors": out[2], "npad": out[3]}
 
     def kernel_ms(self, last_n=1):
         """Device times of the last run, or averaged over the last ``last_n`` runs."""
