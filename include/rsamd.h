@@ -6,8 +6,8 @@
  * Drop-in boundary for bioengstrom/tsbb15-3d-reconstruction-project (snapshot v0).  The
  * reference has no FFI: its boundary is the Python module surface.  Each
  * entry point below names the reference function it replaces; the Python shims in
- * tsbb15_amd/ (lab3.py, fun.py, ransac.py, pnp.py, cv.py, tables.py) bind these through ctypes with the
- * reference's names, argument meaning and ValueError behaviour.
+ * tsbb15_amd/ (lab3.py, fun.py, ransac.py, pnp.py, cv.py, tables.py, features.py) bind these
+ * through ctypes with the reference's names, argument meaning and ValueError behaviour.
  *
  * Conventions
  *   - every function returns int status: RS_OK (0) or a negative RS_E* code; the message of
@@ -640,6 +640,74 @@ int rs_wash_points(rs_ctx *ctx, const double *cams, int64_t nC, double *pts, int
                    const int32_t *obs_view, const int32_t *obs_point, const double *uv, int64_t n,
                    double thresh, int32_t min_views, int32_t depth_sign,
                    int32_t *obs_keep, int32_t *point_keep, double *err2, rs_wash_info *info);
+
+/* ------------------------------------------------------------------------------------------
+ * The image front end (features.hip): the recipe of fun.py:130-151 that turns two images into
+ * the (2, N) putative correspondences fun.getFFromLabCode consumes.  Images are row-major
+ * (h, w); sides are at most RS_IMAGE_MAX_SIDE.  No floating-point atomics: the same inputs give
+ * bitwise the same outputs.
+ * ------------------------------------------------------------------------------------------ */
+#define RS_IMAGE_MAX_SIDE 32768
+#define RS_HARRIS_MAX_BLOCK 31         /* keeps the integer structure tensor below 2^53 */
+#define RS_MATCH_MAX_ROI 15
+#define RS_MATCH_MAX_N 32768           /* patches per image */
+#define RS_MATCH_MAX_PAIRS (1LL << 28) /* n1 * n2 when the matrix is requested (2 GiB) */
+
+/* lab3.harris (lab3.py:131-157) on a uint8 grey image, by the documented cornerHarris: Sobel
+ * derivatives of aperture kernel_size (1: [-1 0 1] unsmoothed; 3: [1 2 1] x [-1 0 1]; 5, 7: the
+ * binomial extensions), the unnormalised block_size x block_size box sum of Ix^2, IxIy, Iy^2
+ * with its anchor at block_size / 2, reflect-101 borders for both steps, scale
+ * s = 1 / (2^(kernel_size-1) block_size 255) on both derivatives, response
+ * a c - b^2 - k (a + c)^2.  The tensor is summed in integers (exact) and the response is
+ * evaluated once in fp64 and rounded to float: the result does not depend on the tiling.
+ * raw == 0 sets negatives to zero (lab3.py:156).  RS_EINVAL: kernel_size not in {1, 3, 5, 7}
+ * (the text of lab3.py:149), block_size outside 1..RS_HARRIS_MAX_BLOCK, k not finite, a side
+ * above RS_IMAGE_MAX_SIDE or not above max(1, kernel_size / 2) + block_size. */
+int rs_harris(rs_ctx *ctx, const uint8_t *image, int64_t h, int64_t w, int32_t block_size,
+              int32_t kernel_size, double k, int32_t raw, float *out);
+
+/* lab3.non_max_suppression (lab3.py:160-185) on a finite float image: a pixel keeps its value
+ * when no pixel of its window_size^2 window is larger and it lies at least (window_size-1)/2
+ * from every border; every other pixel becomes 0 * value, as the reference's False * value.
+ * Bitwise the reference's result.  RS_EINVAL: an even window_size (the text of lab3.py:175). */
+int rs_non_max_suppression(rs_ctx *ctx, const float *image, int64_t h, int64_t w,
+                           int32_t window_size, float *out);
+
+/* The corner list of fun.py:135-138: the positions with (double)H > rel * (double)max(H), in
+ * row-major scan order (np.nonzero's).  xy has room for (2, cap): x (column) of hit k at xy[k],
+ * y (row) at xy[cap + k]; *count is the number of hits.  A device max reduction, then an
+ * order-preserving compaction (hits per chunk, scan, write at offset + rank).  H finite.
+ * RS_EINVAL: rel not finite, more hits than cap (*count is still set). */
+int rs_corners(rs_ctx *ctx, const float *H, int64_t h, int64_t w, double rel, int32_t *xy,
+               int64_t cap, int64_t *count);
+
+/* lab3.cut_out_rois (lab3.py:565-602) fused into fun.matchingMatrix (fun.py:113-120) and the
+ * two argmins of lab3.joint_min (lab3.py:551-552).  xy1 is (2, n1) int32 -- x row, y row -- of
+ * patch centres in img1, xy2 likewise; M[i, j] = |roi1_i - roi2_j|_F over the roi_size^2
+ * patches.  row_min[i] = argmin_j M[i, j] with row_val[i] its value, col_min[j] = argmin_i
+ * M[i, j]; ties go to the smallest index (np.argmin), whatever the block schedule.  M, (n1, n2)
+ * row-major, is written when not null; the argmins never need it in memory.
+ * uint8: the squared distance is an exact integer and M its correctly rounded root; wrap != 0
+ * takes the differences modulo 256, as the reference's uint8 roi1[i] - roi2[j] does.
+ * RS_EINVAL: roi_size even (the text of lab3.py:586) or above RS_MATCH_MAX_ROI, n1 or n2
+ * outside 1..RS_MATCH_MAX_N, n1 * n2 > RS_MATCH_MAX_PAIRS with M requested, a centre nearer
+ * than roi_size / 2 to a border. */
+int rs_match_rois_u8(rs_ctx *ctx, const uint8_t *img1, int64_t h1, int64_t w1,
+                     const int32_t *xy1, int64_t n1, const uint8_t *img2, int64_t h2, int64_t w2,
+                     const int32_t *xy2, int64_t n2, int32_t roi_size, int32_t wrap,
+                     int32_t *row_min, int32_t *col_min, double *row_val, double *M);
+
+/* The same for float64 images: fp64 accumulation over the patch in raster order.  The input
+ * must be finite (not checked here). */
+int rs_match_rois_f64(rs_ctx *ctx, const double *img1, int64_t h1, int64_t w1,
+                      const int32_t *xy1, int64_t n1, const double *img2, int64_t h2, int64_t w2,
+                      const int32_t *xy2, int64_t n2, int32_t roi_size, int32_t *row_min,
+                      int32_t *col_min, double *row_val, double *M);
+
+/* HIP events before the first and after the last kernel of the next front-end calls (enable
+ * != 0).  Returns the last timed call's device ms between its upload and its download, -1 when
+ * none (tools/bench_features.py). */
+int rs_features_timing(rs_ctx *ctx, int32_t enable, double *ms);
 
 /* ------------------------------------------------------------------------------------------
  * Multi-GPU (RCCL over xGMI).  One process per GPU; the unique id travels out of band.

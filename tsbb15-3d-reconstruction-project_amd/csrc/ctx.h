@@ -39,6 +39,11 @@ struct rs_ctx {
   hipEvent_t ba_ev[RS_BA_EVENTS] = {};
   double ba_ms[RS_BA_TIMING_SLOTS] = {};
   int64_t ba_trials = 0;
+  // rs_features_timing: HIP events around the kernels of the next front-end calls (features.hip),
+  // the last timed call's device ms between its upload and its download
+  int feat_timing = 0;
+  hipEvent_t feat_ev[2] = {};
+  double feat_ms = -1.0;
 };
 
 namespace rs {

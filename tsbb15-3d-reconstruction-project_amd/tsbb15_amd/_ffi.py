@@ -28,6 +28,7 @@ _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
 _u32p = C.POINTER(C.c_uint32)
 _u8p = C.POINTER(C.c_uint8)
+_fp = C.POINTER(C.c_float)
 
 
 class F8Result(C.Structure):
@@ -178,6 +179,18 @@ _SIGS = {
     "rs_wash_points": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _i32p, _i32p, _dp,
                                  C.c_int64, C.c_double, C.c_int32, C.c_int32, _i32p, _i32p, _dp,
                                  C.POINTER(WashInfo)]),
+    "rs_harris": (C.c_int, [C.c_void_p, _u8p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                            C.c_double, C.c_int32, _fp]),
+    "rs_non_max_suppression": (C.c_int, [C.c_void_p, _fp, C.c_int64, C.c_int64, C.c_int32, _fp]),
+    "rs_corners": (C.c_int, [C.c_void_p, _fp, C.c_int64, C.c_int64, C.c_double, _i32p, C.c_int64,
+                             _i64p]),
+    "rs_match_rois_u8": (C.c_int, [C.c_void_p, _u8p, C.c_int64, C.c_int64, _i32p, C.c_int64, _u8p,
+                                   C.c_int64, C.c_int64, _i32p, C.c_int64, C.c_int32, C.c_int32,
+                                   _i32p, _i32p, _dp, _dp]),
+    "rs_match_rois_f64": (C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int64, _i32p, C.c_int64, _dp,
+                                    C.c_int64, C.c_int64, _i32p, C.c_int64, C.c_int32, _i32p,
+                                    _i32p, _dp, _dp]),
+    "rs_features_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
     "rs_np_shard_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.POINTER(C.c_void_p)]),
     "rs_np_shard_destroy": (C.c_int, [C.c_void_p]),

@@ -18,6 +18,9 @@ The E / pose functions of fun.py (camera_resectioning, getEAndK, MakeHomogenous,
 relative_camera_pose) are re-exported from :mod:`tsbb15_amd.twoview` (HIP kernels).
 
 ``ransac_f`` exposes the loop alone with its knobs (iterations, threshold, RNG, sampler).
+
+``matchingMatrix(roi1, roi2)`` (fun.py:113-120) runs on the patch-matching kernels of
+:mod:`tsbb15_amd.features`.
 """
 from __future__ import annotations
 
@@ -26,6 +29,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _ffi
+from .features import matching_matrix_rois as matchingMatrix  # noqa: F401
 from .twoview import (MakeHomogenous, camera_resectioning, getEAndK,  # noqa: F401
                       relative_camera_pose)
 

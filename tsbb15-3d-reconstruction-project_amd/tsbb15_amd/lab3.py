@@ -12,13 +12,27 @@ Same names, argument layout and errors as the reference toolbox
   * ``triangulate_optimal(C1, C2, x1, x2)`` lab3.py:382-475 -> rs_triangulate_optimal (HIP)
 
 (implemented in :mod:`tsbb15_amd.twoview`, which also holds the batched forms).
+
+  * ``harris(image, block_size, kernel_size)``       lab3.py:131-157 -> rs_harris (HIP)
+  * ``non_max_suppression(image, window_size)``      lab3.py:160-185 -> rs_non_max_suppression (HIP)
+  * ``cut_out_rois(image, cols, rows, roi_size)``    lab3.py:565-602 (host helper, no arithmetic)
+  * ``joint_min(A)``                                 lab3.py:529-563 (host helper on a given matrix)
+
+(implemented in :mod:`tsbb15_amd.features`, which also holds the fused matching).
 """
 from __future__ import annotations
 
 import numpy as np
 
 from . import _ffi
+from .features import cut_out_rois, joint_min, non_max_suppression  # noqa: F401
+from .features import harris as _harris
 from .twoview import fmatrix_cameras, fmatrix_from_cameras, triangulate_optimal  # noqa: F401
+
+
+def harris(image, block_size, kernel_size):
+    """Harris response (float32, negatives set to zero) of a 2-D uint8 image; k = 0.04."""
+    return _harris(image, block_size, kernel_size)
 
 
 def homog(x):
