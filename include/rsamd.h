@@ -710,6 +710,72 @@ int rs_match_rois_f64(rs_ctx *ctx, const double *img1, int64_t h1, int64_t w1,
 int rs_features_timing(rs_ctx *ctx, int32_t enable, double *ms);
 
 /* ------------------------------------------------------------------------------------------
+ * The point-cloud stage (cloud.hip): what main.py does last (main.py:175-176,
+ * Tables.get3DPointsColorsAndNormals) and the surface normals 3Dvisualization.py attempts.
+ * All fp64, one lane per point, no floating-point atomics: the same inputs give bitwise the
+ * same outputs.
+ * ------------------------------------------------------------------------------------------ */
+#define RS_CLOUD_MAX_POINTS (1LL << 28)
+#define RS_CLOUD_MAX_CELLS (1LL << 21) /* cells per axis: 21 bits each in a 63-bit key */
+
+/* The arithmetic of tables.py:189-226.  cams is (nC, 3, 4) [R | t], pts (nP, 3).  The flat list
+ * of m entries (entry_point[i], entry_obs[i]) names the observations each point averages over;
+ * it is grouped by point with entry_point non-decreasing, and within a point it stands in the
+ * order the caller wants summed (an observation may be listed more than once).  obs_view (nObs)
+ * is the view of every observation, obs_color (nObs, 3) its colour as doubles.
+ *   colors[j]  = (sum of the listed colours / entries of j) / 255
+ *   normals[j] = (sum of centre(view) - pts[j]) / entries of j,  centre = -R^T t,
+ * not normalised, exactly as the reference.  Both sums run in list order.  A point without an
+ * entry gets NaN in both.  RS_EINVAL: an index out of range, entry_point decreasing, nC < 1
+ * with m > 0, nP > RS_CLOUD_MAX_POINTS. */
+int rs_cloud_attributes(rs_ctx *ctx, const double *cams, int64_t nC, const double *pts,
+                        int64_t nP, const int32_t *entry_point, const int32_t *entry_obs,
+                        int64_t m, const int32_t *obs_view, const double *obs_color, int64_t nObs,
+                        double *colors, double *normals);
+
+typedef struct rs_cloud_info {
+  int64_t cells_occupied;    /* grid cells that hold a point                        */
+  int64_t largest_cell;      /* points in the fullest cell                          */
+  int64_t pairs_tested;      /* distance predicates evaluated                       */
+  int64_t neighbours_found;  /* sum of count                                        */
+  int64_t rows_not_ok;       /* points with count < 3 (non-finite points included)  */
+} rs_cloud_info;             /* 40 bytes */
+
+/* Surface normals from fixed-radius neighbourhoods (the plane fit of 3Dvisualization.py:16-31
+ * and :96-113, by its mathematics: the reference's outer product and eigenvector pick are wrong
+ * as written).  pts is (n, 3), radius finite and > 0, orient (n, 3) or null.
+ *   N(i) = { j : |p_j - p_i|^2 <= radius^2 } evaluated in fp64 (i itself is a member; the last-
+ *   bit rounding of the predicate -- FMA contraction -- is not specified), count[i] = |N(i)|.
+ *   With d_j = p_j - p_i, s = sum d_j, S = sum d_j d_j^T, k = count[i]:
+ *   M = S / k - (s / k)(s / k)^T, both sums over N(i) in ascending j.  That order is the
+ *   reproducibility contract.
+ *   evals[i] are the eigenvalues of M in ascending order (cyclic Jacobi), normals[i] the unit
+ *   eigenvector of the smallest.  A row is ok iff k >= 3; rows that are not ok get NaN normals
+ *   and NaN evals, their count is still valid.
+ *   Sign: with orient given and orient[i] finite and non-zero, dot(normal, orient[i]) >= 0;
+ *   otherwise the component of largest magnitude is positive (the first such on ties).
+ *   A non-finite point has count 0, is not ok and is nobody's neighbour.
+ * The search is a hash grid: integer cells of side radius (1 + 2^-20) from the minimum corner
+ * `lo` of the finite points, 21 bits per axis, an open-addressed table of >= 2n slots, every
+ * cell's points sorted by index, and per query a merge of its 27 cells in ascending index.
+ * Memory is O(n) whatever the cloud's extent; RS_EINVAL when (p - lo) / radius reaches
+ * RS_CLOUD_MAX_CELLS on any axis (the message states the limit), for a radius not finite or
+ * <= 0 and for n > RS_CLOUD_MAX_POINTS.  The cost is O(n * 27 * points per cell): a cloud that
+ * fits in one cell is O(n^2) by nature, and one lane sorts each cell, so this is not a tool
+ * for radii that swallow the cloud.  Every loop is bounded: a hash probe that runs `capacity`
+ * steps raises a flag that comes back as RS_EDEVICE.  n = 0 returns at once. */
+int rs_cloud_normals(rs_ctx *ctx, const double *pts, int64_t n, double radius,
+                     const double *orient, double *normals, int32_t *count, double *evals,
+                     rs_cloud_info *info);
+
+/* HIP events between the stages of the next point-cloud calls (enable != 0).  Returns the last
+ * timed call's device ms per stage: grid (minimum corner, keys, hash insertion), scan, sort
+ * (scatter and per-cell sort), normals (neighbour walk and eigen-solve), attributes
+ * (rs_cloud_attributes' kernel); -1 where none (tools/bench_cloud.py). */
+#define RS_CLOUD_TIMING_SLOTS 5
+int rs_cloud_timing(rs_ctx *ctx, int32_t enable, double *ms);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU (RCCL over xGMI).  One process per GPU; the unique id travels out of band.
  * ---------------------------------------------------------------------------------------- */
 #define RS_COMM_ID_BYTES 128

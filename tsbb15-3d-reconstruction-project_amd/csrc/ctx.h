@@ -44,6 +44,11 @@ struct rs_ctx {
   int feat_timing = 0;
   hipEvent_t feat_ev[2] = {};
   double feat_ms = -1.0;
+  // rs_cloud_timing: HIP events between the stages of the next point-cloud calls (cloud.hip),
+  // the last timed call's device ms per stage (RS_CLOUD_TIMING_SLOTS)
+  int cloud_timing = 0;
+  hipEvent_t cloud_ev[5] = {};
+  double cloud_ms[RS_CLOUD_TIMING_SLOTS] = {-1.0, -1.0, -1.0, -1.0, -1.0};
 };
 
 namespace rs {

@@ -76,8 +76,16 @@ class WashInfo(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class CloudInfo(C.Structure):
+    _fields_ = [("cells_occupied", C.c_int64), ("largest_cell", C.c_int64),
+                ("pairs_tested", C.c_int64), ("neighbours_found", C.c_int64),
+                ("rows_not_ok", C.c_int64)]
+
+
 BA_MAX_CAMERAS = 128
 WASH_MAX_TRACK = 128
+CLOUD_MAX_CELLS = 1 << 21
+CLOUD_STAGES = ("grid", "scan", "sort", "normals", "attributes")
 BA_KERNELS = ("k_ba_linearize", "k_ba_camera", "k_ba_pointsum", "k_ba_point", "k_ba_schur",
               "k_ba_chol", "k_ba_step", "k_ba_cost+final")
 
@@ -191,6 +199,11 @@ _SIGS = {
                                     C.c_int64, C.c_int64, _i32p, C.c_int64, C.c_int32, _i32p,
                                     _i32p, _dp, _dp]),
     "rs_features_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "rs_cloud_attributes": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _i32p, _i32p,
+                                      C.c_int64, _i32p, _dp, C.c_int64, _dp, _dp]),
+    "rs_cloud_normals": (C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_double, _dp, _dp, _i32p, _dp,
+                                   C.POINTER(CloudInfo)]),
+    "rs_cloud_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
     "rs_np_shard_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.POINTER(C.c_void_p)]),
     "rs_np_shard_destroy": (C.c_int, [C.c_void_p]),

@@ -30,6 +30,7 @@ arithmetic above on the GPU and do the same bookkeeping in the same order):
   * ``BundleAdjustmentRigid(T)``                                   the same write-back around
                                                                    ``bundle_adjust_rigid``
   * ``wash(T, thresh)``                                            the wash step (no reference code)
+  * ``get3DPointsColorsAndNormals(T)``                             Tables.get3DPointsColorsAndNormals
 """
 from __future__ import annotations
 
@@ -376,3 +377,38 @@ def wash(T, thresh, min_views=2, depth_sign=0, ctx=None):
     out = dict(info)
     out["point_map"], out["obs_map"] = point_map, obs_map
     return out
+
+
+def get3DPointsColorsAndNormals(T, radius=None, ctx=None):
+    """Tables.get3DPointsColorsAndNormals (tables.py:216-226) in two GPU calls instead of three
+    quadratic np.concatenate loops.  Returns (points, colors, normals), each (nP, 3).
+
+    The entry list of a point is its observations_index as it stands, including element 0, the
+    reference's spurious 0 (help_classes.py:26): the reference averages over T_obs[0] for every
+    point (tables.py:192, :204), so this does too.  colors are the mean colour / 255, normals the
+    mean of view.getWorldPosition() - point, not normalised (``cloud.point_attributes``).
+
+    With ``radius`` set, normals are instead the unit PCA normals of
+    ``cloud.surface_normals(points, radius)``, each oriented to agree with its view normal; a row
+    that is not ok (fewer than 3 points within ``radius``) falls back to its view normal,
+    normalised.
+
+    Deviation: for a point whose observations_index holds one entry the reference raises
+    (``normal`` is never bound, tables.py:211-214) after dividing the colour without averaging
+    (tables.py:196-198).  Here that point gets that single vector and that single colour / 255."""
+    from . import cloud
+    cams = np.array([_pose(v.camera_pose) for v in T.T_views]).reshape(-1, 3, 4)
+    pts = np.array([p.point for p in T.T_points], dtype=np.float64).reshape(-1, 3)
+    ov = np.array([o.view_index for o in T.T_obs], dtype=np.int32)
+    col = np.array([np.asarray(o.color, dtype=np.float64).ravel()[:3]
+                    for o in T.T_obs]).reshape(-1, 3)
+    idx = [np.asarray(p.observations_index, dtype=np.int32).ravel() for p in T.T_points]
+    entry_obs = np.concatenate(idx) if idx else np.zeros(0, np.int32)
+    entry_point = np.repeat(np.arange(len(idx), dtype=np.int32), [len(i) for i in idx])
+    colors, normals = cloud.point_attributes(cams, pts, entry_point, entry_obs, ov, col, ctx=ctx)
+    if radius is not None:
+        pca, ok, _, _, _ = cloud.surface_normals(pts, radius, orient=normals, ctx=ctx)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            unit = normals / np.linalg.norm(normals, axis=1, keepdims=True)
+        normals = np.where(ok[:, None], pca, unit)
+    return pts, colors, normals
