@@ -259,6 +259,11 @@ int rs_f8_plan_lane_waits(rs_f8_plan *plan, int64_t *waits);
  * run that was not pruned reports K = npad and no survivors.  Results are those of the
  * unpruned count in every field; rs_f8_plan_counts recounts after a pruned run. */
 int rs_f8_plan_prune_stats(rs_f8_plan *plan, int64_t out[4]);
+/* The counting stages' own per-hypothesis counts of the last run, with no recount (test &
+ * diagnostics).  After a pruned run: the full count of a sample hypothesis or a survivor, and
+ * for a dropped hypothesis K minus its certified outliers among the first K points, an upper
+ * bound of its count there (below L - 1 - (n - K)).  Otherwise what rs_f8_plan_counts returns. */
+int rs_f8_plan_stage_counts(rs_f8_plan *plan, int32_t *counts, int64_t H);
 /* Device time (ms, HIP events on the run's stream lane; a run that records them runs its
  * counting kernel alone, without the other lane's kernels beside it) of the counting kernel,
  * the solve kernel and the whole run: of the last run, or averaged over the last `last_n` runs (<= 64).  Runs

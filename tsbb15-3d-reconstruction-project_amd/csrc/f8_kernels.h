@@ -109,10 +109,11 @@ hipError_t launch_f8_count32q(const float4 *ptsq, const Pt *pts, int n, int H,
                               hipStream_t s, int *gdone, int *status, const float4 *G4,
                               const int *Hdev = nullptr);
 // Pruned count (derivation above k_f8_count32q): after a full count of the first g_first
-// hypothesis groups has left L in status[0], the prefix stage counts the other groups over the
-// points [0, K) only, K from L on the device, and lists the hypotheses that can still reach
-// L - 1 (surv); the rest stage counts those over [K, npad) through the list.  Per-run words:
-constexpr int kPruneWords = 4;  // [0] cA (max prefix count), [1] survivors, [2] K, [3] L
+// hypothesis groups has left L in status[0], the prefix stage screens the other groups over the
+// points [0, K) only (certified outliers, no inlier count), K from L on the device, and lists
+// the hypotheses that can still reach L - 1 (surv); the rest stage counts those over the whole
+// window through the list.  Per-run words:
+constexpr int kPruneWords = 4;  // [0] cA (max count when K = npad), [1] survivors, [2] K, [3] L
 struct PruneArgs {
   int *pw;       // the run's words
   int *surv;     // survivor hypothesis ids (ld ints)

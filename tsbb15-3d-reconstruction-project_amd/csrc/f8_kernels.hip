@@ -239,26 +239,56 @@ __global__ __launch_bounds__(256) void k_f8_count(const Pt *__restrict__ pts, in
 // points ends with at most c_K + (n - K); with L the full count of any hypothesis of the run
 // (L <= c*), c_K + (n - K) < L - 1 means it cannot be a candidate, and its other n - K points
 // need not be scored.  This is exact, no statistical bail-out; it can engage once K > n - c*,
-// and at C2 the mean count is ~90 of 2000, so almost every hypothesis is hopeless.  Three
-// launches in stream order, every decision on the device:
+// and at C2 the mean count is ~90 of 2000, so almost every hypothesis is hopeless.
+// The decision needs no inlier count, only a lower bound o on the outliers among the first K
+// points: c_K <= c' = K - o.  So the prefix stage screens instead of counting.  A point is a
+// certain outlier when fl(e^2 - ko) > fl(beta n1), with n1 = a^2 + b^2 of the first line alone:
+// m = min(n1, n2) <= n1, fl(beta x) is monotone in x for beta >= 0 (f32_model: c >= 100 De, so
+// r <= 0.01 and beta > 0), hence fl(beta m) <= fl(beta n1) < Q, which is the sure-outlier test
+// !(Q <= S) of the full decision above, and that implies a float64 outlier.  a, b, l3, e and n1
+// are computed by pair_terms' operations in its order (screen_terms), so they are its bits.
+// The compare is Q > S: NaN certifies nothing, and a NaN or degenerate model survives.  This
+// drops c, d, n2, both v_min, P, R, two compares, the ambiguity XOR and the float64 re-test
+// with its scalar work: 12 packed ops + 2 compares + 2 count ops per point pair, 56 SIMD
+// cycles against 96.  The price: a survivor has no exact prefix count and is counted again
+// from point 0.  Three launches in stream order, every decision on the device:
 //   sample  (kCountWhole) the first G0 = 32 groups of 64 over all points; status[0] = L
 //   prefix  (kCountPrefix) the other groups over [0, K), K = roundup8(n - L + m), m =
-//           max(16, n / 30), the same in every wave since this stage writes its group maxima
-//           to a word of its own (pw[0]) and never to status[0]; K = npad (the whole count,
-//           nobody dropped) when fewer than n / 8 points would be skipped or L <= 1.  The last
-//           finisher of a group (group_done_win) has its 64 final prefix counts in its lanes
-//           and lists the survivors, count + (n - K) >= L - 1: a ballot, one returning atomic
-//           per group on the run's survivor word (~1 550 per C2 launch, spread over it; no
-//           compaction launch), ids in any order
-//   rest    (kCountRest) the survivors over [K, npad) through that list, the survivor count
-//           read on the device as Hdev is; counts land at counts[surv[j]], completed groups
-//           fold their full counts' maxima into status[0], and the first thread folds pw[0]
-//           (a prefix count never exceeds the full count, so pw[0] <= c*) before the
-//           empty-plane return: status[0] is exactly c* before the tail
-// Every candidate survives (its full count >= c* - 1 >= L - 1), so the tail sees the counts
-// it would have seen; dropped hypotheses keep prefix counts below L - 1 - (n - K) < c* - 1.
+//           max(16, n / 30), the same in every wave since this stage never writes status[0];
+//           K = npad when fewer than n / 8 points would be skipped or L <= 1: then (a
+//           grid-uniform branch) it runs the exact loop, its counts are final, the group
+//           maxima go to a word of their own (pw[0]) and nobody is listed.  Otherwise the
+//           screening loop over [0, K) (K <= npad - 8: no padding point) sums the certified
+//           outliers into counts[]; the last finisher of a group (group_done_win) has its 64
+//           final sums o in its lanes, and c' = K - o.  The survivors, c' + (n - K) >= L - 1,
+//           are listed (a ballot, one returning atomic per group on the run's survivor word,
+//           no compaction launch, ids in any order) and their counts[] reset to 0; a dropped
+//           hypothesis keeps c'.  No maximum is folded: c' can exceed c* when K > c*
+//   rest    (kCountRest) the survivors over the whole window through that list with the exact
+//           loop, the survivor count read on the device as Hdev is; counts land at
+//           counts[surv[j]], completed groups fold their full counts' maxima into status[0],
+//           and the first thread folds pw[0] when K = npad, before the empty-plane return:
+//           status[0] is exactly c* before the tail
+// Every candidate survives (c' >= c_K, and its full count >= c* - 1 >= L - 1), so the tail sees
+// the counts it would have seen; a dropped hypothesis keeps c' < L - 1 - (n - K) <= c* - 1.
 // Shards and slices prune against their local L <= local c* <= global c*.
-// Measured (profiles/prune/ab.txt, one box, interleaved with the parent commit's library, G0 =
+// Measured, the screening prefix against the exact one (profiles/screen/ab.txt, one box,
+// interleaved with the parent commit's library; tools/screen_model.py is the CPU model): C2
+// kernel trace of the bench (two lanes share the machine; shortest launches in brackets): prefix
+// 44.7 us (29.8) against 72.7 us (48.4), 0.61 for 0.58 of the VALU cycles; rest 28.3 us (20.9)
+// against 27.5 us (20.4), sample unchanged at 12.7 us.  The run's count between its timing
+// events, five rounds: 68.6-71.7 us against 88.2-88.6 us (0.79); bench value 1.538-1.582e9
+// against 1.249-1.271e9 hypotheses/s (1.23 x, every round of one arm outside the other's
+// range).  C5: 2.40-2.41 ms per run against 3.79-3.90 ms (0.62).  A second session: count
+// 69.8-70.6 us against 87.0-88.3 us, value 1.544-1.576e9 against 1.264-1.282e9, C5 2.36-2.38 ms
+// against 3.84-3.85 ms, the same trace figures within 0.5 us.  Sweep at C2, bench value in
+// 1e9 hypotheses/s, two rounds each: m = 16 / 33 / 50 / 66 / 100 / 133 / 166 / 200 gave
+// 1.05-1.08 / 1.33-1.35 / 1.50-1.52 / 1.56-1.60 / 1.54-1.55 / 1.51-1.54 / 1.50-1.51 /
+// 1.49-1.50 (the model put the least VALU near n / 15, but a survivor's whole window runs the
+// slower exact loop in a launch that is mostly ramp and drain, and a short prefix is cheap now);
+// G0 = 8 / 16 / 32 / 48 / 64 gave 1.49 / 1.54 / 1.55-1.57 / 1.54-1.57 / 1.55.  The defaults
+// stay m = n / 30 and G0 = 32.
+// The exact prefix stage before it, against the single launch (profiles/prune/ab.txt, G0 =
 // 16 and m = n / 20): a float64 model of the rule on the CPU predicted 0.48 of the counting
 // work at C2 (K ~ 860, 8.5 % survivors) and 0.81 at C5.  C2, kernel trace of the bench (two
 // lanes, so each launch shares the machine; shortest launches in brackets): sample 12.6 us
@@ -313,16 +343,19 @@ __device__ __forceinline__ void group_done_max(int *counts, int *gdone, int *sta
 }
 
 // Stages of the pruned count (k_f8_count32q's MODE): the whole window, the prefix [0, K) of the
-// groups past the sample, the rest [K, npad) of the survivors.
+// groups past the sample (screened), the survivors over the whole window again.
 constexpr int kCountWhole = 0, kCountPrefix = 1, kCountRest = 2;
 
 // group_done_max of a windowed stage: gd counts the window's `target` points of the group, the
 // lane's final count is counts[hc] (valid lanes), and the group's max goes to cword.  The
-// prefix stage (rest >= 0: points past the window) also lists its survivors, the lanes whose
-// count + rest can still reach L - 1: one ballot and one returning atomic on the run's
-// survivor word per group, ids in any order.
+// screening prefix stage (rest >= 0: points past its window of target = K points) has the
+// lane's certified outliers there instead: c' = K - outliers bounds the prefix count from
+// above, the lanes with c' + rest >= L - 1 are the survivors (one ballot and one returning
+// atomic on the run's survivor word per group, ids in any order) and restart from 0 for the
+// rest stage's whole-window count, the others keep c'.  No maximum is folded then: c' is no
+// lower bound of any full count.
 template <int MODE>
-__device__ __forceinline__ void group_done_win(const int *counts, int *gd, int *cword, int len,
+__device__ __forceinline__ void group_done_win(int *counts, int *gd, int *cword, int len,
                                                int target, int hc, bool valid, int h, int rest,
                                                int L, int *nsurv, int *surv) {
   wait_vmem();
@@ -332,20 +365,25 @@ __device__ __forceinline__ void group_done_win(const int *counts, int *gd, int *
   last = __shfl(last, 0);
   if (!last) return;
   const int c = valid ? ld_agent(&counts[hc]) : 0;
+  if constexpr (MODE == kCountPrefix) {
+    if (rest >= 0) {
+      const int cu = target - c;
+      const bool keep = valid && cu + rest >= L - 1;
+      if (valid)
+        __hip_atomic_store(&counts[hc], keep ? 0 : cu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned long long bal = __ballot(keep);
+      if (bal == 0ull) return;
+      int base = 0;
+      if (lane == 0) base = atomicAdd(nsurv, __popcll(bal));
+      base = __shfl(base, 0);
+      if (keep) surv[base + __popcll(bal & ((1ull << lane) - 1ull))] = h;
+      return;
+    }
+  }
   int v = c;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
   if (lane == 0 && v > 0) atomicMax(cword, v);
-  if constexpr (MODE == kCountPrefix) {
-    if (rest < 0) return;  // K = npad: the prefix was the whole count
-    const bool keep = valid && c + rest >= L - 1;
-    const unsigned long long bal = __ballot(keep);
-    if (bal == 0ull) return;
-    int base = 0;
-    if (lane == 0) base = atomicAdd(nsurv, __popcll(bal));
-    base = __shfl(base, 0);
-    if (keep) surv[base + __popcll(bal & ((1ull << lane) - 1ull))] = h;
-  }
 }
 
 #ifndef RSAMD_COUNT_LDS
@@ -412,6 +450,34 @@ __device__ __forceinline__ void pair_terms(f2q P01, f2q P23, f2q P45, f2q P67, f
   RSD_PKMUL_VB(S, m, ALB, "[0,1]", "[1,1]");  // beta m
 }
 
+// The screening terms of one point pair (prefix stage): Q = fma(e, e, -ko) and S = beta n1, with
+// a, b, l3, e and n1 by the operations and in the order of pair_terms, so they are the same
+// bits.  12 packed ops, one asm block for the reason given there; t0 = F1 y2 + F2 -> a -> S,
+// t1 = F4 y2 + F5 -> b -> b^2 -> n1, t2 = F7 y2 + F8 -> l3 -> b y1 + l3 -> e -> Q.
+__device__ __forceinline__ void screen_terms(f2q P01, f2q P23, f2q P45, f2q P67, f2q P8, f2q KIO,
+                                             f2q ALB, f2q X2, f2q Y2, f2q X1, f2q Y1, f2q &Q,
+                                             f2q &S) {
+#pragma clang fp contract(off)
+  f2q t0, t1, t2;
+  asm("v_pk_fma_f32 %[t0], %[P01], %[Y2], %[P23] op_sel:[1,0,0] op_sel_hi:[1,1,0]\n\t"
+      "v_pk_fma_f32 %[t1], %[P45], %[Y2], %[P45] op_sel:[0,0,1] op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %[t2], %[P67], %[Y2], %[P8] op_sel:[1,0,0] op_sel_hi:[1,1,0]\n\t"
+      "v_pk_fma_f32 %[t1], %[P23], %[X2], %[t1] op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"  // b
+      "v_pk_fma_f32 %[t2], %[P67], %[X2], %[t2] op_sel:[0,0,0] op_sel_hi:[0,1,1]\n\t"  // l3
+      "v_pk_fma_f32 %[t0], %[P01], %[X2], %[t0] op_sel:[0,0,0] op_sel_hi:[0,1,1]\n\t"  // a
+      "v_pk_fma_f32 %[t2], %[t1], %[Y1], %[t2]\n\t"                                      // b y1 + l3
+      "v_pk_mul_f32 %[t1], %[t1], %[t1]\n\t"                                             // b^2
+      "v_pk_fma_f32 %[t2], %[t0], %[X1], %[t2]\n\t"                                      // e
+      "v_pk_fma_f32 %[t1], %[t0], %[t0], %[t1]\n\t"                                      // n1
+      "v_pk_fma_f32 %[t2], %[t2], %[t2], %[KIO] op_sel:[0,0,1] op_sel_hi:[1,1,1]\n\t"  // Q
+      "v_pk_mul_f32 %[t0], %[t1], %[ALB] op_sel:[0,1] op_sel_hi:[1,1]"                   // S
+      : [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2)
+      : [P01] "v"(P01), [P23] "v"(P23), [P45] "v"(P45), [P67] "v"(P67), [P8] "v"(P8),
+        [KIO] "v"(KIO), [ALB] "v"(ALB), [X2] "s"(X2), [Y2] "s"(Y2), [X1] "s"(X1), [Y1] "s"(Y1));
+  Q = t2;
+  S = t0;
+}
+
 // Wave timeline of the counting kernel (start / end of each wave, 100 MHz real-time counter):
 // set by the plan only under RSAMD_TSTAMP, for the launch-shape analysis.
 __device__ uint64_t *g_count_ts = nullptr;
@@ -440,9 +506,10 @@ __global__ __launch_bounds__(BT) void k_f8_count32q(const float4 *__restrict__ p
   const int bslot = xc * xq + min(xc, xr) + (bx >> 3);
   const int64_t w = wave_uniform(bslot * (BT / 64) + (threadIdx.x >> 6));
   const int npad = (n + 7) / 8 * 8;
-  // the stage's point window (win points: [0, K) or [K, npad)) and first hypothesis hoff: the
-  // pointers are moved there once, so the slice loop below is the same in every stage with win
-  // for npad; rest / Lq: the prefix stage's points past the window (-1: none skipped) and L
+  // the stage's point window (win points: [0, K) in the prefix stage, else all) and first
+  // hypothesis hoff: the pointers are moved there once, so the slice loop below is the same in
+  // every stage with win for npad; rest / Lq: the prefix stage's points past the window (-1:
+  // none skipped, the exact count; else the screening loop) and L
   int win = npad, hoff = 0, rest = -1, Lq = 0;
   if constexpr (MODE == kCountPrefix) {
     // K from L = status[0], the sample stage's best full count, which no wave of this launch
@@ -468,19 +535,16 @@ __global__ __launch_bounds__(BT) void k_f8_count32q(const float4 *__restrict__ p
     per_wave = ((tot + Wd - 1) / Wd + 7) / 8 * 8;
   }
   if constexpr (MODE == kCountRest) {
-    // c*: the prefix stage's maximum (a prefix count never exceeds the full count; the true
-    // maximum of its groups when K = npad) joins the sample's before the empty-plane return
+    // c*: when nothing was skipped (K = npad) the prefix stage's counts are final and their
+    // maximum joins the sample's before the empty-plane return; a screening prefix stage
+    // leaves no maximum, the survivors' full counts below bring theirs
     if (bx == 0 && threadIdx.x == 0) {
       const int ca = pa.pw[0];
-      if (ca > 0) atomicMax(&status[0], ca);
+      if (pa.pw[2] == npad && ca > 0) atomicMax(&status[0], ca);
     }
-    const int K = pa.pw[2];
-    H = min(H, pa.pw[1]);  // the survivors
-    win = npad - K;
+    H = min(H, pa.pw[1]);  // the survivors, counted over the whole window
     const int64_t tot = static_cast<int64_t>((H + 63) >> 6) * win;
     if (tot == 0) return;  // uniform over the grid, before any barrier
-    ptsq += K;
-    pts += K;
     gdone = pa.gdone_b;
     const int64_t Wd = max<int64_t>(1, min<int64_t>(static_cast<int64_t>(nb) * (BT / 64), tot / 64));
     per_wave = ((tot + Wd - 1) / Wd + 7) / 8 * 8;
@@ -535,40 +599,60 @@ __global__ __launch_bounds__(BT) void k_f8_count32q(const float4 *__restrict__ p
     const float4 q = G4[hl];
     const f2 KIO = {q.x, q.y}, ALB = {q.z, q.w};
     int cnt = 0;
-    for (int i = p0; i < p1; i += 8) {
-      float4 blk[8];  // (x2[8], y2[8], x1[8], y1[8]) of points i..i+7
+    if (MODE == kCountPrefix && rest >= 0) {
+      // screening (grid-uniform branch): cnt = the certified outliers of [p0, p1), Q > S so
+      // that NaN certifies nothing; no re-test, and [0, K) holds no padding point
+      for (int i = p0; i < p1; i += 8) {
+        float4 blk[8];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) blk[k] = ptsq[i + k];
-      const float *v = reinterpret_cast<const float *>(blk);
+        for (int k = 0; k < 8; ++k) blk[k] = ptsq[i + k];
+        const float *v = reinterpret_cast<const float *>(blk);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const f2 X2 = {v[2 * j], v[2 * j + 1]}, Y2 = {v[8 + 2 * j], v[9 + 2 * j]};
-        const f2 X1 = {v[16 + 2 * j], v[17 + 2 * j]}, Y1 = {v[24 + 2 * j], v[25 + 2 * j]};
-        f2 P, Q, R, S;
-        pair_terms(P01, P23, P45, P67, P8, KIO, ALB, X2, Y2, X1, Y1, P, Q, R, S);
-        const unsigned long long i0 = __ballot(P.x < R.x), i1 = __ballot(P.y < R.y);
-        const unsigned long long l0 = __ballot(Q.x <= S.x), l1 = __ballot(Q.y <= S.y);
-        cnt = add_lane_bit(cnt, i0);  // sure inliers
-        cnt = add_lane_bit(cnt, i1);
-        const unsigned long long a0 = i0 ^ l0, a1 = i1 ^ l1;
-        if ((a0 | a1) != 0ull) {  // rare: float64 re-test of the ambiguous lanes
-          ++n_retest;
-          // the opaque pointer keeps these loads (and their 18 VGPRs) inside the rare branch
-          const double *fp = Fsoa + hl;
-          asm volatile("" : "+v"(fp));
+        for (int j = 0; j < 4; ++j) {
+          const f2 X2 = {v[2 * j], v[2 * j + 1]}, Y2 = {v[8 + 2 * j], v[9 + 2 * j]};
+          const f2 X1 = {v[16 + 2 * j], v[17 + 2 * j]}, Y1 = {v[24 + 2 * j], v[25 + 2 * j]};
+          f2 Q, S;
+          screen_terms(P01, P23, P45, P67, P8, KIO, ALB, X2, Y2, X1, Y1, Q, S);
+          cnt = add_lane_bit(cnt, __ballot(Q.x > S.x));
+          cnt = add_lane_bit(cnt, __ballot(Q.y > S.y));
+        }
+      }
+    } else {
+      for (int i = p0; i < p1; i += 8) {
+        float4 blk[8];  // (x2[8], y2[8], x1[8], y1[8]) of points i..i+7
+#pragma unroll
+        for (int k = 0; k < 8; ++k) blk[k] = ptsq[i + k];
+        const float *v = reinterpret_cast<const float *>(blk);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const f2 X2 = {v[2 * j], v[2 * j + 1]}, Y2 = {v[8 + 2 * j], v[9 + 2 * j]};
+          const f2 X1 = {v[16 + 2 * j], v[17 + 2 * j]}, Y1 = {v[24 + 2 * j], v[25 + 2 * j]};
+          f2 P, Q, R, S;
+          pair_terms(P01, P23, P45, P67, P8, KIO, ALB, X2, Y2, X1, Y1, P, Q, R, S);
+          const unsigned long long i0 = __ballot(P.x < R.x), i1 = __ballot(P.y < R.y);
+          const unsigned long long l0 = __ballot(Q.x <= S.x), l1 = __ballot(Q.y <= S.y);
+          cnt = add_lane_bit(cnt, i0);  // sure inliers
+          cnt = add_lane_bit(cnt, i1);
+          const unsigned long long a0 = i0 ^ l0, a1 = i1 ^ l1;
+          if ((a0 | a1) != 0ull) {  // rare: float64 re-test of the ambiguous lanes
+            ++n_retest;
+            // the opaque pointer keeps these loads (and their 18 VGPRs) inside the rare branch
+            const double *fp = Fsoa + hl;
+            asm volatile("" : "+v"(fp));
 #if RSAMD_RETEST_LANES
-          // only the ambiguous lanes fetch their float64 model (a 128-B line of each row holds
-          // 16 hypotheses: a re-test touches the lines of its lanes, not all 36 of the group)
-          if (((a0 | a1) >> lane) & 1ull) {
+            // only the ambiguous lanes fetch their float64 model (a 128-B line of each row holds
+            // 16 hypotheses: a re-test touches the lines of its lanes, not all 36 of the group)
+            if (((a0 | a1) >> lane) & 1ull) {
 #endif
-          double fdd[9];
+            double fdd[9];
 #pragma unroll
-          for (int k = 0; k < 9; ++k) fdd[k] = fp[k * ld];
-          if ((a0 >> lane) & 1ull) cnt += test64(fdd, pts[i + 2 * j], g.thr2_px) ? 1 : 0;
-          if ((a1 >> lane) & 1ull) cnt += test64(fdd, pts[i + 2 * j + 1], g.thr2_px) ? 1 : 0;
+            for (int k = 0; k < 9; ++k) fdd[k] = fp[k * ld];
+            if ((a0 >> lane) & 1ull) cnt += test64(fdd, pts[i + 2 * j], g.thr2_px) ? 1 : 0;
+            if ((a1 >> lane) & 1ull) cnt += test64(fdd, pts[i + 2 * j + 1], g.thr2_px) ? 1 : 0;
 #if RSAMD_RETEST_LANES
+            }
+#endif
           }
-#endif
         }
       }
     }

@@ -93,7 +93,7 @@ struct RunBufs {
 constexpr int kOverlapDefault = 1;
 // rs_f8_plan::prune and the sample size unless RSAMD_PRUNE / RSAMD_PRUNE_SAMPLE are set; the
 // margin and the least number of skipped points worth pruning for come from n
-// (profiles/prune/ab.txt)
+// (profiles/prune/ab.txt; swept again for the screening prefix stage, profiles/screen/ab.txt)
 constexpr int kPruneDefault = 1;
 constexpr int kPruneSampleDefault = 32;
 constexpr int kPruneMarginDiv = 30;   // m = max(16, n / 30)
@@ -158,7 +158,7 @@ struct rs_f8_plan {
   int q_slices = 0;           // slices per resident wave (RSAMD_QSLICES; 0: count32q_shape)
   int tail_cus = 256;         // CUs shared by the tail + solve launch
   // Pruned count (fp32 path; derivation above k_f8_count32q): a full count of the first
-  // prune_sample groups, the prefix [0, K) of the others, the rest of the survivors.
+  // prune_sample groups, the others screened over the prefix [0, K), a full count of the survivors.
   // RSAMD_PRUNE=0: the single whole-window launch.  Margin / min-skip below 0: from n
   // (prune_params)
   int prune = kPruneDefault;                // RSAMD_PRUNE
@@ -612,8 +612,8 @@ static int plan_run(rs_f8_plan *p, int64_t H, int32_t mode, uint64_t seed, uint6
   if (tl >= 1) HIP_TRY(hipEventRecord(ev[0], ms));
   if (staged) {
     // sample (whole window, c* of its groups = L in status[0]) -> prefix [0, K) of the other
-    // groups, K from L on the device, survivors listed -> rest [K, npad) of the survivors;
-    // all three in stream order on this lane, no host decision
+    // groups screened, K from L on the device, survivors listed -> the survivors over the whole
+    // window; all three in stream order on this lane, no host decision
     const rsd::GuardW gw{thresh * thresh};
     const rsd::Count32qShape sh0 = rsd::count32q_shape(n, h0, p->q_waves, p->q_slices);
     HIP_TRY(rsd::launch_f8_count32q(p->d_pts32q, p->d_pts, n, h0, b.d_F32, b.d_F, p->ld, sh0, gw,
@@ -845,7 +845,7 @@ extern "C" int rs_f8_plan_counts(rs_f8_plan *p, int32_t *counts, int64_t H) {
   if (b.staged) HIP_TRY(hipMemcpy(pw, b.d_pw, sizeof(pw), hipMemcpyDeviceToHost));
   const int n = static_cast<int>(p->n);
   if (b.staged && pw[2] < (n + 7) / 8 * 8) {
-    // a pruned run leaves prefix counts for the hypotheses it dropped: the full counts come
+    // a pruned run leaves prefix upper bounds for the hypotheses it dropped: the full counts come
     // from the whole-window kernel over the run's models, still in the buffer set (a
     // diagnostic accessor; nothing else is in flight after plan_wait)
     HIP_TRY(hipSetDevice(p->ctx->device));
@@ -861,6 +861,15 @@ extern "C" int rs_f8_plan_counts(rs_f8_plan *p, int32_t *counts, int64_t H) {
     src = p->d_full;
   }
   HIP_TRY(hipMemcpy(counts, src, sizeof(int) * H, hipMemcpyDeviceToHost));
+  return RS_OK;
+}
+
+extern "C" int rs_f8_plan_stage_counts(rs_f8_plan *p, int32_t *counts, int64_t H) {
+  if (!p || !counts) return fail(RS_EINVAL, "null pointer");
+  int st = plan_wait(p);
+  if (st) return st;
+  if (H > p->last_H) return fail(RS_EINVAL, "H exceeds the last run");
+  HIP_TRY(hipMemcpy(counts, p->last().d_counts, sizeof(int) * H, hipMemcpyDeviceToHost));
   return RS_OK;
 }
 

@@ -132,6 +132,7 @@ _SIGS = {
     "rs_f8_plan_set_timing": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "rs_f8_plan_lane_waits": (C.c_int, [C.c_void_p, _i64p]),
     "rs_f8_plan_prune_stats": (C.c_int, [C.c_void_p, _i64p]),
+    "rs_f8_plan_stage_counts": (C.c_int, [C.c_void_p, _i32p, C.c_int64]),
     "rs_f8_plan_set_count_precision": (C.c_int, [C.c_void_p, C.c_int32]),
     "rs_f8_ransac_np": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64, _u32p, _i32p,
                                   C.c_double, C.POINTER(F8Result), _i64p, C.c_int64, _i64p]),
@@ -649,6 +650,13 @@ class F8Plan:
     def counts(self, H):
         out = np.empty(int(H), dtype=np.int32)
         check(lib().rs_f8_plan_counts(self._h, ptr(out, C.c_int32), int(H)))
+        return out
+
+    def stage_counts(self, H):
+        """The counting stages' own counts of the last run, no recount: after a pruned run a
+        dropped hypothesis holds K minus its certified outliers among the first K points."""
+        out = np.empty(int(H), dtype=np.int32)
+        check(lib().rs_f8_plan_stage_counts(self._h, ptr(out, C.c_int32), int(H)))
         return out
 
     def models(self, H):
