@@ -587,7 +587,40 @@ int rs_bundle_adjust_rigid(rs_ctx *ctx, double *cams, int64_t nC, double *pts, i
                            const int32_t *obs_view, const int32_t *obs_point, const double *uv,
                            int64_t n, int32_t max_iter, double ftol, rs_ba_info *info);
 
-/* HIP events between the kernels of the next rs_bundle_adjust / rs_bundle_adjust_rigid calls
+/* Bundle adjustment under a robust loss (scipy.optimize.least_squares' loss= / f_scale=, which
+ * the reference's BundleAdjustment2 could pass and the two calls above lack).  rigid == 0: the
+ * cameras of rs_bundle_adjust, rigid != 0: those of rs_bundle_adjust_rigid with its rotation
+ * check.  Per observation i with the residual (ru, rv) of rs_ba_residuals, s_i = ru^2 + rv^2,
+ * z_i = s_i / C^2, C = f_scale:
+ *   cost = 0.5 C^2 sum_i rho(z_i),
+ *   loss 0 linear   rho = z                                  w = rho' = 1
+ *        1 soft_l1  rho = 2 (sqrt(1 + z) - 1)                w = 1 / sqrt(1 + z)
+ *        2 huber    rho = z (z <= 1), 2 sqrt(z) - 1 (z > 1)  w = 1 (z <= 1), 1 / sqrt(z)
+ *        3 cauchy   rho = log1p(z)                           w = 1 / (1 + z)
+ * scipy's names and forms; unlike scipy, rho acts on the squared norm of the observation's
+ * residual, not on ru and rv separately.  The iteration is the LM of rs_bundle_adjust, rule for
+ * rule, on the re-weighted problem (IRLS; Triggs' first-order form, no rho'' term): at every
+ * linearisation w_i is taken from the residuals of the accepted state, r, Jc and Jp of
+ * observation i are scaled by sqrt(w_i), and U, V, W, the gradients, the Schur complement, the
+ * Cholesky and the predicted reduction are formed from the scaled quantities.  The weights stay
+ * fixed over the rejected trials of one linearisation; a trial's cost is the robust cost of the
+ * trial state.  info->cost_init and info->cost are robust costs.  weights (n), which may be
+ * NULL, gets w_i at the returned state (all 1.0 for loss 0).  loss 0 is rs_bundle_adjust /
+ * rs_bundle_adjust_rigid bit for bit, whatever f_scale.  Determinism, limits and the unobserved
+ * cameras and points as rs_bundle_adjust.  RS_EINVAL as the two calls above, and for loss
+ * outside 0..3 or f_scale not finite or <= 0.  rs_ba_timing covers this call: the weights of
+ * the linearisation count in the k_ba_linearize slot, the final weights in the last slot. */
+#define RS_BA_LOSS_LINEAR 0
+#define RS_BA_LOSS_SOFT_L1 1
+#define RS_BA_LOSS_HUBER 2
+#define RS_BA_LOSS_CAUCHY 3
+int rs_bundle_adjust_robust(rs_ctx *ctx, double *cams, int64_t nC, double *pts, int64_t nP,
+                            const int32_t *obs_view, const int32_t *obs_point, const double *uv,
+                            int64_t n, int32_t max_iter, double ftol, int32_t rigid, int32_t loss,
+                            double f_scale, double *weights, rs_ba_info *info);
+
+/* HIP events between the kernels of the next rs_bundle_adjust / rs_bundle_adjust_rigid /
+ * rs_bundle_adjust_robust calls
  * (enable != 0; the rigid call's linearisation counts in the k_ba_linearize slot).  Returns the
  * last timed call's device ms summed per kernel -- k_ba_linearize, k_ba_camera, k_ba_pointsum,
  * k_ba_point, k_ba_schur, k_ba_chol, k_ba_step, k_ba_cost + k_ba_final -- and its trials. */

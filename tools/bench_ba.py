@@ -13,6 +13,11 @@ table instead, the start turned into rotations by tests/ba_rigid_fixture.rigid_s
 profiles/ba_rigid_bench.json.  The two problems take different LM paths: compare the time per
 trial as well as per call.
 
+`--loss NAME --f-scale X` (soft_l1, huber, cauchy) times the same table under a robust loss
+(rs_bundle_adjust_robust) against tests/ba_robust_ref.py and writes
+profiles/ba_robust_bench.json; with `--rigid` the rigid model.  The weights of each linearisation
+are formed inside k_ba_linearize's slot, the final weights count in the last slot.
+
 GPU figures: the wall time of whole calls (host clock around the synchronous call: upload, host
 CSR build, LM loop, download), and, from a separate call with rs_ba_timing on, the device time
 per kernel summed over the call (HIP events between the kernels).  Needs a GPU; there is no
@@ -69,11 +74,16 @@ def main():
     ap.add_argument("--no-oracle", action="store_true", help="skip the CPU oracle run")
     ap.add_argument("--rigid", action="store_true",
                     help="time bundle_adjust_rigid from a rigid start")
+    ap.add_argument("--loss", default="linear", choices=("linear", "soft_l1", "huber", "cauchy"))
+    ap.add_argument("--f-scale", type=float, default=3e-4, help="C of a robust --loss")
     ap.add_argument("--out", default=None,
-                    help="default profiles/ba_bench.json, profiles/ba_rigid_bench.json with --rigid")
+                    help="default profiles/ba_bench.json, profiles/ba_rigid_bench.json with "
+                         "--rigid, profiles/ba_robust_bench.json with a robust --loss")
     a = ap.parse_args()
+    robust = a.loss != "linear"
     if a.out is None:
-        a.out = os.path.join(REPO, "profiles", "ba_rigid_bench.json" if a.rigid else "ba_bench.json")
+        a.out = os.path.join(REPO, "profiles", "ba_robust_bench.json" if robust else
+                             "ba_rigid_bench.json" if a.rigid else "ba_bench.json")
 
     from tsbb15_amd import _ffi
     from tsbb15_amd import tables as gt
@@ -81,11 +91,20 @@ def main():
         raise SystemExit("bench_ba: no GPU visible")
     ctx = _ffi.default_context()
     cams0, pts0, ov, op, uv = dino_problem(noise=a.noise, sigma=a.sigma, rigid=a.rigid)
-    adjust = gt.bundle_adjust_rigid if a.rigid else gt.bundle_adjust
+    entry = gt.bundle_adjust_rigid if a.rigid else gt.bundle_adjust
+    if robust:
+        def adjust(*args, **kw):
+            c, p, info = entry(*args, loss=a.loss, f_scale=a.f_scale, **kw)
+            info["weights_min"] = float(info.pop("weights").min())
+            return c, p, info
+    else:
+        adjust = entry
     res = {"problem": {"cameras": len(cams0), "points": len(pts0), "observations": len(ov),
                        "reduced_system": (6 if a.rigid else 12) * (len(cams0) - 1),
                        "noise": a.noise, "sigma": a.sigma, "max_iter": a.max_iter,
-                       "entry": adjust.__name__}}
+                       "entry": entry.__name__}}
+    if robust:
+        res["problem"].update(loss=a.loss, f_scale=a.f_scale)
     print(f"bench_ba: {res['problem']}", flush=True)
 
     adjust(cams0, pts0, ov, op, uv, max_iter=a.max_iter, ctx=ctx)      # warm-up
@@ -112,7 +131,15 @@ def main():
     print(f"bench_ba: gpu {res['gpu']}", flush=True)
 
     if not a.no_oracle:
-        if a.rigid:
+        if robust:
+            import ba_robust_ref as br
+
+            def lm(*args, **kw):
+                c, p, info = br.bundle_adjust_robust_lm(*args, loss=a.loss, f_scale=a.f_scale,
+                                                        rigid=a.rigid, **kw)
+                info["weights_min"] = float(info.pop("weights").min())
+                return c, p, info
+        elif a.rigid:
             import ba_rigid_ref as tr
             lm = tr.bundle_adjust_rigid_lm
         else:

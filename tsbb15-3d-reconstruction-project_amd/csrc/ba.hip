@@ -33,6 +33,13 @@
 // (3 generators a, b, 1/z per observation), runs k_ba_camera and k_ba_schur in one wave per
 // block (36 + 6 workers), pads the reduced system to whole 12-wide block columns with an
 // identity diagonal and a zero right-hand side, and retracts in k_ba_step.
+//
+// Robust losses (rs_bundle_adjust_robust).  The same loop on the re-weighted problem: with
+// w_i = rho'(z_i) at the accepted state, k_ba_linearize<true> / k_ba_linearize_rigid<true> scale
+// r, Jp, W (and, D = 12, the generators of Jc) by sqrt(w_i), k_ba_camera<6, true> scales the
+// rigid Jc while staging it, k_ba_cost<true> writes C^2 rho(z_i), and k_ba_weights writes the
+// final w_i.  Everything from k_ba_pointsum to k_ba_final is shared with the linear path, whose
+// <false> instantiations are the code it had.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -146,11 +153,30 @@ __device__ __forceinline__ bool ba_inv3(const double *V, double lam, double *Vi)
   return ok;
 }
 
+// Robust losses (rs_bundle_adjust_robust; scipy's names and forms) of z = (ru^2 + rv^2) / C^2:
+// 1 soft_l1, 2 huber, 3 cauchy.  `loss` is uniform over a launch.  A NaN z gives NaN.
+__device__ __forceinline__ double ba_rho(int loss, double z) {
+  if (loss == 1) return 2.0 * z / (sqrt(1.0 + z) + 1.0);
+  if (loss == 2) return z <= 1.0 ? z : 2.0 * sqrt(z) - 1.0;
+  return log1p(z);
+}
+
+// w = rho'(z)
+__device__ __forceinline__ double ba_weight(int loss, double z) {
+  if (loss == 1) return 1.0 / sqrt(1.0 + z);
+  if (loss == 2) return z <= 1.0 ? 1.0 : 1.0 / sqrt(z);
+  return 1.0 / (1.0 + z);
+}
+
+// ROB: the re-weighted problem of one IRLS round.  sq = sqrt(w) of the observation's residual at
+// this state scales r, Jp and the 4 generators xh / w (Jc is linear in them), so W comes out as
+// w Jc^T Jp and every kernel downstream runs unchanged.  ic2 = 1 / C^2.
+template <bool ROB>
 __global__ __launch_bounds__(256) void k_ba_linearize(
     const double *__restrict__ cams, const double *__restrict__ pts,
     const int32_t *__restrict__ ov, const int32_t *__restrict__ op,
     const double *__restrict__ uv, int n, double *__restrict__ r, double *__restrict__ jcs,
-    double *__restrict__ Jp, double *__restrict__ W) {
+    double *__restrict__ Jp, double *__restrict__ W, int loss, double ic2) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const double *c = cams + 12 * ov[i];
@@ -161,15 +187,29 @@ __global__ __launch_bounds__(256) void k_ba_linearize(
   const double w = c[8] * xh[0] + c[9] * xh[1] + c[10] * xh[2] + c[11];
   const double iw = 1.0 / w, iw2 = iw * iw;
   const double aw = a / w, bw = b / w;
-  r[2 * i] = uv[2 * i] - aw;
-  r[2 * i + 1] = uv[2 * i + 1] - bw;
+  double r0 = uv[2 * i] - aw, r1 = uv[2 * i + 1] - bw;
+  double sq = 1.0;
+  if constexpr (ROB) {
+    sq = sqrt(ba_weight(loss, (r0 * r0 + r1 * r1) * ic2));
+    r0 *= sq;
+    r1 *= sq;
+  }
+  r[2 * i] = r0;
+  r[2 * i + 1] = r1;
   double g[4], j0[3], j1[3];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) g[k] = xh[k] / w;
+  for (int k = 0; k < 4; ++k) {
+    g[k] = xh[k] / w;
+    if constexpr (ROB) g[k] *= sq;
+  }
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     j0[k] = -(c[k] * w - a * c[8 + k]) * iw2;
     j1[k] = -(c[4 + k] * w - b * c[8 + k]) * iw2;
+    if constexpr (ROB) {
+      j0[k] *= sq;
+      j1[k] *= sq;
+    }
   }
   double *j6 = jcs + 6 * static_cast<int64_t>(i);
 #pragma unroll
@@ -196,11 +236,15 @@ __global__ __launch_bounds__(256) void k_ba_linearize(
 
 // Rigid cameras: r, the 3 generators (a, b, iz), Jp = -Pi R (the arithmetic of k_ba_linearize:
 // with nC == 1 both paths give the same bits) and W = Jc^T Jp (6 x 3).
+// ROB: r, Jp and W are scaled as in k_ba_linearize.  Jc is not linear in (a, b, iz), so the
+// generators stay as they are and sq goes to sw[i] for k_ba_camera<6, true>.
+template <bool ROB>
 __global__ __launch_bounds__(256) void k_ba_linearize_rigid(
     const double *__restrict__ cams, const double *__restrict__ pts,
     const int32_t *__restrict__ ov, const int32_t *__restrict__ op,
     const double *__restrict__ uv, int n, double *__restrict__ r, double *__restrict__ jcs,
-    double *__restrict__ Jp, double *__restrict__ W) {
+    double *__restrict__ Jp, double *__restrict__ W, int loss, double ic2,
+    double *__restrict__ sw) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const double *c = cams + 12 * ov[i];
@@ -211,13 +255,25 @@ __global__ __launch_bounds__(256) void k_ba_linearize_rigid(
   const double w = c[8] * xh[0] + c[9] * xh[1] + c[10] * xh[2] + c[11];
   const double iw = 1.0 / w, iw2 = iw * iw;
   const double aw = a / w, bw = b / w;
-  r[2 * i] = uv[2 * i] - aw;
-  r[2 * i + 1] = uv[2 * i + 1] - bw;
+  double r0 = uv[2 * i] - aw, r1 = uv[2 * i + 1] - bw;
+  double sq = 1.0;
+  if constexpr (ROB) {
+    sq = sqrt(ba_weight(loss, (r0 * r0 + r1 * r1) * ic2));
+    r0 *= sq;
+    r1 *= sq;
+    sw[i] = sq;
+  }
+  r[2 * i] = r0;
+  r[2 * i + 1] = r1;
   double j0[3], j1[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     j0[k] = -(c[k] * w - a * c[8 + k]) * iw2;
     j1[k] = -(c[4 + k] * w - b * c[8 + k]) * iw2;
+    if constexpr (ROB) {
+      j0[k] *= sq;
+      j1[k] *= sq;
+    }
   }
   double *j3 = jcs + 3 * static_cast<int64_t>(i);
   j3[0] = aw;
@@ -233,7 +289,11 @@ __global__ __launch_bounds__(256) void k_ba_linearize_rigid(
   double *wi = W + 18 * static_cast<int64_t>(i);
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
-    const double c0 = ba_jc6(g, k), c1 = ba_jc6(g, 6 + k);
+    double c0 = ba_jc6(g, k), c1 = ba_jc6(g, 6 + k);
+    if constexpr (ROB) {
+      c0 *= sq;
+      c1 *= sq;
+    }
 #pragma unroll
     for (int q = 0; q < 3; ++q) wi[3 * k + q] = c0 * j0[q] + c1 * j1[q];
   }
@@ -243,11 +303,15 @@ __global__ __launch_bounds__(256) void k_ba_linearize_rigid(
 // row is staged through LDS in tiles (generators and residual of each observation, gathered
 // by all threads); every thread then walks the tile in order for its own entry.  D = 6 stages
 // the 2 x 6 Jc itself (each entry formed once from the 3 generators) and runs in one wave.
-template <int D>
+// ROB (D = 6 only; the D = 12 generators arrive scaled): every staged Jc entry of observation i
+// is multiplied by sw[i] = sqrt(w_i).
+template <int D, bool ROB>
 __global__ __launch_bounds__(ba_block_threads(D)) void k_ba_camera(
     const int32_t *__restrict__ cam_of_slot, const int32_t *__restrict__ cam_off,
     const int32_t *__restrict__ cam_obs, const double *__restrict__ jcs,
-    const double *__restrict__ r, double *__restrict__ U, double *__restrict__ gc) {
+    const double *__restrict__ r, double *__restrict__ U, double *__restrict__ gc,
+    const double *__restrict__ sw) {
+  static_assert(!ROB || D == 6, "the 12-parameter generators are scaled by k_ba_linearize");
   constexpr int DD = D * D, NT = ba_block_threads(D), F = D == 12 ? 8 : 14;
   __shared__ double sj[kBaCamTile * F];
   const int slot = blockIdx.x, tid = threadIdx.x;
@@ -263,6 +327,8 @@ __global__ __launch_bounds__(ba_block_threads(D)) void k_ba_camera(
       const int f = idx % F;
       if constexpr (D == 12)
         sj[idx] = f < 6 ? jcs[6 * i + f] : r[2 * i + f - 6];
+      else if constexpr (ROB)
+        sj[idx] = f < 12 ? ba_jc6(jcs + 3 * i, f) * sw[i] : r[2 * i + f - 12];
       else
         sj[idx] = f < 12 ? ba_jc6(jcs + 3 * i, f) : r[2 * i + f - 12];
     }
@@ -661,12 +727,12 @@ __global__ __launch_bounds__(256) void k_ba_step(
   ppred[p] = s;
 }
 
-__global__ __launch_bounds__(256) void k_ba_cost(
-    const double *__restrict__ cams, const double *__restrict__ pts,
-    const int32_t *__restrict__ ov, const int32_t *__restrict__ op,
-    const double *__restrict__ uv, int n, double *__restrict__ e) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+// ru^2 + rv^2 of observation i.
+__device__ __forceinline__ double ba_sqres(const double *__restrict__ cams,
+                                           const double *__restrict__ pts,
+                                           const int32_t *__restrict__ ov,
+                                           const int32_t *__restrict__ op,
+                                           const double *__restrict__ uv, int i) {
   const double *c = cams + 12 * ov[i];
   const double *p = pts + 3 * static_cast<int64_t>(op[i]);
   const double x0 = p[0], x1 = p[1], x2 = p[2];
@@ -674,7 +740,34 @@ __global__ __launch_bounds__(256) void k_ba_cost(
   const double b = c[4] * x0 + c[5] * x1 + c[6] * x2 + c[7];
   const double w = c[8] * x0 + c[9] * x1 + c[10] * x2 + c[11];
   const double ru = uv[2 * i] - a / w, rv = uv[2 * i + 1] - b / w;
-  e[i] = ru * ru + rv * rv;
+  return ru * ru + rv * rv;
+}
+
+// e_i = s_i, the squared residual; ROB: C^2 rho(s_i / C^2), so that k_ba_final's 0.5 sum e is
+// the robust cost.
+template <bool ROB>
+__global__ __launch_bounds__(256) void k_ba_cost(
+    const double *__restrict__ cams, const double *__restrict__ pts,
+    const int32_t *__restrict__ ov, const int32_t *__restrict__ op,
+    const double *__restrict__ uv, int n, double *__restrict__ e, int loss, double c2,
+    double ic2) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double s = ba_sqres(cams, pts, ov, op, uv, i);
+  if constexpr (ROB)
+    e[i] = c2 * ba_rho(loss, s * ic2);
+  else
+    e[i] = s;
+}
+
+// The weights w_i = rho'(s_i / C^2) at the returned state.
+__global__ __launch_bounds__(256) void k_ba_weights(
+    const double *__restrict__ cams, const double *__restrict__ pts,
+    const int32_t *__restrict__ ov, const int32_t *__restrict__ op,
+    const double *__restrict__ uv, int n, double *__restrict__ wout, int loss, double ic2) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  wout[i] = ba_weight(loss, ba_sqres(cams, pts, ov, op, uv, i) * ic2);
 }
 
 // Sum over the workgroup in a fixed order: each thread's strided partial, then a binary tree.
@@ -804,11 +897,14 @@ bool ba_is_rotation(const double *c) {
   return det > 0.0;
 }
 
-// The LM loop of both entry points; D = 12: cameras as 12 free entries, D = 6: rigid.
-template <int D>
+// The LM loop of all entry points; D = 12: cameras as 12 free entries, D = 6: rigid.  ROB: the
+// robust loss `loss` (1..3) at scale f_scale, every linearisation re-weighted from the residuals
+// of the accepted state (the linear instantiation launches what it launched before the robust
+// loss existed).  weights (n) may be NULL; it gets w_i at the returned state, ones without ROB.
+template <int D, bool ROB>
 int ba_run(rs_ctx *c, double *cams, int64_t nC, double *pts, int64_t nP, const int32_t *obs_view,
            const int32_t *obs_point, const double *uv, int64_t n, int32_t max_iter, double ftol,
-           rs_ba_info *info) {
+           int32_t loss, double f_scale, double *weights, rs_ba_info *info) {
   constexpr int BW = D == 12 ? 12 : RS_BA_RIGID_BW, DD = D * D, D3 = 3 * D, NG = D / 2;
   constexpr int NT = rsd::ba_block_threads(D);
   static_assert(BW == 12 || BW == 6, "block-column width");
@@ -908,7 +1004,8 @@ int ba_run(rs_ctx *c, double *cams, int64_t nC, double *pts, int64_t nP, const i
       F8 * 2 * n, F8 * NG * n, F8 * 6 * n, F8 * D3 * n, F8 * D3 * n,   // 15-19 r, jcs, Jp, W, Y
       F8 * DD * nC, F8 * D * nC, F8 * D * nC,                         // 20-22 U, gc, dc
       F8 * 6 * pp, F8 * 6 * pp, F8 * 3 * pp, F8 * pp,                  // 23-26 V, Vinv, gp, ppred
-      F8 * n, F8 * static_cast<size_t>(ld) * ld, 256};               // 27-29 e, S, flag
+      F8 * n, F8 * static_cast<size_t>(ld) * ld, 256,                // 27-29 e, S, flag
+      ROB && D == 6 ? F8 * n : 0};                                   // 30 sw (robust rigid)
   constexpr int kBufs = sizeof(sizes) / sizeof(sizes[0]);
   size_t tot = 0;
   for (size_t s : sizes) tot += al(s);
@@ -941,6 +1038,8 @@ int ba_run(rs_ctx *c, double *cams, int64_t nC, double *pts, int64_t nP, const i
   double *d_gp = reinterpret_cast<double *>(buf[25]), *d_ppred = reinterpret_cast<double *>(buf[26]);
   double *d_e = reinterpret_cast<double *>(buf[27]), *d_S = reinterpret_cast<double *>(buf[28]);
   int32_t *d_flag = reinterpret_cast<int32_t *>(buf[29]);
+  double *d_sw = reinterpret_cast<double *>(buf[30]);
+  const double c2 = ROB ? f_scale * f_scale : 1.0, ic2 = 1.0 / c2;
   volatile double *rec = static_cast<volatile double *>(c->pinned);
 
   hipStream_t s = c->stream;
@@ -975,8 +1074,8 @@ int ba_run(rs_ctx *c, double *cams, int64_t nC, double *pts, int64_t nP, const i
   double serial = 0.0;
   // the cost at (cm, pt) into the record; waits for it
   auto cost_at = [&](const double *cm, const double *pt, bool trial, double lam) -> int {
-    hipLaunchKernelGGL(rsd::k_ba_cost, dim3(blocks(n, 256)), dim3(256), 0, s, cm, pt, d_ov, d_op,
-                       d_uv, ni, d_e);
+    hipLaunchKernelGGL(rsd::k_ba_cost<ROB>, dim3(blocks(n, 256)), dim3(256), 0, s, cm, pt, d_ov,
+                       d_op, d_uv, ni, d_e, loss, c2, ic2);
     serial += 1.0;
     hipLaunchKernelGGL(rsd::k_ba_final<D>, dim3(1), dim3(rsd::kBaFinalThreads), 0, s, d_e, ni,
                        d_ppred, trial ? nPi : 0, d_dc, d_U, d_gc, trial ? nCi : 0, lam, d_flag,
@@ -1000,13 +1099,17 @@ int ba_run(rs_ctx *c, double *cams, int64_t nC, double *pts, int64_t nP, const i
   bool done = false;
   for (it = 1; it <= max_iter && !done; ++it) {
     HIP_TRY(mk.begin());
-    hipLaunchKernelGGL(D == 12 ? rsd::k_ba_linearize : rsd::k_ba_linearize_rigid,
-                       dim3(blocks(n, 256)), dim3(256), 0, s, d_cams, d_pts, d_ov, d_op, d_uv, ni,
-                       d_r, d_jcs, d_Jp, d_W);
+    if constexpr (D == 12)
+      hipLaunchKernelGGL(rsd::k_ba_linearize<ROB>, dim3(blocks(n, 256)), dim3(256), 0, s, d_cams,
+                         d_pts, d_ov, d_op, d_uv, ni, d_r, d_jcs, d_Jp, d_W, loss, ic2);
+    else
+      hipLaunchKernelGGL(rsd::k_ba_linearize_rigid<ROB>, dim3(blocks(n, 256)), dim3(256), 0, s,
+                         d_cams, d_pts, d_ov, d_op, d_uv, ni, d_r, d_jcs, d_Jp, d_W, loss, ic2,
+                         d_sw);
     HIP_TRY(mk.mark(T_LIN));
     if (nf > 0) {
-      hipLaunchKernelGGL(rsd::k_ba_camera<D>, dim3(nf), dim3(NT), 0, s, d_cos, d_cam_off, d_cam_obs,
-                         d_jcs, d_r, d_U, d_gc);
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(rsd::k_ba_camera<D, ROB && D == 6>), dim3(nf), dim3(NT), 0,
+                         s, d_cos, d_cam_off, d_cam_obs, d_jcs, d_r, d_U, d_gc, d_sw);
       HIP_TRY(mk.mark(T_CAM));
     }
     hipLaunchKernelGGL(rsd::k_ba_pointsum, dim3(blocks(pp, 256)), dim3(256), 0, s, d_pt_off,
@@ -1063,9 +1166,22 @@ int ba_run(rs_ctx *c, double *cams, int64_t nC, double *pts, int64_t nP, const i
   }
   it = done ? it - 1 : max_iter;
 
+  if constexpr (ROB) {
+    if (weights) {
+      HIP_TRY(mk.begin());
+      hipLaunchKernelGGL(rsd::k_ba_weights, dim3(blocks(n, 256)), dim3(256), 0, s, d_cams, d_pts,
+                         d_ov, d_op, d_uv, ni, d_e, loss, ic2);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(mk.mark(T_COST));
+      HIP_TRY(hipMemcpyAsync(weights, d_e, F8 * n, hipMemcpyDeviceToHost, s));
+    }
+  } else if (weights) {
+    for (int64_t i = 0; i < n; ++i) weights[i] = 1.0;
+  }
   HIP_TRY(hipMemcpyAsync(cams, d_cams, F8 * 12 * nC, hipMemcpyDeviceToHost, s));
   if (nP > 0) HIP_TRY(hipMemcpyAsync(pts, d_pts, F8 * 3 * nP, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(mk.collect());
   info->cost_init = cost0;
   info->cost = cost;
   info->lambda = lam;
@@ -1082,12 +1198,36 @@ extern "C" int rs_bundle_adjust(rs_ctx *c, double *cams, int64_t nC, double *pts
                                 const int32_t *obs_view, const int32_t *obs_point,
                                 const double *uv, int64_t n, int32_t max_iter, double ftol,
                                 rs_ba_info *info) {
-  return ba_run<12>(c, cams, nC, pts, nP, obs_view, obs_point, uv, n, max_iter, ftol, info);
+  return ba_run<12, false>(c, cams, nC, pts, nP, obs_view, obs_point, uv, n, max_iter, ftol, 0,
+                           1.0, nullptr, info);
 }
 
 extern "C" int rs_bundle_adjust_rigid(rs_ctx *c, double *cams, int64_t nC, double *pts,
                                       int64_t nP, const int32_t *obs_view,
                                       const int32_t *obs_point, const double *uv, int64_t n,
                                       int32_t max_iter, double ftol, rs_ba_info *info) {
-  return ba_run<6>(c, cams, nC, pts, nP, obs_view, obs_point, uv, n, max_iter, ftol, info);
+  return ba_run<6, false>(c, cams, nC, pts, nP, obs_view, obs_point, uv, n, max_iter, ftol, 0,
+                          1.0, nullptr, info);
+}
+
+extern "C" int rs_bundle_adjust_robust(rs_ctx *c, double *cams, int64_t nC, double *pts,
+                                       int64_t nP, const int32_t *obs_view,
+                                       const int32_t *obs_point, const double *uv, int64_t n,
+                                       int32_t max_iter, double ftol, int32_t rigid, int32_t loss,
+                                       double f_scale, double *weights, rs_ba_info *info) {
+  if (loss < 0 || loss > 3) return fail(RS_EINVAL, "loss must be 0 (linear) .. 3 (cauchy)");
+  if (!std::isfinite(f_scale) || f_scale <= 0.0)
+    return fail(RS_EINVAL, "f_scale must be finite and > 0");
+  if (loss == 0) {
+    if (rigid)
+      return ba_run<6, false>(c, cams, nC, pts, nP, obs_view, obs_point, uv, n, max_iter, ftol, 0,
+                              1.0, weights, info);
+    return ba_run<12, false>(c, cams, nC, pts, nP, obs_view, obs_point, uv, n, max_iter, ftol, 0,
+                             1.0, weights, info);
+  }
+  if (rigid)
+    return ba_run<6, true>(c, cams, nC, pts, nP, obs_view, obs_point, uv, n, max_iter, ftol, loss,
+                           f_scale, weights, info);
+  return ba_run<12, true>(c, cams, nC, pts, nP, obs_view, obs_point, uv, n, max_iter, ftol, loss,
+                          f_scale, weights, info);
 }

@@ -86,6 +86,7 @@ BA_MAX_CAMERAS = 128
 WASH_MAX_TRACK = 128
 CLOUD_MAX_CELLS = 1 << 21
 CLOUD_STAGES = ("grid", "scan", "sort", "normals", "attributes")
+BA_LOSSES = ("linear", "soft_l1", "huber", "cauchy")   # RS_BA_LOSS_*: the index is the code
 BA_KERNELS = ("k_ba_linearize", "k_ba_camera", "k_ba_pointsum", "k_ba_point", "k_ba_schur",
               "k_ba_chol", "k_ba_step", "k_ba_cost+final")
 
@@ -182,6 +183,10 @@ _SIGS = {
     "rs_bundle_adjust_rigid": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _i32p, _i32p,
                                          _dp, C.c_int64, C.c_int32, C.c_double,
                                          C.POINTER(BaInfo)]),
+    "rs_bundle_adjust_robust": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _i32p,
+                                          _i32p, _dp, C.c_int64, C.c_int32, C.c_double,
+                                          C.c_int32, C.c_int32, C.c_double, _dp,
+                                          C.POINTER(BaInfo)]),
     "rs_ba_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp, _i64p]),
     "rs_triangulate_nview": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _i32p, _i32p,
                                        _dp, C.c_int64, _i32p]),

@@ -12,7 +12,9 @@ Array-level functions (HIP kernels of tables.hip):
                             points eliminated by a Schur complement, camera 0 fixed
   * ``bundle_adjust_rigid`` the same objective over rigid poses: 6 local coordinates per camera,
                             R+ = Exp(omega) R, t+ = Exp(omega) t + tau, so every R stays a
-                            rotation (ba.hip, rs_bundle_adjust_rigid)
+                            rotation (ba.hip, rs_bundle_adjust_rigid).  Both take scipy's
+                            ``loss=`` ("soft_l1", "huber", "cauchy") and ``f_scale=``
+                            (rs_bundle_adjust_robust); run them so before ``wash_points``
   * ``nearest_rotations``   host helper: the nearest rotation to every 3 x 3 block of (nC, 3, 4)
                             cameras, for tables that came through the 12-parameter adjustment
   * ``triangulate_nview``   every point from all its observations (wash.hip)
@@ -33,6 +35,9 @@ arithmetic above on the GPU and do the same bookkeeping in the same order):
   * ``get3DPointsColorsAndNormals(T)``                             Tables.get3DPointsColorsAndNormals
 """
 from __future__ import annotations
+
+import functools
+import inspect
 
 import numpy as np
 
@@ -138,6 +143,37 @@ def ba_jacobian(cams, pts, obs_view, obs_point, ctx=None):
     return Jc, Jp
 
 
+def _loss_code(loss, f_scale):
+    if loss not in _ffi.BA_LOSSES:
+        raise ValueError(f"unknown loss {loss!r}: one of {', '.join(_ffi.BA_LOSSES)}")
+    f_scale = float(f_scale)
+    if not (np.isfinite(f_scale) and f_scale > 0.0):
+        raise ValueError(f"f_scale must be finite and > 0, not {f_scale}")
+    return _ffi.BA_LOSSES.index(loss), f_scale
+
+
+def _robust_keywords(robust):
+    """Decorator of the four adjustments.  The decorated function is the sum-of-squares call
+    and keeps its parameters, positions and defaults (``inspect.signature`` reports them, through
+    ``__wrapped__``); on top it accepts the keyword-only ``loss="linear"`` and ``f_scale=1.0``.
+    Both are checked before anything else happens; "linear" calls the function itself, any other
+    loss calls ``robust(*its_arguments, loss, f_scale)``."""
+    def decorate(linear):
+        sig = inspect.signature(linear)
+
+        @functools.wraps(linear)
+        def adjust(*args, loss="linear", f_scale=1.0, **kw):
+            code, f_scale = _loss_code(loss, f_scale)
+            if code == 0:
+                return linear(*args, **kw)
+            bound = sig.bind(*args, **kw)
+            bound.apply_defaults()
+            return robust(*bound.args, loss, f_scale)
+        return adjust
+    return decorate
+
+
+@_robust_keywords(lambda *a: _bundle_adjust(False, *a))
 def bundle_adjust(cams, pts, obs_view, obs_point, uv, max_iter=200, ftol=1e-15, ctx=None):
     """The objective of ``ba_residuals`` minimised over cameras 1.. (12 parameters each) and the
     points: Levenberg-Marquardt with Marquardt damping and Nielsen's update, the points
@@ -147,12 +183,27 @@ def bundle_adjust(cams, pts, obs_view, obs_point, uv, max_iter=200, ftol=1e-15, 
 
     Returns (cams (nC, 3, 4), pts (nP, 3), info) with info = dict(cost_init, cost, iterations,
     status, rejected, lambda): costs are 0.5 |r|^2; status 1 = an accepted step gained
-    <= ftol * cost, 2 = damping above 1e32, 0 = max_iter linearisations."""
-    return _bundle_adjust("rs_bundle_adjust", cams, pts, obs_view, obs_point, uv, max_iter, ftol,
-                          ctx)
+    <= ftol * cost, 2 = damping above 1e32, 0 = max_iter linearisations.
+
+    ``loss`` = "soft_l1", "huber" or "cauchy" with the scale ``f_scale`` = C > 0 minimises the
+    robust cost 0.5 C^2 sum_i rho(z_i), z_i = (ru_i^2 + rv_i^2) / C^2, instead
+    (rs_bundle_adjust_robust): soft_l1 rho = 2 (sqrt(1 + z) - 1), huber rho = z for z <= 1 and
+    2 sqrt(z) - 1 above, cauchy rho = log1p(z).  These are the names and forms of
+    scipy.optimize.least_squares; unlike scipy, rho acts on the squared norm of an observation's
+    residual, not on its u and v components separately.  The same LM runs on the re-weighted
+    problem, the weights w_i = rho'(z_i) taken anew at every linearisation.  The costs in info
+    are then robust costs, and info gains "weights": w_i (n,) at the returned state, in the
+    order of the observations.  An outlier's weight is small: with "cauchy" and ``f_scale`` a
+    few times the noise, the cameras come out as if the outliers had been removed, which is
+    what ``wash_points`` needs to judge them.  ``loss`` = "linear" (the default) is the plain
+    sum of squares, bit for bit what it was without these keywords.  ValueError for an unknown
+    loss name or an ``f_scale`` that is not finite and > 0.  Both are keyword-only."""
+    return _bundle_adjust(False, cams, pts, obs_view, obs_point, uv, max_iter, ftol, ctx)
 
 
-def _bundle_adjust(entry, cams, pts, obs_view, obs_point, uv, max_iter, ftol, ctx):
+def _bundle_adjust(rigid, cams, pts, obs_view, obs_point, uv, max_iter, ftol, ctx,
+                   loss="linear", f_scale=1.0):
+    code, f_scale = _loss_code(loss, f_scale)
     cams, pts, ov, op = _ba_args(cams, pts, obs_view, obs_point)
     cams, pts = cams.copy(), pts.copy()
     uv = _ffi.f64c(uv).reshape(-1, 2)
@@ -164,15 +215,25 @@ def _bundle_adjust(entry, cams, pts, obs_view, obs_point, uv, max_iter, ftol, ct
         raise ValueError('bundle adjustment needs at least one camera')
     info = _ffi.BaInfo()
     i32 = _ffi.C.c_int32
-    _ffi.check(getattr(_ffi.lib(), entry)(
-        _ctx(ctx), _ffi.ptr(cams, _d), len(cams), _ffi.ptr(pts, _d), len(pts), _ffi.ptr(ov, i32),
-        _ffi.ptr(op, i32), _ffi.ptr(uv, _d), len(ov), int(max_iter), float(ftol),
-        _ffi.C.byref(info)))
-    return cams, pts, {"cost_init": info.cost_init, "cost": info.cost,
-                       "iterations": info.iterations, "status": info.status,
-                       "rejected": info.rejected, "lambda": info.lam}
+    args = (_ctx(ctx), _ffi.ptr(cams, _d), len(cams), _ffi.ptr(pts, _d), len(pts),
+            _ffi.ptr(ov, i32), _ffi.ptr(op, i32), _ffi.ptr(uv, _d), len(ov), int(max_iter),
+            float(ftol))
+    weights = None
+    if code == 0:
+        entry = _ffi.lib().rs_bundle_adjust_rigid if rigid else _ffi.lib().rs_bundle_adjust
+        _ffi.check(entry(*args, _ffi.C.byref(info)))
+    else:
+        weights = np.empty(len(ov))
+        _ffi.check(_ffi.lib().rs_bundle_adjust_robust(
+            *args, int(bool(rigid)), code, f_scale, _ffi.ptr(weights, _d), _ffi.C.byref(info)))
+    out = {"cost_init": info.cost_init, "cost": info.cost, "iterations": info.iterations,
+           "status": info.status, "rejected": info.rejected, "lambda": info.lam}
+    if weights is not None:
+        out["weights"] = weights
+    return cams, pts, out
 
 
+@_robust_keywords(lambda *a: _bundle_adjust(True, *a))
 def bundle_adjust_rigid(cams, pts, obs_view, obs_point, uv, max_iter=200, ftol=1e-15, ctx=None):
     """``bundle_adjust`` over rigid poses (rs_bundle_adjust_rigid): the same objective, LM rules
     and return value, but camera k = [R | t] moves by 6 local coordinates (omega, tau),
@@ -182,9 +243,9 @@ def bundle_adjust_rigid(cams, pts, obs_view, obs_point, uv, max_iter=200, ftol=1
     Every free camera (1.. with an observation) must hold a rotation: max |R^T R - I| <= 1e-6
     and det R > 0, else ValueError names the camera -- ``nearest_rotations`` repairs cameras
     that came through the 12-parameter ``bundle_adjust``.  Camera 0, and every camera or point
-    without an observation, comes back bit for bit unchanged.  The inputs are not modified."""
-    return _bundle_adjust("rs_bundle_adjust_rigid", cams, pts, obs_view, obs_point, uv, max_iter,
-                          ftol, ctx)
+    without an observation, comes back bit for bit unchanged.  The inputs are not modified.
+    The keywords ``loss`` and ``f_scale`` as in ``bundle_adjust``."""
+    return _bundle_adjust(True, cams, pts, obs_view, obs_point, uv, max_iter, ftol, ctx)
 
 
 def nearest_rotations(cams):
@@ -310,23 +371,29 @@ def add_new_points_table(T, A_y1_hom, A_y2_hom, view_index_1, view_index_2):
     return counter
 
 
+@_robust_keywords(lambda *a: _adjust_table(bundle_adjust, *a))
 def BundleAdjustment2(T, max_iter=200, ftol=1e-15, ctx=None):
     """Tables.BundleAdjustment2 (tables.py:260-338) on the GPU: the cameras [R | t] of T_views,
     the points of T_points and image_coordinates[:2] of T_obs, in table order, through
     ``bundle_adjust`` instead of scipy's TRF, then the write-back of updateCameras3Dpoints2
     (tables.py:384-390): every view gets a new pose of its own pose class built from the 3 x 4
-    result, every point its new coordinates.  Returns the info dict of ``bundle_adjust``."""
+    result, every point its new coordinates.  Returns the info dict of ``bundle_adjust``.
+    The keywords ``loss`` and ``f_scale`` are those of ``bundle_adjust`` (the reference's
+    least_squares call leaves them at scipy's defaults, "linear" and 1.0); info["weights"] is in
+    T_obs order."""
     return _adjust_table(bundle_adjust, T, max_iter, ftol, ctx)
 
 
+@_robust_keywords(lambda *a: _adjust_table(bundle_adjust_rigid, *a))
 def BundleAdjustmentRigid(T, max_iter=200, ftol=1e-15, ctx=None):
     """``BundleAdjustment2`` with ``bundle_adjust_rigid`` in place of ``bundle_adjust``: the same
     gathering and write-back, every view's R stays a rotation.  The poses of the table must be
-    rotations already (ValueError otherwise; see ``nearest_rotations``)."""
+    rotations already (ValueError otherwise; see ``nearest_rotations``).  The keywords ``loss``
+    and ``f_scale`` as in ``BundleAdjustment2``."""
     return _adjust_table(bundle_adjust_rigid, T, max_iter, ftol, ctx)
 
 
-def _adjust_table(adjust, T, max_iter, ftol, ctx):
+def _adjust_table(adjust, T, max_iter, ftol, ctx, loss="linear", f_scale=1.0):
     cams = np.array([_pose(v.camera_pose) for v in T.T_views]).reshape(-1, 3, 4)
     pts = np.array([p.point for p in T.T_points], dtype=np.float64).reshape(-1, 3)
     uv = np.array([np.asarray(o.image_coordinates, dtype=np.float64).ravel()[:2]
@@ -334,7 +401,7 @@ def _adjust_table(adjust, T, max_iter, ftol, ctx):
     ov = np.array([o.view_index for o in T.T_obs], dtype=np.int32)
     op = np.array([o.point_3D_index for o in T.T_obs], dtype=np.int32)
     new_pose, new_points, info = adjust(cams, pts, ov, op, uv, max_iter=max_iter, ftol=ftol,
-                                        ctx=ctx)
+                                        ctx=ctx, loss=loss, f_scale=f_scale)
     for i, v in enumerate(T.T_views):
         v.camera_pose = type(v.camera_pose)(new_pose[i, :3, :3], new_pose[i, :, 3])
     for i, p in enumerate(T.T_points):
