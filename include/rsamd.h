@@ -814,6 +814,78 @@ int rs_cloud_normals(rs_ctx *ctx, const double *pts, int64_t n, double radius,
 int rs_cloud_timing(rs_ctx *ctx, int32_t enable, double *ms);
 
 /* ------------------------------------------------------------------------------------------
+ * The dense stage (dense.hip): plane-sweep depth maps and their fusion.  The reference project
+ * stops at a sparse cloud; nothing here restates code of it.  No atomics, one fixed summation
+ * order: the same inputs give bitwise the same outputs.
+ * ------------------------------------------------------------------------------------------ */
+#define RS_DENSE_MAX_SOURCES 8
+#define RS_DENSE_MAX_PATCH 11
+#define RS_DENSE_MAX_DEPTHS 4096
+#define RS_DENSE_MAX_SIDE 16384
+#define RS_DENSE_MAX_PIXELS (1LL << 26)
+#define RS_DENSE_MAX_VOLUME (1LL << 28)
+#define RS_DENSE_MAX_VIEWS 128
+
+/* Plane sweep of one reference view against S source views.  Images are h x w uint8, row-major;
+ * pixel (x, y) is column x, row y, centres at integers.  src holds the S source images one after
+ * the other.  With P = K C = [M | m] per view, the caller passes per source s, row-major,
+ *   A_s = M_s M_ref^-1 (3 x 3),  b_s = m_s - A_s m_ref (3),
+ * and the D plane depths d_k (finite, nonzero, of one sign): plane k is c3_ref . [X; 1] = d_k,
+ * fronto-parallel in the reference view.
+ *   Warp.  Reference pixel p = (x, y, 1) maps to q = d_k (A_s p) + b_s, the source position is
+ *   (x', y') = (q0 / q2, q1 / q2), all fp64.  The sample is valid when q2 d_k > 0,
+ *   0 <= x' <= w - 1 and 0 <= y' <= h - 1.
+ *   Sample.  x0 = floor(x'), y0 = floor(y'); fx = (float)(x' - x0), fy likewise; the right and
+ *   lower neighbours are clamped to the last column and row.  With v = pixel - 128 (exact), in
+ *   fp32: top = v00 + fx (v01 - v00), bottom = v10 + fx (v11 - v10),
+ *   sample = top + fy (bottom - top).
+ *   Score.  r = patch / 2, n = patch^2.  Over the n pixels of the window around (x, y), with
+ *   a = reference pixel - 128 and b = the warped sample of that same pixel (each window pixel
+ *   goes through the plane's warp itself):
+ *     va = n sum a^2 - (sum a)^2   (exact integer),   vb = n sum b^2 - (sum b)^2,
+ *     score = (n sum ab - sum a sum b) / sqrt(va vb),
+ *   the b-sums in fp32 in raster order.  The sums are accumulated on the values shifted by 128
+ *   (one pass, no second centring pass).  The score is valid when the window lies inside the
+ *   image, all n samples are valid, va >= min_var n^2 (on the integers) and vb >= min_var n^2.
+ *   Cost.  cost(pixel, k) = the sum of the valid sources' scores in source order / their number
+ *   nvalid; no valid source: the hypothesis is invalid (NaN in the volume).
+ *   Winner.  index = the k of the largest cost, the smallest such k on ties; score its cost,
+ *   nvalid its number of sources.  With c-, c0, c+ the costs at index - 1, index, index + 1:
+ *   delta = clamp(0.5 (c- - c+) / (c- - 2 c0 + c+), -0.5, 0.5), and 0 when a neighbour is
+ *   missing or invalid or the denominator is not negative.  A pixel without a valid hypothesis
+ *   gets index -1, delta 0, score NaN, nvalid 0.
+ * index (h, w) int32, delta and score (h, w) float, nvalid (h, w) uint8; volume (D, h, w) float
+ * is written when not null, and the other outputs do not depend on that.
+ * RS_EINVAL before any launch: patch even or outside 3..RS_DENSE_MAX_PATCH, S outside
+ * 1..RS_DENSE_MAX_SOURCES, D outside 1..RS_DENSE_MAX_DEPTHS, a side not above patch or above
+ * RS_DENSE_MAX_SIDE, h w > RS_DENSE_MAX_PIXELS, D h w > RS_DENSE_MAX_VOLUME with a volume,
+ * min_var not finite or <= 0, A or b not finite, a depth zero or not finite, depths of mixed
+ * sign. */
+int rs_dense_plane_sweep(rs_ctx *ctx, const uint8_t *ref, int64_t h, int64_t w,
+                         const uint8_t *src, int32_t S, const double *A, const double *b,
+                         const double *depths, int64_t D, int32_t patch, double min_var,
+                         int32_t *index, float *delta, float *score, uint8_t *nvalid,
+                         float *volume);
+
+/* Cross-view agreement of V depth maps, depth (V, h, w) fp64 with NaN for "none".  P is
+ * (V, 3, 4) = K C per view, [M | m]; Minv (V, 3, 3) the inverses of the M.  For view i and pixel
+ * p = (x, y, 1) with finite depth d: X = Minv_i (d p - m_i).  For every other view j:
+ * q = M_j X + m_j, d' = q2, (u, v) = (floor(q0 / q2 + 0.5), floor(q1 / q2 + 0.5)); when
+ * 0 <= u <= w - 1 and 0 <= v <= h - 1, view j agrees if d_j = depth[j, v, u] is finite and
+ * |d_j - d'| <= rel_tol |d'|.  count[i, y, x] is the number of agreeing views, 0 for a
+ * non-finite depth.  All fp64, one lane per (i, pixel).  RS_EINVAL: V outside
+ * 1..RS_DENSE_MAX_VIEWS, a side outside 1..RS_DENSE_MAX_SIDE, h w > RS_DENSE_MAX_PIXELS,
+ * V h w > RS_DENSE_MAX_VOLUME, rel_tol not finite or negative, a camera not finite. */
+int rs_dense_consistency(rs_ctx *ctx, const double *depth, int32_t V, int64_t h, int64_t w,
+                         const double *P, const double *Minv, double rel_tol, uint8_t *count);
+
+/* HIP events around the kernel of the next dense calls (enable != 0).  Returns the last timed
+ * calls' device ms: slot 0 the plane sweep, slot 1 the consistency count; -1 where none
+ * (tools/bench_dense.py). */
+#define RS_DENSE_TIMING_SLOTS 2
+int rs_dense_timing(rs_ctx *ctx, int32_t enable, double *ms);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU (RCCL over xGMI).  One process per GPU; the unique id travels out of band.
  * ---------------------------------------------------------------------------------------- */
 #define RS_COMM_ID_BYTES 128

@@ -138,6 +138,8 @@ extern "C" int rs_ctx_destroy(rs_ctx *c) {
     if (e) (void)hipEventDestroy(e);
   for (auto &e : c->cloud_ev)
     if (e) (void)hipEventDestroy(e);
+  for (auto &e : c->dense_ev)
+    if (e) (void)hipEventDestroy(e);
   if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;

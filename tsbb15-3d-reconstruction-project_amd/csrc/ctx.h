@@ -49,6 +49,11 @@ struct rs_ctx {
   int cloud_timing = 0;
   hipEvent_t cloud_ev[5] = {};
   double cloud_ms[RS_CLOUD_TIMING_SLOTS] = {-1.0, -1.0, -1.0, -1.0, -1.0};
+  // rs_dense_timing: HIP events around the kernel of the next dense calls (dense.hip), the last
+  // timed calls' device ms (RS_DENSE_TIMING_SLOTS: plane sweep, consistency)
+  int dense_timing = 0;
+  hipEvent_t dense_ev[2] = {};
+  double dense_ms[RS_DENSE_TIMING_SLOTS] = {-1.0, -1.0};
 };
 
 namespace rs {

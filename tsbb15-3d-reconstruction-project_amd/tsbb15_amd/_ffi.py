@@ -210,6 +210,12 @@ _SIGS = {
     "rs_cloud_normals": (C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_double, _dp, _dp, _i32p, _dp,
                                    C.POINTER(CloudInfo)]),
     "rs_cloud_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "rs_dense_plane_sweep": (C.c_int, [C.c_void_p, _u8p, C.c_int64, C.c_int64, _u8p, C.c_int32,
+                                       _dp, _dp, _dp, C.c_int64, C.c_int32, C.c_double, _i32p,
+                                       _fp, _fp, _u8p, _fp]),
+    "rs_dense_consistency": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_int64, C.c_int64, _dp,
+                                       _dp, C.c_double, _u8p]),
+    "rs_dense_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
     "rs_np_shard_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.POINTER(C.c_void_p)]),
     "rs_np_shard_destroy": (C.c_int, [C.c_void_p]),

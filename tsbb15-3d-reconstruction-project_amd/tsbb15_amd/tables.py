@@ -65,6 +65,9 @@ def _pose(C):
     return M
 
 
+pose_matrix = _pose   # the public name (dense.table_views)
+
+
 def match_observations(obs_coords, obs_point, queries, tol=MATCH_TOL, ctx=None):
     obs = _ffi.f64c(obs_coords).reshape(-1, 3)
     op = np.ascontiguousarray(obs_point, dtype=np.int64).ravel()
