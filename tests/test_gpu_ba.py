@@ -21,6 +21,7 @@ import ba_fixture as bf
 from conftest import golden
 from oracle import tables_ref as tr
 from tables_fixture import MiniTables, Pose
+from tsbb15_amd import _ffi, cloud, dense, features
 from tsbb15_amd import tables as gt
 
 pytestmark = pytest.mark.gpu
@@ -296,3 +297,57 @@ def test_bundle_adjustment2_on_a_table(ctx):
     gt.add_new_view(T, g("K"), 2, g("match_queries"), g("match_y2_hom"), g("match_y1"),
                     g("match_y2"))
     assert T.T_views.size == n_views + 1
+
+
+# ------------------------------------------------------------------------------------------
+# rs_ba_timing
+# ------------------------------------------------------------------------------------------
+def test_timing_slots():
+    """The sums per kernel start at 0; a timed call fills them and counts its trials; the next
+    timed call starts from zero again; a call after disabling changes nothing; timed and
+    untimed results are bit-equal.  A context of its own, so that no earlier call has timed."""
+    P = _problem("5x40")
+    ov, op, uv = P["ov"], P["op"], P["uv"]
+    c0, p0 = bf.start(P, 1e-3)
+    run = lambda it: gt.bundle_adjust(c0, p0, ov, op, uv, max_iter=it, ctx=own)
+    cost = _ffi.BA_KERNELS[-1]
+    own = _ffi.Context()
+    try:
+        plain = run(3)
+        assert _ffi.ba_timing(own, 1) == (dict.fromkeys(_ffi.BA_KERNELS, 0.0), 0)
+        timed = run(3)
+        ms, trials = _ffi.ba_timing(own, 1)
+        print("3 iterations:", ms, trials)
+        assert trials >= 1 and ms[cost] > 0.0
+        assert all(np.isfinite(v) and 0.0 <= v < 1e3 for v in ms.values())
+        # the same call again: the same trials, not the two calls' together
+        run(3)
+        assert _ffi.ba_timing(own, 1)[1] == trials
+        # no iteration at all: only the first cost is timed, nothing of the calls before stays
+        run(0)
+        ms0, trials0 = _ffi.ba_timing(own, 0)
+        print("0 iterations:", ms0, trials0)
+        assert trials0 == 0 and 0.0 < ms0[cost] < 1e3
+        assert all(v == 0.0 for k, v in ms0.items() if k != cost)
+        again = run(3)
+        assert _ffi.ba_timing(own, 0) == (ms0, trials0)
+        for a, b, c in zip(plain[:2], timed[:2], again[:2]):
+            assert a.tobytes() == b.tobytes() == c.tobytes()
+        assert plain[2] == timed[2] == again[2]
+    finally:
+        own.close()
+
+
+def test_context_with_every_timer_enabled_is_destroyed():
+    P = _problem("5x40")
+    c0, p0 = bf.start(P, 1e-3)
+    own = _ffi.Context()
+    _ffi.pnp_timing(own, 1)
+    _ffi.ba_timing(own, 1)
+    features.timing(1, ctx=own)
+    cloud.timing(1, ctx=own)
+    dense.timing(1, ctx=own)
+    gt.bundle_adjust(c0, p0, P["ov"], P["op"], P["uv"], max_iter=1, ctx=own)   # BA's events exist
+    own.close()
+    with pytest.raises(RuntimeError):
+        own.handle

@@ -15,7 +15,7 @@ import pytest
 
 import cloud_fixture as cf
 import cloud_ref as cr
-from tsbb15_amd import cloud
+from tsbb15_amd import _ffi, cloud
 from tsbb15_amd import tables as gt
 
 pytestmark = pytest.mark.gpu
@@ -312,3 +312,48 @@ def test_table_dropin_with_radius(ctx, tmp_path):
     out = io.BytesIO()
     cloud.save_txt(out, points, colors, normals)
     assert out.getvalue() == open(path, "rb").read()
+
+
+# ------------------------------------------------------------------------------------------
+# rs_cloud_timing
+# ------------------------------------------------------------------------------------------
+def _timed(ms, names):
+    return all(np.isfinite(ms[k]) and 0.0 < ms[k] < 1e3 for k in names)
+
+
+def test_timing_slots():
+    """Slots start at -1; rs_cloud_normals fills grid / scan / sort / normals and
+    rs_cloud_attributes fills attributes alone; a call after disabling changes nothing; timed
+    and untimed results are bit-equal.  A context of its own, so that no earlier call has timed."""
+    pts, radius, orient, _ = cf.reference("dino0.1")
+    T = cf.table()
+    tp, _, _ = cr.table_attributes(T)
+    ep, eo = cr.table_entries(T)
+    cams = np.array([v.camera_pose.GetCameraMatrix() for v in T.T_views])
+    ov = np.array([o.view_index for o in T.T_obs])
+    col = np.array([o.color for o in T.T_obs])
+    normals_of = lambda c: cloud.surface_normals(pts, radius, orient=orient, ctx=c)
+    attrs_of = lambda c: cloud.point_attributes(cams, tp, ep, eo, ov, col, ctx=c)
+    stages = _ffi.CLOUD_STAGES[:4]
+    own = _ffi.Context()
+    try:
+        plain_n, plain_a = normals_of(own), attrs_of(own)
+        assert cloud.timing(1, ctx=own) == dict.fromkeys(_ffi.CLOUD_STAGES, -1.0)
+        timed_n = normals_of(own)
+        ms = cloud.timing(1, ctx=own)
+        print("after surface_normals:", ms)
+        assert _timed(ms, stages) and ms["attributes"] == -1.0
+        timed_a = attrs_of(own)
+        ms2 = cloud.timing(0, ctx=own)
+        print("after point_attributes:", ms2)
+        assert _timed(ms2, ["attributes"])
+        assert all(ms2[k] == ms[k] for k in stages)
+        again_n, again_a = normals_of(own), attrs_of(own)
+        assert cloud.timing(0, ctx=own) == ms2
+        for a, b, c in zip(plain_n[:4], timed_n[:4], again_n[:4]):
+            assert _same_bits(a, b) and _same_bits(a, c)
+        assert plain_n[4] == timed_n[4] == again_n[4]
+        for a, b, c in zip(plain_a, timed_a, again_a):
+            assert _same_bits(a, b) and _same_bits(a, c)
+    finally:
+        own.close()

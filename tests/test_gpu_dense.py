@@ -24,7 +24,7 @@ import pytest
 
 import dense_fixture as df
 import dense_ref as dr
-from tsbb15_amd import dense
+from tsbb15_amd import _ffi, dense
 
 pytestmark = pytest.mark.gpu
 
@@ -301,3 +301,32 @@ def test_fuse(ctx):
     n, c = df.SLANTED
     assert np.abs(pts @ n - c).max() < 0.5
     assert np.all((grey >= 0) & (grey <= 1)) and np.array_equal(np.unique(view), [0, 1, 2])
+
+
+def test_timing_slots():
+    """Slots start at -1; rs_dense_plane_sweep fills plane_sweep alone and rs_dense_consistency
+    fills consistency alone; a call after disabling changes nothing; timed and untimed results
+    are bit-equal.  A context of its own, so that no earlier call has timed."""
+    case = df.sweep_cases()["fronto_p5"]
+    depth, cams = df.consistency_case()
+    timed = lambda ms, k: np.isfinite(ms[k]) and 0.0 < ms[k] < 1e3
+    own = _ffi.Context()
+    try:
+        plain_s = _sweep(case, own, return_volume=True)
+        plain_c = dense.consistency(depth, cams, df.K, rel_tol=0.01, ctx=own)
+        assert dense.timing(1, ctx=own) == {"plane_sweep": -1.0, "consistency": -1.0}
+        timed_c = dense.consistency(depth, cams, df.K, rel_tol=0.01, ctx=own)
+        ms = dense.timing(1, ctx=own)
+        print("after consistency:", ms)
+        assert timed(ms, "consistency") and ms["plane_sweep"] == -1.0
+        timed_s = _sweep(case, own, return_volume=True)
+        ms2 = dense.timing(0, ctx=own)
+        print("after plane_sweep:", ms2)
+        assert timed(ms2, "plane_sweep") and ms2["consistency"] == ms["consistency"]
+        again_s = _sweep(case, own, return_volume=True)
+        again_c = dense.consistency(depth, cams, df.K, rel_tol=0.01, ctx=own)
+        assert dense.timing(0, ctx=own) == ms2
+        assert _same_bits(plain_s, timed_s) and _same_bits(plain_s, again_s)
+        assert np.array_equal(plain_c, timed_c) and np.array_equal(plain_c, again_c)
+    finally:
+        own.close()

@@ -8,7 +8,7 @@ import pytest
 
 from conftest import golden
 from oracle import pnp_ref
-from tsbb15_amd import cv, pnp, ransac, synth
+from tsbb15_amd import _ffi, cv, pnp, ransac, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -545,3 +545,27 @@ def test_dlt_minimal_samples_accuracy_against_numpy_svd(ctx):
           f"{np.percentile(dr, 99):.3g}; t rel max {dt.max():.3g} p99 {np.percentile(dt, 99):.3g}")
     assert len(dr) >= 390
     assert dr.max() < 1e-8 and dt.max() < 1e-8
+
+
+def test_pnp_timing_slots():
+    """solve_ms and count_ms start at -1; a timed rs_pnp_ransac fills both; a call after
+    disabling changes nothing; timed and untimed results are bit-equal.  A context of its own,
+    so that no earlier call has timed."""
+    X, _, y, _, _, _ = synth.pnp_scene(500, 0.30, seed=3)
+    thr = (1.5 / 800.0) ** 2
+    run = lambda: ransac.ransac_pnp(X, y, X, y, 2000, thr, 6, sampler="philox", seed=11, ctx=own)
+    own = _ffi.Context()
+    try:
+        plain = run()
+        assert _ffi.pnp_timing(own, 1) == (-1.0, -1.0)
+        timed = run()
+        ms = _ffi.pnp_timing(own, 0)
+        print("solve, count ms:", ms)
+        assert all(np.isfinite(v) and 0.0 < v < 1e3 for v in ms)
+        again = run()
+        assert _ffi.pnp_timing(own, 0) == ms
+        for a, b, c in zip(plain[:4], timed[:4], again[:4]):
+            assert a.tobytes() == b.tobytes() == c.tobytes()
+        assert plain[4:] == timed[4:] == again[4:] and plain[4] >= 0      # a pose was found
+    finally:
+        own.close()

@@ -10,8 +10,7 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
-#include "ctx.h"
+#include "host.h"
 #include "device_math.h"
 #include "f8_kernels.h"
 
@@ -58,15 +57,6 @@ int ensure_pinned(rs_ctx *c, size_t bytes) {
 }
 
 }  // namespace rs
-
-using rs::fail;
-using rs::hip_fail;
-
-#define HIP_TRY(expr)                                     \
-  do {                                                    \
-    hipError_t e_ = (expr);                               \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr);     \
-  } while (0)
 
 extern "C" const char *rs_last_error(void) { return rs::g_err.c_str(); }
 extern "C" int rs_version(void) { return 100; }
@@ -130,16 +120,11 @@ extern "C" int rs_ctx_destroy(rs_ctx *c) {
   rs::np_shard_free(c);
   if (c->scratch) (void)hipFree(c->scratch);
   if (c->pinned) (void)hipHostFree(c->pinned);
-  for (auto &e : c->pnp_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto &e : c->ba_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto &e : c->feat_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto &e : c->cloud_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto &e : c->dense_ev)
-    if (e) (void)hipEventDestroy(e);
+  c->pnp.destroy();
+  c->ba.destroy();
+  c->feat.destroy();
+  c->cloud.destroy();
+  c->dense.destroy();
   if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
@@ -162,14 +147,17 @@ extern "C" int rs_fmatrix_residuals(rs_ctx *c, const double *F, const double *x,
   if (n < 0 || n > (1LL << 30)) return fail(RS_EINVAL, "bad point count");
   if (n == 0) return RS_OK;
   HIP_TRY(hipSetDevice(c->device));
-  const size_t bpts = sizeof(double) * 4 * n, bpt = sizeof(rsd::Pt) * n, bout = sizeof(double) * 2 * n;
-  int st = rs::ensure_scratch(c, bpts + bpt + bout + 128);
+  // packed; F counts as part of the 128 bytes after the residuals
+  rs::Layout L(1);
+  const auto xy = L.add<double>(4 * n);
+  const auto pts = L.add<rsd::Pt>(n);
+  const auto out = L.add<double>(2 * n);
+  const auto Fm = L.add<double>(9);
+  int st = L.bind(c, 128 - Fm.bytes);
   if (st) return st;
-  char *base = static_cast<char *>(c->scratch);
-  double *d_xy = reinterpret_cast<double *>(base);
-  rsd::Pt *d_pts = reinterpret_cast<rsd::Pt *>(base + bpts);
-  double *d_out = reinterpret_cast<double *>(base + bpts + bpt);
-  double *d_F = reinterpret_cast<double *>(base + bpts + bpt + bout);
+  double *d_xy = xy.dev(), *d_out = out.dev(), *d_F = Fm.dev();
+  rsd::Pt *d_pts = pts.dev();
+  const size_t bout = out.bytes;
   HIP_TRY(hipMemcpyAsync(d_xy, x, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(d_xy + 2 * n, y, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(d_F, F, sizeof(double) * 9, hipMemcpyHostToDevice, c->stream));
@@ -188,15 +176,19 @@ extern "C" int rs_fmatrix_stls_batch(rs_ctx *c, const double *pl, const double *
     if (tuples[i] < 0 || tuples[i] >= n) return fail(RS_EINVAL, "tuple index out of range");
   HIP_TRY(hipSetDevice(c->device));
   const int64_t ld = (count + 63) / 64 * 64;
-  const size_t bpts = sizeof(double) * 4 * n, bpt = sizeof(rsd::Pt) * n;
-  const size_t btup = sizeof(int) * 8 * count, bF = sizeof(double) * 9 * ld;
-  int st = rs::ensure_scratch(c, bpts + bpt + btup + bF + 256);
+  // packed, F at the next multiple of 64; the bytes skipped for that come out of the 256 after it
+  rs::Layout L(1);
+  const auto xy = L.add<double>(4 * n);
+  const auto pts = L.add<rsd::Pt>(n);
+  const auto tup = L.add<int>(8 * count);
+  const size_t gap = L.skip_to(64);
+  const auto Fs = L.add<double>(9 * ld);
+  int st = L.bind(c, 256 - gap);
   if (st) return st;
-  char *base = static_cast<char *>(c->scratch);
-  double *d_xy = reinterpret_cast<double *>(base);
-  rsd::Pt *d_pts = reinterpret_cast<rsd::Pt *>(base + bpts);
-  int *d_tup = reinterpret_cast<int *>(base + bpts + bpt);
-  double *d_F = reinterpret_cast<double *>(base + ((bpts + bpt + btup + 63) / 64) * 64);
+  double *d_xy = xy.dev(), *d_F = Fs.dev();
+  rsd::Pt *d_pts = pts.dev();
+  int *d_tup = tup.dev();
+  const size_t btup = tup.bytes, bF = Fs.bytes;
   HIP_TRY(hipMemcpyAsync(d_xy, pl, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(d_xy + 2 * n, pr, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(d_tup, tuples, btup, hipMemcpyHostToDevice, c->stream));

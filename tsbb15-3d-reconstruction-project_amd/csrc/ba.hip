@@ -47,8 +47,7 @@
 #include <utility>
 #include <vector>
 
-#include "common.h"
-#include "ctx.h"
+#include "host.h"
 
 namespace rsd {
 
@@ -817,62 +816,43 @@ __global__ __launch_bounds__(kBaFinalThreads) void k_ba_final(
 
 }  // namespace rsd
 
-using rs::fail;
-using rs::hip_fail;
-
-#define HIP_TRY(expr)                                 \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
-
 namespace {
 
 enum { T_LIN, T_CAM, T_PSUM, T_POINT, T_SCHUR, T_CHOL, T_STEP, T_COST, T_SLOTS };
 static_assert(T_SLOTS == RS_BA_TIMING_SLOTS, "rs_ba_timing slots");
 
-// HIP events between the kernels of one batch (up to the next host wait), summed per kernel.
-struct Marks {
+// The context's BA timer over one batch of kernels (up to the next host wait): event k closes
+// the kernel whose slot is slot[k], and collect() adds the batch to the sums per kernel.
+struct BaMarks {
   rs_ctx *c;
   int used = 0;
   int slot[RS_BA_EVENTS] = {};
-  hipError_t begin() {
+  int begin() {
     used = 0;
     return mark(-1);
   }
-  hipError_t mark(int s) {
-    if (!c->ba_timing || used >= RS_BA_EVENTS) return hipSuccess;
-    if (!c->ba_ev[used]) {
-      hipError_t e = hipEventCreate(&c->ba_ev[used]);
-      if (e != hipSuccess) return e;
-    }
+  int mark(int s) {
+    if (!c->ba.on || used >= RS_BA_EVENTS) return RS_OK;
     slot[used] = s;
-    return hipEventRecord(c->ba_ev[used++], c->stream);
+    return c->ba.mark(used++, c->stream);
   }
-  hipError_t collect() {  // after the stream has been waited for
-    for (int k = 1; k < used; ++k) {
-      float ms = 0.f;
-      hipError_t e = hipEventElapsedTime(&ms, c->ba_ev[k - 1], c->ba_ev[k]);
-      if (e != hipSuccess) return e;
-      c->ba_ms[slot[k]] += ms;
-    }
+  int collect() {  // after the stream has been waited for
+    for (int k = 1; k < used; ++k)
+      if (int st = c->ba.add(slot[k], k - 1, k)) return st;
     used = 0;
-    return hipSuccess;
+    return RS_OK;
   }
 };
 
-size_t al(size_t b) { return (b + 255) / 256 * 256; }
-
-unsigned blocks(int64_t n, int per) { return static_cast<unsigned>((n + per - 1) / per); }
+using rs::blocks;
 
 }  // namespace
 
 extern "C" int rs_ba_timing(rs_ctx *c, int32_t enable, double *ms, int64_t *trials) {
   if (!c) return fail(RS_EINVAL, "null context");
-  if (ms)
-    for (int k = 0; k < RS_BA_TIMING_SLOTS; ++k) ms[k] = c->ba_ms[k];
+  if (ms) c->ba.copy_out(ms);
   if (trials) *trials = c->ba_trials;
-  c->ba_timing = enable ? 1 : 0;
+  c->ba.on = enable ? 1 : 0;  // no device call here: the events are created by the first marks
   return RS_OK;
 }
 
@@ -996,49 +976,49 @@ int ba_run(rs_ctx *c, double *cams, int64_t nC, double *pts, int64_t nP, const i
   HIP_TRY(hipSetDevice(c->device));
   const size_t F8 = sizeof(double), I = sizeof(int32_t);
   const int64_t pp = nP > 0 ? nP : 1;
-  const size_t sizes[] = {
-      F8 * 12 * nC, F8 * 12 * nC, F8 * 3 * pp, F8 * 3 * pp,            // 0-3 cams, cams_n, pts, pts_n
-      I * n, I * n, F8 * 2 * n,                                     // 4-6 ov, op, uv
-      I * (nP + 1), I * n, I * (nf + 1), I * cam_obs.size(),       // 7-10 CSR
-      I * nC, I * (nf + 1), sizeof(int64_t) * (npair + 1), I * ent.size(),  // 11-14
-      F8 * 2 * n, F8 * NG * n, F8 * 6 * n, F8 * D3 * n, F8 * D3 * n,   // 15-19 r, jcs, Jp, W, Y
-      F8 * DD * nC, F8 * D * nC, F8 * D * nC,                         // 20-22 U, gc, dc
-      F8 * 6 * pp, F8 * 6 * pp, F8 * 3 * pp, F8 * pp,                  // 23-26 V, Vinv, gp, ppred
-      F8 * n, F8 * static_cast<size_t>(ld) * ld, 256,                // 27-29 e, S, flag
-      ROB && D == 6 ? F8 * n : 0};                                   // 30 sw (robust rigid)
-  constexpr int kBufs = sizeof(sizes) / sizeof(sizes[0]);
-  size_t tot = 0;
-  for (size_t s : sizes) tot += al(s);
-  st = rs::ensure_scratch(c, tot + 256);
+  rs::Layout L;
+  // the state and its trial copy
+  const auto b_cams = L.add<double>(12 * nC), b_cams_n = L.add<double>(12 * nC);
+  const auto b_pts = L.add<double>(3 * pp), b_pts_n = L.add<double>(3 * pp);
+  // the observations
+  const auto b_ov = L.add<int32_t>(n), b_op = L.add<int32_t>(n);
+  const auto b_uv = L.add<double>(2 * n);
+  // CSR by point and by free camera
+  const auto b_pt_off = L.add<int32_t>(nP + 1), b_pt_obs = L.add<int32_t>(n);
+  const auto b_cam_off = L.add<int32_t>(nf + 1), b_cam_obs = L.add<int32_t>(cam_obs.size());
+  // camera -> slot, slot -> camera, the observation pairs of every camera block pair
+  const auto b_slot = L.add<int32_t>(nC), b_cos = L.add<int32_t>(nf + 1);
+  const auto b_pair_off = L.add<int64_t>(npair + 1);
+  const auto b_ent = L.add<int32_t>(ent.size());
+  // r, jcs, Jp, W, Y per observation
+  const auto b_r = L.add<double>(2 * n), b_jcs = L.add<double>(NG * n), b_Jp = L.add<double>(6 * n);
+  const auto b_W = L.add<double>(D3 * n), b_Y = L.add<double>(D3 * n);
+  // U, gc, dc per camera
+  const auto b_U = L.add<double>(DD * nC), b_gc = L.add<double>(D * nC), b_dc = L.add<double>(D * nC);
+  // V, Vinv, gp, ppred per point
+  const auto b_V = L.add<double>(6 * pp), b_Vinv = L.add<double>(6 * pp);
+  const auto b_gp = L.add<double>(3 * pp), b_ppred = L.add<double>(pp);
+  // e per observation, the reduced system S, the failure flag
+  const auto b_e = L.add<double>(n), b_S = L.add<double>(static_cast<size_t>(ld) * ld);
+  const auto b_flag = L.add<int32_t>(64);
+  const auto b_sw = L.add<double>(ROB && D == 6 ? n : 0);  // robust rigid only
+  st = L.bind(c, 256, 256);  // pinned: the status record alone
   if (st) return st;
-  st = rs::ensure_pinned(c, 256);
-  if (st) return st;
-  char *buf[kBufs];
-  {
-    char *q = static_cast<char *>(c->scratch);
-    for (int k = 0; k < kBufs; ++k) {
-      buf[k] = q;
-      q += al(sizes[k]);
-    }
-  }
-  double *d_cams = reinterpret_cast<double *>(buf[0]), *d_cams_n = reinterpret_cast<double *>(buf[1]);
-  double *d_pts = reinterpret_cast<double *>(buf[2]), *d_pts_n = reinterpret_cast<double *>(buf[3]);
-  int32_t *d_ov = reinterpret_cast<int32_t *>(buf[4]), *d_op = reinterpret_cast<int32_t *>(buf[5]);
-  double *d_uv = reinterpret_cast<double *>(buf[6]);
-  int32_t *d_pt_off = reinterpret_cast<int32_t *>(buf[7]), *d_pt_obs = reinterpret_cast<int32_t *>(buf[8]);
-  int32_t *d_cam_off = reinterpret_cast<int32_t *>(buf[9]), *d_cam_obs = reinterpret_cast<int32_t *>(buf[10]);
-  int32_t *d_slot = reinterpret_cast<int32_t *>(buf[11]), *d_cos = reinterpret_cast<int32_t *>(buf[12]);
-  int64_t *d_pair_off = reinterpret_cast<int64_t *>(buf[13]);
-  int32_t *d_ent = reinterpret_cast<int32_t *>(buf[14]);
-  double *d_r = reinterpret_cast<double *>(buf[15]), *d_jcs = reinterpret_cast<double *>(buf[16]);
-  double *d_Jp = reinterpret_cast<double *>(buf[17]), *d_W = reinterpret_cast<double *>(buf[18]);
-  double *d_Y = reinterpret_cast<double *>(buf[19]), *d_U = reinterpret_cast<double *>(buf[20]);
-  double *d_gc = reinterpret_cast<double *>(buf[21]), *d_dc = reinterpret_cast<double *>(buf[22]);
-  double *d_V = reinterpret_cast<double *>(buf[23]), *d_Vinv = reinterpret_cast<double *>(buf[24]);
-  double *d_gp = reinterpret_cast<double *>(buf[25]), *d_ppred = reinterpret_cast<double *>(buf[26]);
-  double *d_e = reinterpret_cast<double *>(buf[27]), *d_S = reinterpret_cast<double *>(buf[28]);
-  int32_t *d_flag = reinterpret_cast<int32_t *>(buf[29]);
-  double *d_sw = reinterpret_cast<double *>(buf[30]);
+  double *d_cams = b_cams.dev(), *d_cams_n = b_cams_n.dev();
+  double *d_pts = b_pts.dev(), *d_pts_n = b_pts_n.dev();
+  int32_t *d_ov = b_ov.dev(), *d_op = b_op.dev();
+  double *d_uv = b_uv.dev();
+  int32_t *d_pt_off = b_pt_off.dev(), *d_pt_obs = b_pt_obs.dev();
+  int32_t *d_cam_off = b_cam_off.dev(), *d_cam_obs = b_cam_obs.dev();
+  int32_t *d_slot = b_slot.dev(), *d_cos = b_cos.dev();
+  int64_t *d_pair_off = b_pair_off.dev();
+  int32_t *d_ent = b_ent.dev();
+  double *d_r = b_r.dev(), *d_jcs = b_jcs.dev(), *d_Jp = b_Jp.dev(), *d_W = b_W.dev();
+  double *d_Y = b_Y.dev(), *d_U = b_U.dev(), *d_gc = b_gc.dev(), *d_dc = b_dc.dev();
+  double *d_V = b_V.dev(), *d_Vinv = b_Vinv.dev(), *d_gp = b_gp.dev(), *d_ppred = b_ppred.dev();
+  double *d_e = b_e.dev(), *d_S = b_S.dev();
+  int32_t *d_flag = b_flag.dev();
+  double *d_sw = b_sw.dev();
   const double c2 = ROB ? f_scale * f_scale : 1.0, ic2 = 1.0 / c2;
   volatile double *rec = static_cast<volatile double *>(c->pinned);
 
@@ -1063,11 +1043,11 @@ int ba_run(rs_ctx *c, double *cams, int64_t nC, double *pts, int64_t nP, const i
   HIP_TRY(hipMemsetAsync(d_U, 0, F8 * DD * nC, s));
   HIP_TRY(hipMemsetAsync(d_gc, 0, F8 * D * nC, s));
   HIP_TRY(hipMemsetAsync(d_dc, 0, F8 * D * nC, s));
-  HIP_TRY(hipMemsetAsync(d_flag, 0, 256, s));
+  HIP_TRY(hipMemsetAsync(d_flag, 0, b_flag.bytes, s));
 
-  Marks mk{c};
-  if (c->ba_timing) {
-    for (double &v : c->ba_ms) v = 0.0;
+  BaMarks mk{c};
+  if (c->ba.on) {
+    for (double &v : c->ba.ms) v = 0.0;
     c->ba_trials = 0;
   }
   const int ni = static_cast<int>(n), nPi = static_cast<int>(nP), nCi = static_cast<int>(nC);
@@ -1081,14 +1061,14 @@ int ba_run(rs_ctx *c, double *cams, int64_t nC, double *pts, int64_t nP, const i
                        d_ppred, trial ? nPi : 0, d_dc, d_U, d_gc, trial ? nCi : 0, lam, d_flag,
                        serial, const_cast<double *>(rec));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(mk.mark(T_COST));
+    if (int e = mk.mark(T_COST)) return e;
     HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(mk.collect());
+    if (int e = mk.collect()) return e;
     if (rec[3] != serial) return fail(RS_EDEVICE, "bundle adjustment: status record not written");
     return RS_OK;
   };
 
-  HIP_TRY(mk.begin());
+  if ((st = mk.begin())) return st;
   st = cost_at(d_cams, d_pts, false, 0.0);
   if (st) return st;
   double cost = rec[0];
@@ -1098,7 +1078,7 @@ int ba_run(rs_ctx *c, double *cams, int64_t nC, double *pts, int64_t nP, const i
   int32_t it = 0, rejected = 0, status = 0;
   bool done = false;
   for (it = 1; it <= max_iter && !done; ++it) {
-    HIP_TRY(mk.begin());
+    if ((st = mk.begin())) return st;
     if constexpr (D == 12)
       hipLaunchKernelGGL(rsd::k_ba_linearize<ROB>, dim3(blocks(n, 256)), dim3(256), 0, s, d_cams,
                          d_pts, d_ov, d_op, d_uv, ni, d_r, d_jcs, d_Jp, d_W, loss, ic2);
@@ -1106,36 +1086,36 @@ int ba_run(rs_ctx *c, double *cams, int64_t nC, double *pts, int64_t nP, const i
       hipLaunchKernelGGL(rsd::k_ba_linearize_rigid<ROB>, dim3(blocks(n, 256)), dim3(256), 0, s,
                          d_cams, d_pts, d_ov, d_op, d_uv, ni, d_r, d_jcs, d_Jp, d_W, loss, ic2,
                          d_sw);
-    HIP_TRY(mk.mark(T_LIN));
+    if ((st = mk.mark(T_LIN))) return st;
     if (nf > 0) {
       hipLaunchKernelGGL(HIP_KERNEL_NAME(rsd::k_ba_camera<D, ROB && D == 6>), dim3(nf), dim3(NT), 0,
                          s, d_cos, d_cam_off, d_cam_obs, d_jcs, d_r, d_U, d_gc, d_sw);
-      HIP_TRY(mk.mark(T_CAM));
+      if ((st = mk.mark(T_CAM))) return st;
     }
     hipLaunchKernelGGL(rsd::k_ba_pointsum, dim3(blocks(pp, 256)), dim3(256), 0, s, d_pt_off,
                        d_pt_obs, nPi, d_Jp, d_r, d_V, d_gp);
-    HIP_TRY(mk.mark(T_PSUM));
+    if ((st = mk.mark(T_PSUM))) return st;
     for (;;) {
       hipLaunchKernelGGL(rsd::k_ba_point<D>, dim3(blocks(n, 256)), dim3(256), 0, s, d_op, d_pt_off,
                          d_pt_obs, ni, d_V, lam, d_W, d_Y, d_Vinv, d_flag);
-      HIP_TRY(mk.mark(T_POINT));
+      if ((st = mk.mark(T_POINT))) return st;
       if (nf > 0) {
         hipLaunchKernelGGL(rsd::k_ba_schur<D>, dim3(static_cast<unsigned>(npair)), dim3(NT), 0, s,
                            nf, d_pair_off, d_ent, d_Y, d_W, d_U, d_gc, d_gp, d_op, d_cos,
                            d_cam_off, d_cam_obs, lam, d_S, ld);
-        HIP_TRY(mk.mark(T_SCHUR));
+        if ((st = mk.mark(T_SCHUR))) return st;
         hipLaunchKernelGGL(HIP_KERNEL_NAME(rsd::k_ba_chol<D, BW>), dim3(1),
                            dim3(rsd::kBaCholThreads), 0, s, d_S, N, nreal, d_cos, d_dc, d_flag);
-        HIP_TRY(mk.mark(T_CHOL));
+        if ((st = mk.mark(T_CHOL))) return st;
       }
       const int64_t clanes = D == 12 ? 12 * nC : nC, lanes = nP > clanes ? nP : clanes;
       hipLaunchKernelGGL(rsd::k_ba_step<D>, dim3(blocks(lanes, 256)), dim3(256), 0, s, d_pt_off,
                          d_pt_obs, d_ov, nPi, nCi, d_slot, d_W, d_V, d_Vinv, d_gp, d_dc, lam,
                          d_cams, d_pts, d_cams_n, d_pts_n, d_ppred);
-      HIP_TRY(mk.mark(T_STEP));
+      if ((st = mk.mark(T_STEP))) return st;
       st = cost_at(d_cams_n, d_pts_n, true, lam);
       if (st) return st;
-      if (c->ba_timing) ++c->ba_trials;
+      if (c->ba.on) ++c->ba_trials;
       const double cost_n = rec[0], pred = rec[1];
       const bool failed = rec[2] != 0.0 || !std::isfinite(cost_n);
       if (!failed && cost_n < cost && pred > 0.0) {
@@ -1161,18 +1141,18 @@ int ba_run(rs_ctx *c, double *cams, int64_t nC, double *pts, int64_t nP, const i
         done = true;
         break;
       }
-      HIP_TRY(mk.begin());
+      if ((st = mk.begin())) return st;
     }
   }
   it = done ? it - 1 : max_iter;
 
   if constexpr (ROB) {
     if (weights) {
-      HIP_TRY(mk.begin());
+      if ((st = mk.begin())) return st;
       hipLaunchKernelGGL(rsd::k_ba_weights, dim3(blocks(n, 256)), dim3(256), 0, s, d_cams, d_pts,
                          d_ov, d_op, d_uv, ni, d_e, loss, ic2);
       HIP_TRY(hipGetLastError());
-      HIP_TRY(mk.mark(T_COST));
+      if ((st = mk.mark(T_COST))) return st;
       HIP_TRY(hipMemcpyAsync(weights, d_e, F8 * n, hipMemcpyDeviceToHost, s));
     }
   } else if (weights) {
@@ -1181,7 +1161,7 @@ int ba_run(rs_ctx *c, double *cams, int64_t nC, double *pts, int64_t nP, const i
   HIP_TRY(hipMemcpyAsync(cams, d_cams, F8 * 12 * nC, hipMemcpyDeviceToHost, s));
   if (nP > 0) HIP_TRY(hipMemcpyAsync(pts, d_pts, F8 * 3 * nP, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(mk.collect());
+  if ((st = mk.collect())) return st;
   info->cost_init = cost0;
   info->cost = cost;
   info->lambda = lam;

@@ -37,8 +37,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "common.h"
-#include "ctx.h"
+#include "host.h"
 
 namespace rsd {
 
@@ -464,36 +463,7 @@ __global__ __launch_bounds__(kCloudThreads) void k_cloud_attr(
 
 }  // namespace rsd
 
-using rs::fail;
-using rs::hip_fail;
-
-#define HIP_TRY(expr)                                 \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
-
-namespace {
-
-size_t al(size_t b) { return (b + 255) / 256 * 256; }
-
-int time_mark(rs_ctx *c, int k, hipStream_t s) {
-  if (c->cloud_timing) HIP_TRY(hipEventRecord(c->cloud_ev[k], s));
-  return RS_OK;
-}
-
-// slot `slot` = the time between events a and b of the call that just synchronised
-int time_read(rs_ctx *c, int slot, int a, int b) {
-  if (!c->cloud_timing) return RS_OK;
-  float ms = 0.0f;
-  HIP_TRY(hipEventElapsedTime(&ms, c->cloud_ev[a], c->cloud_ev[b]));
-  c->cloud_ms[slot] = ms;
-  return RS_OK;
-}
-
-unsigned blocks(int64_t n, int per) { return static_cast<unsigned>((n + per - 1) / per); }
-
-}  // namespace
+using rs::blocks;
 
 extern "C" int rs_cloud_attributes(rs_ctx *c, const double *cams, int64_t nC, const double *pts,
                                    int64_t nP, const int32_t *entry_point,
@@ -514,21 +484,17 @@ extern "C" int rs_cloud_attributes(rs_ctx *c, const double *cams, int64_t nC, co
   for (int64_t o = 0; o < nObs && m > 0; ++o)
     if (obs_view[o] < 0 || obs_view[o] >= nC) return fail(RS_EINVAL, "obs_view out of range");
 
-  const size_t D = sizeof(double), I = sizeof(int32_t);
   // [cams | pts | obs_color | off | entry_obs | obs_view] go up, [colors | normals] come down
-  const size_t sizes[] = {D * 12 * nC, D * 3 * nP,   D * 3 * nObs, I * (nP + 1),
-                          I * m,       I * nObs,     D * 3 * nP,   D * 3 * nP};
-  constexpr int kBufs = sizeof(sizes) / sizeof(sizes[0]);
-  size_t at[kBufs + 1] = {0};
-  for (int k = 0; k < kBufs; ++k) at[k + 1] = at[k] + al(sizes[k]);
+  rs::Layout L;
+  const auto b_cams = L.add<double>(12 * nC), b_pts = L.add<double>(3 * nP);
+  const auto b_color = L.add<double>(3 * nObs);
+  const auto b_off = L.add<int32_t>(nP + 1), b_eobs = L.add<int32_t>(m), b_oview = L.add<int32_t>(nObs);
+  const auto b_colors = L.add<double>(3 * nP), b_normals = L.add<double>(3 * nP);
   HIP_TRY(hipSetDevice(c->device));
-  int st = rs::ensure_scratch(c, at[kBufs] + 256);
+  int st = L.bind(c, 256, L.total() + 256);
   if (st) return st;
-  st = rs::ensure_pinned(c, at[kBufs] + 256);
-  if (st) return st;
-  char *h = static_cast<char *>(c->pinned), *d = static_cast<char *>(c->scratch);
-  int32_t *off = reinterpret_cast<int32_t *>(h + at[3]);
-  std::memset(off, 0, sizes[3]);
+  int32_t *off = b_off.host();
+  std::memset(off, 0, b_off.bytes);
   for (int64_t e = 0; e < m; ++e) {
     const int32_t j = entry_point[e];
     if (j < 0 || j >= nP) return fail(RS_EINVAL, "entry_point out of range");
@@ -539,34 +505,28 @@ extern "C" int rs_cloud_attributes(rs_ctx *c, const double *cams, int64_t nC, co
   }
   for (int64_t j = 0; j < nP; ++j) off[j + 1] += off[j];
   if (m > 0) {
-    std::memcpy(h + at[0], cams, sizes[0]);
-    std::memcpy(h + at[2], obs_color, sizes[2]);
-    std::memcpy(h + at[4], entry_obs, sizes[4]);
-    std::memcpy(h + at[5], obs_view, sizes[5]);
+    std::memcpy(b_cams.host(), cams, b_cams.bytes);
+    std::memcpy(b_color.host(), obs_color, b_color.bytes);
+    std::memcpy(b_eobs.host(), entry_obs, b_eobs.bytes);
+    std::memcpy(b_oview.host(), obs_view, b_oview.bytes);
   }
-  std::memcpy(h + at[1], pts, sizes[1]);
+  std::memcpy(b_pts.host(), pts, b_pts.bytes);
 
   hipStream_t s = c->stream;
-  HIP_TRY(hipMemcpyAsync(d, h, at[6], hipMemcpyHostToDevice, s));
-  st = time_mark(c, 0, s);
-  if (st) return st;
+  HIP_TRY(hipMemcpyAsync(L.dev(), L.host(), L.upto(b_colors), hipMemcpyHostToDevice, s));
+  if ((st = c->cloud.mark(0, s))) return st;
   hipLaunchKernelGGL(rsd::k_cloud_attr, dim3(blocks(nP, rsd::kCloudThreads)),
-                     dim3(rsd::kCloudThreads), 0, s, reinterpret_cast<const double *>(d + at[0]),
-                     reinterpret_cast<const double *>(d + at[1]),
-                     reinterpret_cast<const int32_t *>(d + at[3]),
-                     reinterpret_cast<const int32_t *>(d + at[4]),
-                     reinterpret_cast<const int32_t *>(d + at[5]),
-                     reinterpret_cast<const double *>(d + at[2]), nP,
-                     reinterpret_cast<double *>(d + at[6]), reinterpret_cast<double *>(d + at[7]));
+                     dim3(rsd::kCloudThreads), 0, s, b_cams.dev(), b_pts.dev(), b_off.dev(),
+                     b_eobs.dev(), b_oview.dev(), b_color.dev(), nP, b_colors.dev(),
+                     b_normals.dev());
   HIP_TRY(hipGetLastError());
-  st = time_mark(c, 1, s);
-  if (st) return st;
-  HIP_TRY(hipMemcpyAsync(h + at[6], d + at[6], at[kBufs] - at[6], hipMemcpyDeviceToHost, s));
+  if ((st = c->cloud.mark(1, s))) return st;
+  HIP_TRY(hipMemcpyAsync(b_colors.host(), b_colors.dev(), L.from(b_colors), hipMemcpyDeviceToHost,
+                         s));
   HIP_TRY(hipStreamSynchronize(s));
-  st = time_read(c, 4, 0, 1);
-  if (st) return st;
-  std::memcpy(colors, h + at[6], sizes[6]);
-  std::memcpy(normals, h + at[7], sizes[7]);
+  if ((st = c->cloud.read(4, 0, 1))) return st;
+  std::memcpy(colors, b_colors.host(), b_colors.bytes);
+  std::memcpy(normals, b_normals.host(), b_normals.bytes);
   return RS_OK;
 }
 
@@ -589,86 +549,86 @@ extern "C" int rs_cloud_normals(rs_ctx *c, const double *pts, int64_t n, double 
                                                     (n + rsd::kCloudThreads - 1) /
                                                         rsd::kCloudThreads));
   const int nchunks = static_cast<int>((cap + rsd::kCloudScanChunk - 1) / rsd::kCloudScanChunk);
-  const size_t D = sizeof(double), I = sizeof(int32_t), U = sizeof(unsigned long long);
+  using U64 = unsigned long long;
   // [pts | orient] go up, [normals | evals | count | stats] come down, the rest is the grid
-  const size_t sizes[] = {D * 3 * n, orient ? D * 3 * n : 0, D * 3 * n, D * 3 * n, I * n,
-                          U * 8,     U * n,                  I * n,     I * n,     U * cap,
-                          I * (cap + 1), I * cap,            D * 3 * nb, D * 3,
-                          I * (nchunks + 1)};
-  constexpr int kBufs = sizeof(sizes) / sizeof(sizes[0]);
-  size_t at[kBufs + 1] = {0};
-  for (int k = 0; k < kBufs; ++k) at[k + 1] = at[k] + al(sizes[k]);
+  rs::Layout L;
+  const auto b_pts = L.add<double>(3 * n), b_orient = L.add<double>(orient ? 3 * n : 0);
+  const auto b_normals = L.add<double>(3 * n), b_evals = L.add<double>(3 * n);
+  const auto b_count = L.add<int32_t>(n);
+  const auto b_stats = L.add<U64>(8);
+  const auto b_pkey = L.add<U64>(n);
+  const auto b_slot_of = L.add<int32_t>(n), b_cell_pts = L.add<int32_t>(n);
+  const auto b_keys = L.add<U64>(cap);
+  const auto b_cnt = L.add<int32_t>(cap + 1), b_fill = L.add<int32_t>(cap);
+  const auto b_part = L.add<double>(3 * nb), b_lo = L.add<double>(3);
+  const auto b_sums = L.add<int32_t>(nchunks + 1);
   HIP_TRY(hipSetDevice(c->device));
-  int st = rs::ensure_scratch(c, at[kBufs] + 256);
+  int st = L.bind(c, 256, L.upto(b_pkey) + 256);  // the pinned mirror ends with stats
   if (st) return st;
-  st = rs::ensure_pinned(c, at[6] + 256);
-  if (st) return st;
-  char *h = static_cast<char *>(c->pinned), *d = static_cast<char *>(c->scratch);
-  std::memcpy(h + at[0], pts, sizes[0]);
-  if (orient) std::memcpy(h + at[1], orient, sizes[1]);
+  std::memcpy(b_pts.host(), pts, b_pts.bytes);
+  if (orient) std::memcpy(b_orient.host(), orient, b_orient.bytes);
 
-  const double *d_pts = reinterpret_cast<const double *>(d + at[0]);
-  const double *d_orient = orient ? reinterpret_cast<const double *>(d + at[1]) : nullptr;
-  double *d_normals = reinterpret_cast<double *>(d + at[2]);
-  double *d_evals = reinterpret_cast<double *>(d + at[3]);
-  int32_t *d_count = reinterpret_cast<int32_t *>(d + at[4]);
-  double *d_part = reinterpret_cast<double *>(d + at[12]);
-  double *d_lo = reinterpret_cast<double *>(d + at[13]);
-  int32_t *d_sums = reinterpret_cast<int32_t *>(d + at[14]);
+  const double *d_pts = b_pts.dev();
+  const double *d_orient = orient ? b_orient.dev() : nullptr;
+  double *d_normals = b_normals.dev(), *d_evals = b_evals.dev();
+  int32_t *d_count = b_count.dev();
+  double *d_part = b_part.dev(), *d_lo = b_lo.dev();
+  int32_t *d_sums = b_sums.dev();
   rsd::CloudGrid G;
-  G.stats = reinterpret_cast<unsigned long long *>(d + at[5]);
-  G.pkey = reinterpret_cast<unsigned long long *>(d + at[6]);
-  G.slot_of = reinterpret_cast<int32_t *>(d + at[7]);
-  G.cell_pts = reinterpret_cast<int32_t *>(d + at[8]);
-  G.keys = reinterpret_cast<unsigned long long *>(d + at[9]);
-  G.cnt = reinterpret_cast<int32_t *>(d + at[10]);
-  G.fill = reinterpret_cast<int32_t *>(d + at[11]);
+  G.stats = b_stats.dev();
+  G.pkey = b_pkey.dev();
+  G.slot_of = b_slot_of.dev();
+  G.cell_pts = b_cell_pts.dev();
+  G.keys = b_keys.dev();
+  G.cnt = b_cnt.dev();
+  G.fill = b_fill.dev();
   G.mask = static_cast<unsigned>(cap - 1);
 
   hipStream_t s = c->stream;
   const dim3 blk(rsd::kCloudThreads);
-  HIP_TRY(hipMemcpyAsync(d, h, at[2], hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemsetAsync(d + at[5], 0, sizes[5], s));
-  HIP_TRY(hipMemsetAsync(d + at[9], 0xff, sizes[9], s));
-  HIP_TRY(hipMemsetAsync(d + at[10], 0, at[12] - at[10], s));
-  if ((st = time_mark(c, 0, s))) return st;
+  HIP_TRY(hipMemcpyAsync(L.dev(), L.host(), L.upto(b_normals), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(b_stats.dev(), 0, b_stats.bytes, s));
+  HIP_TRY(hipMemsetAsync(b_keys.dev(), 0xff, b_keys.bytes, s));
+  HIP_TRY(hipMemsetAsync(b_cnt.dev(), 0, L.span(b_cnt, b_part), s));  // cnt and fill
+  if ((st = c->cloud.mark(0, s))) return st;
   hipLaunchKernelGGL(rsd::k_cloud_min, dim3(nb), blk, 0, s, d_pts, n, d_part);
   hipLaunchKernelGGL(rsd::k_cloud_min, dim3(1), blk, 0, s, d_part, static_cast<int64_t>(nb),
                      d_lo);
   hipLaunchKernelGGL(rsd::k_cloud_key, dim3(blocks(n, rsd::kCloudThreads)), blk, 0, s, d_pts, n,
                      d_lo, radius, G, d_normals, d_evals, d_count);
-  if ((st = time_mark(c, 1, s))) return st;
+  if ((st = c->cloud.mark(1, s))) return st;
   const dim3 sblk(rsd::kCloudScanThreads);
   hipLaunchKernelGGL(rsd::k_cloud_scan_chunks, dim3(nchunks), sblk, 0, s, G.cnt, cap, d_sums);
   hipLaunchKernelGGL(rsd::k_cloud_scan, dim3(1), sblk, 0, s, d_sums,
                      static_cast<int64_t>(nchunks));
   hipLaunchKernelGGL(rsd::k_cloud_scan_add, dim3(nchunks), sblk, 0, s, G.cnt, cap, d_sums,
                      nchunks);
-  if ((st = time_mark(c, 2, s))) return st;
+  if ((st = c->cloud.mark(2, s))) return st;
   hipLaunchKernelGGL(rsd::k_cloud_scatter, dim3(blocks(n, rsd::kCloudThreads)), blk, 0, s, n, G);
   hipLaunchKernelGGL(rsd::k_cloud_sort, dim3(static_cast<unsigned>(cap / rsd::kCloudThreads)),
                      blk, 0, s, G);
-  if ((st = time_mark(c, 3, s))) return st;
+  if ((st = c->cloud.mark(3, s))) return st;
   hipLaunchKernelGGL(rsd::k_cloud_normals, dim3(blocks(n, rsd::kCloudWave)),
                      dim3(rsd::kCloudWave), 0, s, d_pts, d_orient, cap, G, radius * radius,
                      d_normals, d_evals, d_count);
   HIP_TRY(hipGetLastError());
-  if ((st = time_mark(c, 4, s))) return st;
-  HIP_TRY(hipMemcpyAsync(h + at[2], d + at[2], at[6] - at[2], hipMemcpyDeviceToHost, s));
+  if ((st = c->cloud.mark(4, s))) return st;
+  HIP_TRY(hipMemcpyAsync(b_normals.host(), b_normals.dev(), L.span(b_normals, b_pkey),
+                         hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   for (int k = 0; k < 4; ++k)
-    if ((st = time_read(c, k, k, k + 1))) return st;
+    if ((st = c->cloud.read(k, k, k + 1))) return st;
 
-  const unsigned long long *stats = reinterpret_cast<const unsigned long long *>(h + at[5]);
+  const U64 *stats = b_stats.host();
   if (stats[rsd::kStatFlags] & rsd::kFlagRange)
     return fail(RS_EINVAL,
                 "the cloud is too wide for this radius: (p - lo) / radius must stay below "
                 "2^21 = 2097152 on every axis (lo: the minimum corner of the finite points)");
   if (stats[rsd::kStatFlags] & rsd::kFlagProbe)
     return fail(RS_EDEVICE, "the cell table overflowed (a hash probe ran its whole capacity)");
-  std::memcpy(normals, h + at[2], sizes[2]);
-  std::memcpy(evals, h + at[3], sizes[3]);
-  std::memcpy(count, h + at[4], sizes[4]);
+  std::memcpy(normals, b_normals.host(), b_normals.bytes);
+  std::memcpy(evals, b_evals.host(), b_evals.bytes);
+  std::memcpy(count, b_count.host(), b_count.bytes);
   rs_cloud_info r = zero;
   r.cells_occupied = static_cast<int64_t>(stats[rsd::kStatOccupied]);
   r.largest_cell = static_cast<int64_t>(stats[rsd::kStatLargest]);
@@ -684,9 +644,8 @@ extern "C" int rs_cloud_normals(rs_ctx *c, const double *pts, int64_t n, double 
 extern "C" int rs_cloud_timing(rs_ctx *c, int32_t enable, double *ms) {
   if (!c || !ms) return fail(RS_EINVAL, "null pointer");
   HIP_TRY(hipSetDevice(c->device));
-  if (enable && !c->cloud_ev[0])
-    for (auto &e : c->cloud_ev) HIP_TRY(hipEventCreate(&e));
-  c->cloud_timing = enable ? 1 : 0;
-  for (int k = 0; k < RS_CLOUD_TIMING_SLOTS; ++k) ms[k] = c->cloud_ms[k];
+  const int st = c->cloud.enable(enable != 0);
+  if (st) return st;
+  c->cloud.copy_out(ms);
   return RS_OK;
 }

@@ -8,10 +8,7 @@
 
 #include <cstring>
 
-#include "common.h"
-#include "ctx.h"
-
-using rs::fail;
+#include "host.h"
 
 static int nccl_fail(ncclResult_t r, const char *what) {
   rs::set_error("%s: %s", what, ncclGetErrorString(r));

@@ -30,8 +30,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "common.h"
-#include "ctx.h"
+#include "host.h"
 
 namespace rsd {
 
@@ -223,31 +222,7 @@ __global__ __launch_bounds__(kDenseThreads) void k_dense_consistency(
 
 }  // namespace rsd
 
-using rs::fail;
-using rs::hip_fail;
-
-#define HIP_TRY(expr)                                 \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
-
 namespace {
-
-size_t al(size_t b) { return (b + 255) / 256 * 256; }
-
-int time_mark(rs_ctx *c, int k, hipStream_t s) {
-  if (c->dense_timing) HIP_TRY(hipEventRecord(c->dense_ev[k], s));
-  return RS_OK;
-}
-
-int time_read(rs_ctx *c, int slot) {
-  if (!c->dense_timing) return RS_OK;
-  float ms = 0.0f;
-  HIP_TRY(hipEventElapsedTime(&ms, c->dense_ev[0], c->dense_ev[1]));
-  c->dense_ms[slot] = ms;
-  return RS_OK;
-}
 
 bool all_finite(const double *v, int64_t n) {
   for (int64_t i = 0; i < n; ++i)
@@ -294,19 +269,20 @@ extern "C" int rs_dense_plane_sweep(rs_ctx *c, const uint8_t *ref, int64_t h, in
 
   const size_t hw = static_cast<size_t>(h * w);
   // [ref | src | depths] go up, [index | delta | score | nvalid | volume] come down
-  const size_t sizes[] = {hw,     hw * S, sizeof(double) * D, 4 * hw,
-                          4 * hw, 4 * hw, hw,                 volume ? 4 * hw * D : 0};
-  constexpr int kBufs = sizeof(sizes) / sizeof(sizes[0]);
-  size_t at[kBufs + 1] = {0};
-  for (int k = 0; k < kBufs; ++k) at[k + 1] = at[k] + al(sizes[k]);
+  rs::Layout L;
+  const auto b_ref = L.add<uint8_t>(hw), b_src = L.add<uint8_t>(hw * S);
+  const auto b_depths = L.add<double>(D);
+  const auto b_index = L.add<int32_t>(hw);
+  const auto b_delta = L.add<float>(hw), b_score = L.add<float>(hw);
+  const auto b_nvalid = L.add<uint8_t>(hw);
+  const auto b_volume = L.add<float>(volume ? hw * D : 0);
   HIP_TRY(hipSetDevice(c->device));
-  int st = rs::ensure_scratch(c, at[kBufs] + 256);
+  int st = L.bind(c);
   if (st) return st;
-  char *d = static_cast<char *>(c->scratch);
   hipStream_t s = c->stream;
-  HIP_TRY(hipMemcpyAsync(d + at[0], ref, sizes[0], hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + at[1], src, sizes[1], hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + at[2], depths, sizes[2], hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(b_ref.dev(), ref, b_ref.bytes, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(b_src.dev(), src, b_src.bytes, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(b_depths.dev(), depths, b_depths.bytes, hipMemcpyHostToDevice, s));
 
   rsd::DenseWarp W;
   std::memset(&W, 0, sizeof(W));
@@ -316,15 +292,13 @@ extern "C" int rs_dense_plane_sweep(rs_ctx *c, const uint8_t *ref, int64_t h, in
   const double thr = min_var * n * n;
   const dim3 grid(static_cast<unsigned>((w + rsd::kDenseTX - 1) / rsd::kDenseTX),
                   static_cast<unsigned>((h + rsd::kDenseTY - 1) / rsd::kDenseTY));
-  const uint8_t *d_ref = reinterpret_cast<const uint8_t *>(d + at[0]);
-  const uint8_t *d_src = reinterpret_cast<const uint8_t *>(d + at[1]);
-  const double *d_depths = reinterpret_cast<const double *>(d + at[2]);
-  int32_t *d_index = reinterpret_cast<int32_t *>(d + at[3]);
-  float *d_delta = reinterpret_cast<float *>(d + at[4]);
-  float *d_score = reinterpret_cast<float *>(d + at[5]);
-  uint8_t *d_nvalid = reinterpret_cast<uint8_t *>(d + at[6]);
-  float *d_volume = volume ? reinterpret_cast<float *>(d + at[7]) : nullptr;
-  if ((st = time_mark(c, 0, s))) return st;
+  const uint8_t *d_ref = b_ref.dev(), *d_src = b_src.dev();
+  const double *d_depths = b_depths.dev();
+  int32_t *d_index = b_index.dev();
+  float *d_delta = b_delta.dev(), *d_score = b_score.dev();
+  uint8_t *d_nvalid = b_nvalid.dev();
+  float *d_volume = volume ? b_volume.dev() : nullptr;
+  if ((st = c->dense.mark(0, s))) return st;
 #define RS_DENSE_LAUNCH(R)                                                                      \
   launch_sweep<R>(grid, s, d_ref, d_src, static_cast<int>(h), static_cast<int>(w), S, W,       \
                   d_depths, static_cast<int>(D), thr, d_index, d_delta, d_score, d_nvalid,     \
@@ -338,14 +312,14 @@ extern "C" int rs_dense_plane_sweep(rs_ctx *c, const uint8_t *ref, int64_t h, in
   }
 #undef RS_DENSE_LAUNCH
   HIP_TRY(hipGetLastError());
-  if ((st = time_mark(c, 1, s))) return st;
-  HIP_TRY(hipMemcpyAsync(index, d_index, sizes[3], hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(delta, d_delta, sizes[4], hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(score, d_score, sizes[5], hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(nvalid, d_nvalid, sizes[6], hipMemcpyDeviceToHost, s));
-  if (volume) HIP_TRY(hipMemcpyAsync(volume, d_volume, sizes[7], hipMemcpyDeviceToHost, s));
+  if ((st = c->dense.mark(1, s))) return st;
+  HIP_TRY(hipMemcpyAsync(index, d_index, b_index.bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(delta, d_delta, b_delta.bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(score, d_score, b_score.bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(nvalid, d_nvalid, b_nvalid.bytes, hipMemcpyDeviceToHost, s));
+  if (volume) HIP_TRY(hipMemcpyAsync(volume, d_volume, b_volume.bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  return time_read(c, 0);
+  return c->dense.read(0, 0, 1);
 }
 
 extern "C" int rs_dense_consistency(rs_ctx *c, const double *depth, int32_t V, int64_t h,
@@ -363,39 +337,33 @@ extern "C" int rs_dense_consistency(rs_ctx *c, const double *depth, int32_t V, i
     return fail(RS_EINVAL, "the cameras must be finite");
 
   const size_t n = static_cast<size_t>(V * h * w);
-  const size_t sizes[] = {sizeof(double) * n, sizeof(double) * 12 * V, sizeof(double) * 9 * V, n};
-  constexpr int kBufs = sizeof(sizes) / sizeof(sizes[0]);
-  size_t at[kBufs + 1] = {0};
-  for (int k = 0; k < kBufs; ++k) at[k + 1] = at[k] + al(sizes[k]);
+  rs::Layout L;  // [depth | P | Minv] go up, [count] comes down
+  const auto b_depth = L.add<double>(n), b_P = L.add<double>(12 * V), b_Minv = L.add<double>(9 * V);
+  const auto b_count = L.add<uint8_t>(n);
   HIP_TRY(hipSetDevice(c->device));
-  int st = rs::ensure_scratch(c, at[kBufs] + 256);
+  int st = L.bind(c);
   if (st) return st;
-  char *d = static_cast<char *>(c->scratch);
   hipStream_t s = c->stream;
-  HIP_TRY(hipMemcpyAsync(d + at[0], depth, sizes[0], hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + at[1], P, sizes[1], hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + at[2], Minv, sizes[2], hipMemcpyHostToDevice, s));
-  if ((st = time_mark(c, 0, s))) return st;
+  HIP_TRY(hipMemcpyAsync(b_depth.dev(), depth, b_depth.bytes, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(b_P.dev(), P, b_P.bytes, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(b_Minv.dev(), Minv, b_Minv.bytes, hipMemcpyHostToDevice, s));
+  if ((st = c->dense.mark(0, s))) return st;
   hipLaunchKernelGGL(rsd::k_dense_consistency,
                      dim3(static_cast<unsigned>((n + rsd::kDenseThreads - 1) / rsd::kDenseThreads)),
-                     dim3(rsd::kDenseThreads), 0, s, reinterpret_cast<const double *>(d + at[0]),
-                     V, static_cast<int>(h), static_cast<int>(w),
-                     reinterpret_cast<const double *>(d + at[1]),
-                     reinterpret_cast<const double *>(d + at[2]), rel_tol,
-                     reinterpret_cast<uint8_t *>(d + at[3]));
+                     dim3(rsd::kDenseThreads), 0, s, b_depth.dev(), V, static_cast<int>(h),
+                     static_cast<int>(w), b_P.dev(), b_Minv.dev(), rel_tol, b_count.dev());
   HIP_TRY(hipGetLastError());
-  if ((st = time_mark(c, 1, s))) return st;
-  HIP_TRY(hipMemcpyAsync(count, d + at[3], sizes[3], hipMemcpyDeviceToHost, s));
+  if ((st = c->dense.mark(1, s))) return st;
+  HIP_TRY(hipMemcpyAsync(count, b_count.dev(), b_count.bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  return time_read(c, 1);
+  return c->dense.read(1, 0, 1);
 }
 
 extern "C" int rs_dense_timing(rs_ctx *c, int32_t enable, double *ms) {
   if (!c || !ms) return fail(RS_EINVAL, "null pointer");
   HIP_TRY(hipSetDevice(c->device));
-  if (enable && !c->dense_ev[0])
-    for (auto &e : c->dense_ev) HIP_TRY(hipEventCreate(&e));
-  c->dense_timing = enable ? 1 : 0;
-  for (int k = 0; k < RS_DENSE_TIMING_SLOTS; ++k) ms[k] = c->dense_ms[k];
+  const int st = c->dense.enable(enable != 0);
+  if (st) return st;
+  c->dense.copy_out(ms);
   return RS_OK;
 }

@@ -41,8 +41,7 @@
 #include <cstring>
 #include <vector>
 
-#include "common.h"
-#include "ctx.h"
+#include "host.h"
 #include "device_math.h"
 #include "f8_kernels.h"
 #include "twoview_math.h"
@@ -1112,16 +1111,6 @@ __device__ __forceinline__ void e5_inliers_body(const Pt *__restrict__ pts, int 
 }  // namespace rsd
 
 // ------------------------------------------------------------------------------------------
-using rs::fail;
-using rs::hip_fail;
-
-#define HIP_TRY(expr)                                 \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
-
-static size_t e5_align(size_t b) { return (b + 255) / 256 * 256; }
 constexpr int kE5CountWaves = 6144;  // resident waves of k_f8_count32q (as the F-RANSAC plan)
 // sweeps of the root finder's first phase (0: one phase).  Measured at C2 (20 000 samples,
 // profiles/r04b_e5_split_ab.txt, two passes): one phase 0.440 / 0.446 ms per E-RANSAC run;
@@ -1129,12 +1118,17 @@ constexpr int kE5CountWaves = 6144;  // resident waves of k_f8_count32q (as the 
 // second phase's set-up (B rows, polynomial, start state) costs more than the drained sweeps
 constexpr int kE5SplitDefault = 0;
 
-// bytes of the three solve kernels' work buffers for S samples: the 10 x 20 system, null
-// basis and B rows (296 doubles), Gauss-Jordan flags, the deferred list + count and the
-// deferred rows' root state (48 doubles) of the two-phase root finder
-static size_t e5_work_bytes(int64_t S) {
-  return e5_align(sizeof(double) * 296 * static_cast<size_t>(S)) + e5_align(sizeof(int) * S) +
-         e5_align(sizeof(int) * (S + 1)) + e5_align(sizeof(double) * 48 * static_cast<size_t>(S));
+// the three solve kernels' work buffers for S samples, added to the call's layout: the 10 x 20
+// system, null basis and B rows (296 doubles), Gauss-Jordan flags, the deferred count + list and
+// the deferred rows' root state (48 doubles) of the two-phase root finder
+struct E5Work {
+  rs::Layout::Buf<double> sys;
+  rs::Layout::Buf<int> ok, defer;
+  rs::Layout::Buf<double> zst;
+};
+static E5Work e5_work(rs::Layout &L, int64_t S) {
+  const size_t n = static_cast<size_t>(S);
+  return {L.add<double>(296 * n), L.add<int>(n), L.add<int>(n + 1), L.add<double>(48 * n)};
 }
 
 // sweeps before the root finder's rows still moving are repacked (RSAMD_E5_SPLIT; 0: one phase)
@@ -1147,19 +1141,16 @@ static int e5_split() {
 }
 
 // the solve (k_e5_build, k_e5_gj, k_e5_roots) into a.Esoa / a.Fsoa, work buffers from `work`
-static int launch_e5_solve(rsd::E5Args &a, char *work, hipStream_t s) {
+static int launch_e5_solve(rsd::E5Args &a, const E5Work &work, hipStream_t s) {
   const int64_t S = a.S;
   a.ldw = S;
-  a.Mg = reinterpret_cast<double *>(work);
+  a.Mg = work.sys.dev();
   a.Bas = a.Mg + 200 * S;
   a.Bg = a.Bas + 36 * S;
-  char *w2 = work + e5_align(sizeof(double) * 296 * static_cast<size_t>(S));
-  a.okg = reinterpret_cast<int *>(w2);
-  w2 += e5_align(sizeof(int) * S);
-  a.defer_n = reinterpret_cast<int *>(w2);
+  a.okg = work.ok.dev();
+  a.defer_n = work.defer.dev();
   a.defer_list = a.defer_n + 1;
-  w2 += e5_align(sizeof(int) * (S + 1));
-  a.zst = reinterpret_cast<double *>(w2);
+  a.zst = work.zst.dev();
   a.split = e5_split();
   hipLaunchKernelGGL(rsd::k_e5_build, dim3((S + 63) / 64), dim3(64), 0, s, a);
   HIP_TRY(hipGetLastError());
@@ -1212,15 +1203,16 @@ extern "C" int rs_e5_solve(rs_ctx *c, const double *y1, const double *y2, int64_
     hp[i] = rsd::Pt{y1[3 * i] / y1[3 * i + 2], y1[3 * i + 1] / y1[3 * i + 2],
                     y2[3 * i] / y2[3 * i + 2], y2[3 * i + 1] / y2[3 * i + 2]};
   }
-  const size_t bp = e5_align(sizeof(rsd::Pt) * m), bE = e5_align(sizeof(double) * 9 * ld),
-               bn = e5_align(sizeof(int) * S);
-  int st = rs::ensure_scratch(c, bp + bE + bn + e5_work_bytes(S));
+  rs::Layout L;
+  const auto b_p = L.add<rsd::Pt>(m);
+  const auto b_E = L.add<double>(9 * ld);
+  const auto b_n = L.add<int>(S);
+  const E5Work work = e5_work(L, S);
+  int st = L.bind(c, 0);
   if (st) return st;
-  char *base = static_cast<char *>(c->scratch);
-  auto *dp = reinterpret_cast<rsd::Pt *>(base);
-  auto *dE = reinterpret_cast<double *>(base + bp);
-  auto *dn = reinterpret_cast<int *>(base + bp + bE);
-  char *work = base + bp + bE + bn;
+  auto *dp = b_p.dev();
+  auto *dE = b_E.dev();
+  auto *dn = b_n.dev();
   hipStream_t s = c->stream;
   HIP_TRY(hipMemcpyAsync(dp, hp.data(), sizeof(rsd::Pt) * m, hipMemcpyHostToDevice, s));
   rsd::E5Args a{};
@@ -1263,42 +1255,36 @@ extern "C" int rs_e5_ransac(rs_ctx *c, const double *p1, const double *p2, int64
     }
   HIP_TRY(hipSetDevice(c->device));
   const int64_t H = rsd::kE5Sol * S, ld = (H + 63) / 64 * 64;
-  const size_t bin = e5_align(sizeof(double) * 2 * n), bp = e5_align(sizeof(rsd::Pt) * n);
-  const size_t bE = e5_align(sizeof(double) * 9 * ld), bc = e5_align(sizeof(int) * ld);
-  const size_t br = e5_align(sizeof(rsd::E5DevResult) + sizeof(int64_t) * n);
-  const size_t bnorm = e5_align(sizeof(double) * ld);
-  const size_t bpq = e5_align(sizeof(float) * 4 * ((n + 7) / 8 * 8));
-  const size_t bF32 = e5_align(sizeof(float) * 9 * ld), bG4 = e5_align(sizeof(float4) * ld);
-  int st = rs::ensure_scratch(c, 2 * bin + bp + 3 * bE + bc + br + bnorm + 256 + bpq + bF32 + bG4 +
-                                     2 * e5_align(sizeof(int) * ld) + 2 * e5_align(sizeof(int) * S) +
-                                     e5_align(sizeof(int) * (ld / 64 + 1)) + e5_work_bytes(S));
-  if (st) return st;
-  char *ptr = static_cast<char *>(c->scratch);
-  auto take = [&ptr](size_t b) {
-    char *q = ptr;
-    ptr += b;
-    return q;
-  };
-  double *d1 = reinterpret_cast<double *>(take(bin));
-  double *d2 = reinterpret_cast<double *>(take(bin));
-  auto *dp = reinterpret_cast<rsd::Pt *>(take(bp));
-  double *dE = reinterpret_cast<double *>(take(bE));
-  double *dF = reinterpret_cast<double *>(take(bE));
-  int *dc = reinterpret_cast<int *>(take(bc));
-  auto *dr = reinterpret_cast<rsd::E5DevResult *>(take(br));
-  double *dnorm = reinterpret_cast<double *>(take(bnorm));
-  int *dcmax = reinterpret_cast<int *>(take(256));  // c* (0), candidates (1), real solutions (2)
-  int *dcand = reinterpret_cast<int *>(take(e5_align(sizeof(int) * ld)));
-  int *dnsol = reinterpret_cast<int *>(take(e5_align(sizeof(int) * S)));
-  int *dslot = reinterpret_cast<int *>(take(e5_align(sizeof(int) * ld)));
-  int *doff = reinterpret_cast<int *>(take(e5_align(sizeof(int) * S)));  // workgroup bases
-  int *dgdone = reinterpret_cast<int *>(take(e5_align(sizeof(int) * (ld / 64 + 1))));  // per group
+  rs::Layout L;
+  const auto b_1 = L.add<double>(2 * n), b_2 = L.add<double>(2 * n);
+  const auto b_p = L.add<rsd::Pt>(n);
+  const auto b_E = L.add<double>(9 * ld), b_F = L.add<double>(9 * ld);
+  const auto b_c = L.add<int>(ld);
+  const auto b_r = L.add_bytes<rsd::E5DevResult>(sizeof(rsd::E5DevResult) + sizeof(int64_t) * n);
+  const auto b_norm = L.add<double>(ld);
+  const auto b_cmax = L.add<int>(64);  // c* (0), candidates (1), real solutions (2)
+  const auto b_cand = L.add<int>(ld), b_nsol = L.add<int>(S), b_slot = L.add<int>(ld);
+  const auto b_off = L.add<int>(S);             // workgroup bases
+  const auto b_gdone = L.add<int>(ld / 64 + 1);  // per group
   // fp32 counting: point-pair layout, dense float64 / fp32 models, decision constants
-  auto *dpq = reinterpret_cast<float4 *>(take(bpq));
-  double *dFd = reinterpret_cast<double *>(take(bE));
-  float *dF32 = reinterpret_cast<float *>(take(bF32));
-  auto *dG4 = reinterpret_cast<float4 *>(take(bG4));
-  char *work = take(e5_work_bytes(S));
+  const auto b_pq = L.add<float4>((n + 7) / 8 * 8);
+  const auto b_Fd = L.add<double>(9 * ld);
+  const auto b_F32 = L.add<float>(9 * ld);
+  const auto b_G4 = L.add<float4>(ld);
+  const E5Work work = e5_work(L, S);
+  int st = L.bind(c, 0);
+  if (st) return st;
+  double *d1 = b_1.dev(), *d2 = b_2.dev(), *dE = b_E.dev(), *dF = b_F.dev();
+  auto *dp = b_p.dev();
+  int *dc = b_c.dev();
+  auto *dr = b_r.dev();
+  double *dnorm = b_norm.dev();
+  int *dcmax = b_cmax.dev(), *dcand = b_cand.dev(), *dnsol = b_nsol.dev(), *dslot = b_slot.dev();
+  int *doff = b_off.dev(), *dgdone = b_gdone.dev();
+  auto *dpq = b_pq.dev();
+  double *dFd = b_Fd.dev();
+  float *dF32 = b_F32.dev();
+  auto *dG4 = b_G4.dev();
   hipStream_t s = c->stream;
   HIP_TRY(hipMemcpyAsync(d1, p1, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(d2, p2, sizeof(double) * 2 * n, hipMemcpyHostToDevice, s));

@@ -44,13 +44,9 @@
 #include <cstring>
 #include <vector>
 
-#include "common.h"
-#include "ctx.h"
+#include "host.h"
 #include "device_math.h"
 #include "f8_kernels.h"
-
-using rs::fail;
-using rs::hip_fail;
 
 namespace {
 
@@ -172,12 +168,6 @@ struct rs_f8_plan {
 
   const RunBufs &last() const { return buf[(runs - 1) % kBufs]; }
 };
-
-#define HIP_TRY(expr)                                   \
-  do {                                                  \
-    hipError_t e_ = (expr);                             \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr);   \
-  } while (0)
 
 static void plan_free(rs_f8_plan *p) {
   (void)hipFree(p->d_p12);

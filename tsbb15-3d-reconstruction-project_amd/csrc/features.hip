@@ -30,8 +30,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "common.h"
-#include "ctx.h"
+#include "host.h"
 
 namespace rsd {
 
@@ -462,33 +461,7 @@ __global__ __launch_bounds__(256) void k_match_argmin(const double *row_val, con
 
 }  // namespace rsd
 
-using rs::fail;
-using rs::hip_fail;
-
-#define HIP_TRY(expr)                                 \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
-
 namespace {
-
-size_t al(size_t b) { return (b + 255) / 256 * 256; }
-
-// rs_features_timing: an event before the first and after the last kernel of a call, read after
-// the call's synchronise.
-int time_mark(rs_ctx *c, int k, hipStream_t s) {
-  if (c->feat_timing) HIP_TRY(hipEventRecord(c->feat_ev[k], s));
-  return RS_OK;
-}
-
-int time_read(rs_ctx *c) {
-  if (!c->feat_timing) return RS_OK;
-  float ms = 0.0f;
-  HIP_TRY(hipEventElapsedTime(&ms, c->feat_ev[0], c->feat_ev[1]));
-  c->feat_ms = ms;
-  return RS_OK;
-}
 
 bool image_size_ok(int64_t h, int64_t w) {
   return h >= 1 && w >= 1 && h <= RS_IMAGE_MAX_SIDE && w <= RS_IMAGE_MAX_SIDE;
@@ -513,11 +486,13 @@ extern "C" int rs_harris(rs_ctx *c, const uint8_t *image, int64_t h, int64_t w, 
 
   const size_t npx = static_cast<size_t>(h) * w;
   HIP_TRY(hipSetDevice(c->device));
-  int st = rs::ensure_scratch(c, al(npx) + al(npx * sizeof(float)));
+  rs::Layout L;
+  const auto b_img = L.add<uint8_t>(npx);
+  const auto b_out = L.add<float>(npx);
+  int st = L.bind(c, 0);
   if (st) return st;
-  char *d = static_cast<char *>(c->scratch);
-  A.img = reinterpret_cast<const uint8_t *>(d);
-  A.out = reinterpret_cast<float *>(d + al(npx));
+  A.img = b_img.dev();
+  A.out = b_out.dev();
   A.h = static_cast<int>(h);
   A.w = static_cast<int>(w);
   A.bs = block_size;
@@ -530,18 +505,16 @@ extern "C" int rs_harris(rs_ctx *c, const uint8_t *image, int64_t h, int64_t w, 
   const int IW = rsd::kHarrisTW + 2 * A.R, IH = rsd::kHarrisTH + 2 * A.R;
   const size_t lds = sizeof(int32_t) * 2 * DW * DH + static_cast<size_t>(IW) * IH;
   hipStream_t s_ = c->stream;
-  HIP_TRY(hipMemcpyAsync(d, image, npx, hipMemcpyHostToDevice, s_));
+  HIP_TRY(hipMemcpyAsync(b_img.dev(), image, npx, hipMemcpyHostToDevice, s_));
   const dim3 grid((A.w + rsd::kHarrisTW - 1) / rsd::kHarrisTW,
                   (A.h + rsd::kHarrisTH - 1) / rsd::kHarrisTH);
-  st = time_mark(c, 0, s_);
-  if (st) return st;
+  if ((st = c->feat.mark(0, s_))) return st;
   hipLaunchKernelGGL(rsd::k_harris, grid, dim3(rsd::kHarrisThreads), lds, s_, A);
   HIP_TRY(hipGetLastError());
-  st = time_mark(c, 1, s_);
-  if (st) return st;
+  if ((st = c->feat.mark(1, s_))) return st;
   HIP_TRY(hipMemcpyAsync(out, A.out, npx * sizeof(float), hipMemcpyDeviceToHost, s_));
   HIP_TRY(hipStreamSynchronize(s_));
-  return time_read(c);
+  return c->feat.read(0, 0, 1);
 }
 
 extern "C" int rs_non_max_suppression(rs_ctx *c, const float *image, int64_t h, int64_t w,
@@ -551,25 +524,25 @@ extern "C" int rs_non_max_suppression(rs_ctx *c, const float *image, int64_t h, 
   if (!image_size_ok(h, w)) return fail(RS_EINVAL, "bad image size");
   const size_t bytes = static_cast<size_t>(h) * w * sizeof(float);
   HIP_TRY(hipSetDevice(c->device));
-  int st = rs::ensure_scratch(c, 2 * al(bytes));
+  const size_t npx = static_cast<size_t>(h) * w;
+  rs::Layout L;
+  const auto b_in = L.add<float>(npx), b_out = L.add<float>(npx);
+  int st = L.bind(c, 0);
   if (st) return st;
-  char *d = static_cast<char *>(c->scratch);
-  float *d_in = reinterpret_cast<float *>(d), *d_out = reinterpret_cast<float *>(d + al(bytes));
+  float *d_in = b_in.dev(), *d_out = b_out.dev();
   hipStream_t s = c->stream;
   HIP_TRY(hipMemcpyAsync(d_in, image, bytes, hipMemcpyHostToDevice, s));
   // a window wider than the image leaves no valid position: m is capped so that y + m stays small
   const int m = static_cast<int>(std::min<int64_t>((window_size - 1) / 2, RS_IMAGE_MAX_SIDE));
   const dim3 grid(static_cast<unsigned>((w + 31) / 32), static_cast<unsigned>((h + 7) / 8));
-  st = time_mark(c, 0, s);
-  if (st) return st;
+  if ((st = c->feat.mark(0, s))) return st;
   hipLaunchKernelGGL(rsd::k_nms, grid, dim3(256), 0, s, d_in, d_out, static_cast<int>(h),
                      static_cast<int>(w), m);
   HIP_TRY(hipGetLastError());
-  st = time_mark(c, 1, s);
-  if (st) return st;
+  if ((st = c->feat.mark(1, s))) return st;
   HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  return time_read(c);
+  return c->feat.read(0, 0, 1);
 }
 
 extern "C" int rs_corners(rs_ctx *c, const float *H, int64_t h, int64_t w, double rel, int32_t *xy,
@@ -581,34 +554,30 @@ extern "C" int rs_corners(rs_ctx *c, const float *H, int64_t h, int64_t w, doubl
   const int64_t n = h * w;   // <= 2^30
   const int nb = static_cast<int>((n + rsd::kCornerChunk - 1) / rsd::kCornerChunk);
   const int nparts = std::min(nb, rsd::kCornerMaxBlocks);
-  const size_t bH = al(n * sizeof(float)), bP = al(sizeof(float) * rsd::kCornerMaxBlocks),
-               bC = al(sizeof(int32_t) * (nb + 1)), bX = al(n * sizeof(int32_t));
+  rs::Layout L;
+  const auto b_H = L.add<float>(n), b_part = L.add<float>(rsd::kCornerMaxBlocks);
+  const auto b_cnt = L.add<int32_t>(nb + 1);
+  const auto b_xs = L.add<int32_t>(n), b_ys = L.add<int32_t>(n);
   HIP_TRY(hipSetDevice(c->device));
-  int st = rs::ensure_scratch(c, bH + bP + bC + 2 * bX);
+  int st = L.bind(c, 0);
   if (st) return st;
-  char *d = static_cast<char *>(c->scratch);
-  float *d_H = reinterpret_cast<float *>(d), *d_part = reinterpret_cast<float *>(d + bH);
-  int32_t *d_cnt = reinterpret_cast<int32_t *>(d + bH + bP);
-  int32_t *d_xs = reinterpret_cast<int32_t *>(d + bH + bP + bC);
-  int32_t *d_ys = reinterpret_cast<int32_t *>(d + bH + bP + bC + bX);
+  float *d_H = b_H.dev(), *d_part = b_part.dev();
+  int32_t *d_cnt = b_cnt.dev(), *d_xs = b_xs.dev(), *d_ys = b_ys.dev();
   hipStream_t s = c->stream;
   HIP_TRY(hipMemcpyAsync(d_H, H, n * sizeof(float), hipMemcpyHostToDevice, s));
   const dim3 blk(rsd::kCornerThreads);
-  st = time_mark(c, 0, s);
-  if (st) return st;
+  if ((st = c->feat.mark(0, s))) return st;
   hipLaunchKernelGGL(rsd::k_corner_max, dim3(nparts), blk, 0, s, d_H, n, d_part);
   hipLaunchKernelGGL(rsd::k_corner_count, dim3(nb), blk, 0, s, d_H, n, d_part, nparts, rel, d_cnt);
   hipLaunchKernelGGL(rsd::k_corner_scan, dim3(1), blk, 0, s, d_cnt, nb);
   hipLaunchKernelGGL(rsd::k_corner_write, dim3(nb), blk, 0, s, d_H, n, static_cast<int>(w), d_part,
                      nparts, rel, d_cnt, d_xs, d_ys);
   HIP_TRY(hipGetLastError());
-  st = time_mark(c, 1, s);
-  if (st) return st;
+  if ((st = c->feat.mark(1, s))) return st;
   int32_t total = 0;
   HIP_TRY(hipMemcpyAsync(&total, d_cnt + nb, sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  st = time_read(c);
-  if (st) return st;
+  if ((st = c->feat.read(0, 0, 1))) return st;
   *count = total;
   if (total > cap) return fail(RS_EINVAL, "more corners than the capacity of xy");
   if (total > 0) {
@@ -652,26 +621,27 @@ int match_run(rs_ctx *c, const T *img1, int64_t h1, int64_t w1, const int32_t *x
 
   const int nt1 = static_cast<int>((n1 + rsd::kMatchTile - 1) / rsd::kMatchTile);
   const int nt2 = static_cast<int>((n2 + rsd::kMatchTile - 1) / rsd::kMatchTile);
-  const size_t D = sizeof(double), I = sizeof(int32_t);
-  const size_t sizes[] = {sizeof(T) * h1 * w1, sizeof(T) * h2 * w2, I * 2 * n1, I * 2 * n2,
-                          D * nt2 * n1,        D * nt1 * n2,        I * nt2 * n1, I * nt1 * n2,
-                          I * n1,              I * n2,              D * n1};
-  constexpr int kBufs = sizeof(sizes) / sizeof(sizes[0]);
-  size_t at[kBufs + 1] = {0};
-  for (int k = 0; k < kBufs; ++k) at[k + 1] = at[k] + al(sizes[k]);
+  const size_t D = sizeof(double);
+  rs::Layout L;
+  const auto b_img1 = L.add<T>(h1 * w1), b_img2 = L.add<T>(h2 * w2);
+  const auto b_xy1 = L.add<int32_t>(2 * n1), b_xy2 = L.add<int32_t>(2 * n2);
+  // the partial minima per tile row / column, then the results
+  const auto b_row_val = L.add<double>(nt2 * n1), b_col_val = L.add<double>(nt1 * n2);
+  const auto b_row_idx = L.add<int32_t>(nt2 * n1), b_col_idx = L.add<int32_t>(nt1 * n2);
+  const auto b_rmin = L.add<int32_t>(n1), b_cmin = L.add<int32_t>(n2);
+  const auto b_rval = L.add<double>(n1);
   HIP_TRY(hipSetDevice(c->device));
-  st = rs::ensure_scratch(c, at[kBufs]);
+  st = L.bind(c, 0);
   if (st) return st;
-  char *d = static_cast<char *>(c->scratch);
   double *d_M = nullptr;   // the matrix is not kept in the grow-only scratch
   if (M) HIP_TRY(hipMalloc(&d_M, D * n1 * n2));
 
   hipStream_t s = c->stream;
   rsd::MatchArgs<T> A;
-  A.img1 = reinterpret_cast<const T *>(d + at[0]);
-  A.img2 = reinterpret_cast<const T *>(d + at[1]);
-  A.xy1 = reinterpret_cast<const int32_t *>(d + at[2]);
-  A.xy2 = reinterpret_cast<const int32_t *>(d + at[3]);
+  A.img1 = b_img1.dev();
+  A.img2 = b_img2.dev();
+  A.xy1 = b_xy1.dev();
+  A.xy2 = b_xy2.dev();
   A.w1 = static_cast<int>(w1);
   A.w2 = static_cast<int>(w2);
   A.n1 = static_cast<int>(n1);
@@ -679,19 +649,19 @@ int match_run(rs_ctx *c, const T *img1, int64_t h1, int64_t w1, const int32_t *x
   A.roi = roi_size;
   A.wrap = wrap ? 1 : 0;
   A.M = d_M;
-  A.row_val = reinterpret_cast<double *>(d + at[4]);
-  A.col_val = reinterpret_cast<double *>(d + at[5]);
-  A.row_idx = reinterpret_cast<int32_t *>(d + at[6]);
-  A.col_idx = reinterpret_cast<int32_t *>(d + at[7]);
-  int32_t *d_rmin = reinterpret_cast<int32_t *>(d + at[8]);
-  int32_t *d_cmin = reinterpret_cast<int32_t *>(d + at[9]);
-  double *d_rval = reinterpret_cast<double *>(d + at[10]);
+  A.row_val = b_row_val.dev();
+  A.col_val = b_col_val.dev();
+  A.row_idx = b_row_idx.dev();
+  A.col_idx = b_col_idx.dev();
+  int32_t *d_rmin = b_rmin.dev(), *d_cmin = b_cmin.dev();
+  double *d_rval = b_rval.dev();
 
-  hipError_t e = hipMemcpyAsync(d + at[0], img1, sizes[0], hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d + at[1], img2, sizes[1], hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d + at[2], xy1, sizes[2], hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d + at[3], xy2, sizes[3], hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && c->feat_timing) e = hipEventRecord(c->feat_ev[0], s);
+  // one error path, so that the matrix is freed: the timer's events are recorded by hand
+  hipError_t e = hipMemcpyAsync(b_img1.dev(), img1, b_img1.bytes, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(b_img2.dev(), img2, b_img2.bytes, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(b_xy1.dev(), xy1, b_xy1.bytes, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(b_xy2.dev(), xy2, b_xy2.bytes, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && c->feat.on) e = hipEventRecord(c->feat.ev[0], s);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(rsd::k_match<T>, dim3(nt2, nt1), dim3(rsd::kMatchThreads), 0, s, A);
     hipLaunchKernelGGL(rsd::k_match_argmin, dim3(static_cast<unsigned>((n1 + n2 + 255) / 256)),
@@ -699,15 +669,15 @@ int match_run(rs_ctx *c, const T *img1, int64_t h1, int64_t w1, const int32_t *x
                        nt1, nt2, d_rmin, d_rval, d_cmin);
     e = hipGetLastError();
   }
-  if (e == hipSuccess && c->feat_timing) e = hipEventRecord(c->feat_ev[1], s);
-  if (e == hipSuccess) e = hipMemcpyAsync(row_min, d_rmin, sizes[8], hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(col_min, d_cmin, sizes[9], hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(row_val, d_rval, sizes[10], hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && c->feat.on) e = hipEventRecord(c->feat.ev[1], s);
+  if (e == hipSuccess) e = hipMemcpyAsync(row_min, d_rmin, b_rmin.bytes, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(col_min, d_cmin, b_cmin.bytes, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(row_val, d_rval, b_rval.bytes, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess && M) e = hipMemcpyAsync(M, d_M, D * n1 * n2, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (d_M) (void)hipFree(d_M);
   if (e != hipSuccess) return hip_fail(e, "rs_match_rois");
-  return time_read(c);
+  return c->feat.read(0, 0, 1);
 }
 
 }  // namespace
@@ -729,12 +699,13 @@ extern "C" int rs_match_rois_f64(rs_ctx *c, const double *img1, int64_t h1, int6
                            col_min, row_val, M);
 }
 
+// An event before the first and after the last kernel of a call, read after the call's
+// synchronise.
 extern "C" int rs_features_timing(rs_ctx *c, int32_t enable, double *ms) {
   if (!c || !ms) return fail(RS_EINVAL, "null pointer");
   HIP_TRY(hipSetDevice(c->device));
-  if (enable && !c->feat_ev[0])
-    for (auto &e : c->feat_ev) HIP_TRY(hipEventCreate(&e));
-  c->feat_timing = enable ? 1 : 0;
-  *ms = c->feat_ms;
+  const int st = c->feat.enable(enable != 0);
+  if (st) return st;
+  c->feat.copy_out(ms);
   return RS_OK;
 }

@@ -6,8 +6,7 @@
 
 #include <cstring>
 
-#include "common.h"
-#include "ctx.h"
+#include "host.h"
 #include "device_math.h"
 
 namespace rsd {
@@ -186,16 +185,15 @@ int fmatrix_stls_lsq(rs_ctx *c, const double *pl, const double *pr, int64_t n, d
   if (n > (1LL << 26)) return fail(RS_EINVAL, "too many correspondences");
   hipError_t e = hipSetDevice(c->device);
   if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-  const size_t bp = sizeof(double) * 2 * n, bA = sizeof(double) * 9 * n;
-  int st = ensure_scratch(c, 2 * bp + bA + 256);
+  // packed; F counts as part of the 256 bytes after A
+  Layout L(1);
+  const auto pl_b = L.add<double>(2 * n), pr_b = L.add<double>(2 * n), A_b = L.add<double>(9 * n);
+  const auto F_b = L.add<double>(9);
+  int st = L.bind(c, 256 - F_b.bytes);
   if (st) return st;
-  char *base = static_cast<char *>(c->scratch);
-  double *d_pl = reinterpret_cast<double *>(base);
-  double *d_pr = reinterpret_cast<double *>(base + bp);
-  double *d_A = reinterpret_cast<double *>(base + 2 * bp);
-  double *d_F = reinterpret_cast<double *>(base + 2 * bp + bA);
-  if ((e = hipMemcpyAsync(d_pl, pl, bp, hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
-      (e = hipMemcpyAsync(d_pr, pr, bp, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
+  double *d_pl = pl_b.dev(), *d_pr = pr_b.dev(), *d_A = A_b.dev(), *d_F = F_b.dev();
+  if ((e = hipMemcpyAsync(d_pl, pl, pl_b.bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(d_pr, pr, pr_b.bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
     return hip_fail(e, "hipMemcpyAsync");
   hipLaunchKernelGGL(rsd::k_fstls_lsq, dim3(1), dim3(rsd::kT), 0, c->stream, d_pl, d_pr,
                      static_cast<int>(n), d_A, d_F);

@@ -38,22 +38,14 @@
 #include <thread>
 #include <vector>
 
-#include "common.h"
-#include "ctx.h"
+#include "host.h"
 
 namespace rs {
-int hip_fail(hipError_t e, const char *what);
 void mt_jump_poly(uint64_t J, std::vector<uint64_t> &out);
 void mt_poly_square(std::vector<uint64_t> &p);
 void mt_poly_mulmod(const std::vector<uint64_t> &a, const std::vector<uint64_t> &b,
                     std::vector<uint64_t> &r);
 }  // namespace rs
-
-#define HIP_TRY(expr)                                     \
-  do {                                                    \
-    hipError_t e_ = (expr);                               \
-    if (e_ != hipSuccess) return rs::hip_fail(e_, #expr); \
-  } while (0)
 
 namespace {
 

@@ -19,8 +19,7 @@
 #include <initializer_list>
 #include <vector>
 
-#include "common.h"
-#include "ctx.h"
+#include "host.h"
 #include "device_math.h"
 #include "f8_kernels.h"
 
@@ -282,15 +281,6 @@ __global__ __launch_bounds__(kPairSelT) void k_pairs_select(
 
 }  // namespace rsd
 
-using rs::fail;
-using rs::hip_fail;
-
-#define HIP_TRY(expr)                                 \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
-
 static_assert(sizeof(rsd::PairDevResult) == sizeof(rs_pair_result), "rs_pair_result layout");
 
 namespace rs {
@@ -322,35 +312,27 @@ int pairs_enqueue(rs_ctx *c, const double *p1, const double *p2, const int64_t *
     }
   HIP_TRY(hipSetDevice(c->device));
   const int64_t ld = B * H, tp = total > 0 ? total : 1;
-  auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-  const size_t sizes[] = {sizeof(rsd::Pt) * tp,         sizeof(int64_t) * (B + 1),
-                          sizeof(double) * 9 * ld,      sizeof(int) * ld,
-                          sizeof(int) * ld,             sizeof(double) * rsd::kCountChunks * ld,
-                          sizeof(double) * ld,          sizeof(rsd::PairDevResult) * B,
-                          sizeof(int32_t) * tp,
-                          mode == RS_SAMPLER_TUPLES ? sizeof(int32_t) * 8 * ld : 0,
-                          seed_ids ? sizeof(int64_t) * B : 0, extra};
-  size_t tot = 0;
-  for (size_t s : sizes) tot += al(s);
-  int st = rs::ensure_scratch(c, tot + 256);
+  rs::Layout L;
+  const auto b_pts = L.add<rsd::Pt>(tp);
+  const auto b_off = L.add<int64_t>(B + 1);
+  const auto b_F = L.add<double>(9 * ld);
+  const auto b_counts = L.add<int>(ld), b_cand = L.add<int>(ld);
+  const auto b_nrm = L.add<double>(rsd::kCountChunks * ld), b_cnorm = L.add<double>(ld);
+  const auto b_res = L.add<rsd::PairDevResult>(B);
+  const auto b_inl = L.add<int32_t>(tp);
+  const auto b_tup = L.add<int32_t>(mode == RS_SAMPLER_TUPLES ? 8 * ld : 0);
+  const auto b_ids = L.add<int64_t>(seed_ids ? B : 0);
+  const auto b_extra = L.add<char>(extra);
+  int st = L.bind(c);
   if (st) return st;
-  std::vector<char *> buf;
-  char *p = static_cast<char *>(c->scratch);
-  for (size_t s : sizes) {
-    buf.push_back(p);
-    p += al(s);
-  }
-  auto *d_pts = reinterpret_cast<rsd::Pt *>(buf[0]);
-  auto *d_off = reinterpret_cast<int64_t *>(buf[1]);
-  auto *d_F = reinterpret_cast<double *>(buf[2]);
-  auto *d_counts = reinterpret_cast<int *>(buf[3]);
-  auto *d_cand = reinterpret_cast<int *>(buf[4]);
-  auto *d_nrm = reinterpret_cast<double *>(buf[5]);
-  auto *d_cnorm = reinterpret_cast<double *>(buf[6]);
-  auto *d_res = reinterpret_cast<rsd::PairDevResult *>(buf[7]);
-  auto *d_inl = reinterpret_cast<int32_t *>(buf[8]);
-  auto *d_tup = reinterpret_cast<int32_t *>(buf[9]);
-  auto *d_ids = seed_ids ? reinterpret_cast<int64_t *>(buf[10]) : nullptr;
+  auto *d_pts = b_pts.dev();
+  auto *d_off = b_off.dev();
+  auto *d_F = b_F.dev();
+  auto *d_counts = b_counts.dev(), *d_cand = b_cand.dev();
+  auto *d_nrm = b_nrm.dev(), *d_cnorm = b_cnorm.dev();
+  auto *d_res = b_res.dev();
+  auto *d_inl = b_inl.dev(), *d_tup = b_tup.dev();
+  auto *d_ids = seed_ids ? b_ids.dev() : nullptr;
   if (total > 0) {
     std::vector<rsd::Pt> hp(total);
     for (int64_t i = 0; i < total; ++i) hp[i] = {p1[i], p1[total + i], p2[i], p2[total + i]};
@@ -383,7 +365,7 @@ int pairs_enqueue(rs_ctx *c, const double *p1, const double *p2, const int64_t *
   d->res = d_res;
   d->inl = d_inl;
   d->total = total;
-  d->extra = buf[11];
+  d->extra = b_extra.dev();
   return RS_OK;
 }
 }  // namespace rs

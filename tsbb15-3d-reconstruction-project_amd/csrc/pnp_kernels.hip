@@ -28,8 +28,7 @@
 #include <limits>
 #include <vector>
 
-#include "common.h"
-#include "ctx.h"
+#include "host.h"
 #include "device_math.h"
 #include "f8_kernels.h"
 
@@ -1499,17 +1498,6 @@ __global__ __launch_bounds__(kLmThreads) void k_pnp_lm(const double *__restrict_
 }  // namespace rsd
 
 // ------------------------------------------------------------------------------------------
-using rs::fail;
-using rs::hip_fail;
-
-#define HIP_TRY(expr)                                 \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
-
-static size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
 // Bounds of the call's points for k_pnp_count<true>'s guard band: xmax >= |x|_1 and umax >=
 // max(|y0 / y2|, |y1 / y2|) over all points (a non-finite point makes both infinite: every pair
 // then takes the reference-order test).
@@ -1535,13 +1523,14 @@ extern "C" int rs_pnp_dlt(rs_ctx *c, const double *X, const double *y, int64_t m
   if (m < 6) return fail(RS_EINVAL, "the DLT needs m >= 6 correspondences (pnp.py:134)");
   if (m > (1 << 24)) return fail(RS_EINVAL, "too many correspondences");
   HIP_TRY(hipSetDevice(c->device));
-  const size_t bin = align256(sizeof(double) * 3 * m), bp = align256(sizeof(rsd::PPt) * m);
-  int st = rs::ensure_scratch(c, 2 * bin + bp + 256);
+  rs::Layout L;
+  const auto b_X = L.add<double>(3 * m), b_y = L.add<double>(3 * m);
+  const auto b_p = L.add<rsd::PPt>(m);
+  const auto b_out = L.add<double>(12);
+  int st = L.bind(c, 0);
   if (st) return st;
-  char *base = static_cast<char *>(c->scratch);
-  double *dX = reinterpret_cast<double *>(base), *dy = reinterpret_cast<double *>(base + bin);
-  auto *dp = reinterpret_cast<rsd::PPt *>(base + 2 * bin);
-  double *dout = reinterpret_cast<double *>(base + 2 * bin + bp);
+  double *dX = b_X.dev(), *dy = b_y.dev(), *dout = b_out.dev();
+  auto *dp = b_p.dev();
   HIP_TRY(hipMemcpyAsync(dX, X, sizeof(double) * 3 * m, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(dy, y, sizeof(double) * 3 * m, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(rsd::k_pack_ppts, dim3((m + 255) / 256), dim3(256), 0, c->stream, dX, dy,
@@ -1567,13 +1556,14 @@ extern "C" int rs_pnp_minimal(rs_ctx *c, const double *X, const double *y, int64
   if (m < 4) return fail(RS_EINVAL, "EPnP needs m >= 4 correspondences");
   if (m > (1 << 24)) return fail(RS_EINVAL, "too many correspondences");
   HIP_TRY(hipSetDevice(c->device));
-  const size_t bin = align256(sizeof(double) * 3 * m), bp = align256(sizeof(rsd::PPt) * m);
-  int st = rs::ensure_scratch(c, 2 * bin + bp + 256);
+  rs::Layout L;
+  const auto b_X = L.add<double>(3 * m), b_y = L.add<double>(3 * m);
+  const auto b_p = L.add<rsd::PPt>(m);
+  const auto b_out = L.add<double>(13);
+  int st = L.bind(c, 0);
   if (st) return st;
-  char *base = static_cast<char *>(c->scratch);
-  double *dX = reinterpret_cast<double *>(base), *dy = reinterpret_cast<double *>(base + bin);
-  auto *dp = reinterpret_cast<rsd::PPt *>(base + 2 * bin);
-  double *dout = reinterpret_cast<double *>(base + 2 * bin + bp);
+  double *dX = b_X.dev(), *dy = b_y.dev(), *dout = b_out.dev();
+  auto *dp = b_p.dev();
   HIP_TRY(hipMemcpyAsync(dX, X, sizeof(double) * 3 * m, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(dy, y, sizeof(double) * 3 * m, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(rsd::k_pack_ppts, dim3((m + 255) / 256), dim3(256), 0, c->stream, dX, dy,
@@ -1619,54 +1609,42 @@ extern "C" int rs_pnp_ransac(rs_ctx *c, const double *X_med, const double *y_med
   }
   HIP_TRY(hipSetDevice(c->device));
   const int64_t ld = (Hm + 63) / 64 * 64;
-  const size_t b_in_m = align256(sizeof(double) * 3 * m_med), b_in_h = align256(sizeof(double) * 3 * m_high);
-  const size_t b_pm = align256(sizeof(rsd::PPt) * m_med), b_ph = align256(sizeof(rsd::PPt) * m_high);
-  const size_t b_tup = align256(sizeof(int) * (mode == RS_SAMPLER_TUPLES ? H * k : 1));
-  const size_t b_P = align256(sizeof(double) * 12 * ld), b_cnt = align256(sizeof(int) * ld);
-  const size_t b_res = align256(sizeof(rsd::PnpDevResult) + sizeof(int64_t) * (m_med + m_high));
-  const size_t b_mir = align256(k == 3 ? static_cast<size_t>(Hm) : 1);
-  int st = rs::ensure_scratch(c, 2 * b_in_m + 2 * b_in_h + b_pm + b_ph + b_tup + b_P + b_cnt + b_res +
-                                     b_mir);
-  if (st) return st;
-  char *p = static_cast<char *>(c->scratch);
-  auto take = [&p](size_t b) {
-    char *q = p;
-    p += b;
-    return q;
-  };
-  double *dXm = reinterpret_cast<double *>(take(b_in_m));
-  double *dym = reinterpret_cast<double *>(take(b_in_m));
-  double *dXh = reinterpret_cast<double *>(take(b_in_h));
-  double *dyh = reinterpret_cast<double *>(take(b_in_h));
-  auto *pm = reinterpret_cast<rsd::PPt *>(take(b_pm));
-  auto *ph = reinterpret_cast<rsd::PPt *>(take(b_ph));
-  int *dtup = reinterpret_cast<int *>(take(b_tup));
-  double *dP = reinterpret_cast<double *>(take(b_P));
-  int *dcnt = reinterpret_cast<int *>(take(b_cnt));
-  auto *dres = reinterpret_cast<rsd::PnpDevResult *>(take(b_res));
-  auto *dmir = reinterpret_cast<unsigned char *>(take(b_mir));  // P3P poses' mirrored flags
-  hipStream_t s = c->stream;
+  rs::Layout L;
+  const auto b_Xm = L.add<double>(3 * m_med), b_ym = L.add<double>(3 * m_med);
+  const auto b_Xh = L.add<double>(3 * m_high), b_yh = L.add<double>(3 * m_high);
+  const auto b_pm = L.add<rsd::PPt>(m_med), b_ph = L.add<rsd::PPt>(m_high);
+  const auto b_tup = L.add<int>(mode == RS_SAMPLER_TUPLES ? H * k : 1);
+  const auto b_P = L.add<double>(12 * ld);
+  const auto b_cnt = L.add<int>(ld);
+  const auto b_res = L.add_bytes<rsd::PnpDevResult>(sizeof(rsd::PnpDevResult) +
+                                                    sizeof(int64_t) * (m_med + m_high));
+  const auto b_mir = L.add<unsigned char>(k == 3 ? Hm : 1);  // P3P poses' mirrored flags
   // the inputs staged contiguously in pinned memory (the layout of the scratch buffers up to the
   // tuples) and sent with one DMA copy; the call synchronises before returning, so the staging
   // is free again for the next call.  The same set as med and high (ransac.py's usual call,
   // D_med = D_high) is sent and packed once.
+  int st = L.bind(c, 0, L.upto(b_P));
+  if (st) return st;
+  double *dXm = b_Xm.dev(), *dym = b_ym.dev(), *dXh = b_Xh.dev(), *dyh = b_yh.dev();
+  auto *pm = b_pm.dev(), *ph = b_ph.dev();
+  int *dtup = b_tup.dev(), *dcnt = b_cnt.dev();
+  double *dP = b_P.dev();
+  auto *dres = b_res.dev();
+  auto *dmir = b_mir.dev();
+  hipStream_t s = c->stream;
   const bool same = X_med == X_high && y_med == y_high && m_med == m_high;
-  const size_t n_stage = 2 * b_in_m + 2 * b_in_h + b_pm + b_ph + b_tup;
-  if ((st = rs::ensure_pinned(c, n_stage))) return st;
-  char *hp = static_cast<char *>(c->pinned);
-  std::memcpy(hp, X_med, sizeof(double) * 3 * m_med);
-  std::memcpy(hp + b_in_m, y_med, sizeof(double) * 3 * m_med);
-  size_t up = 2 * b_in_m;
+  std::memcpy(b_Xm.host(), X_med, b_Xm.bytes);
+  std::memcpy(b_ym.host(), y_med, b_ym.bytes);
+  size_t up = L.upto(b_Xh);
   if (!same) {
-    std::memcpy(hp + 2 * b_in_m, X_high, sizeof(double) * 3 * m_high);
-    std::memcpy(hp + 2 * b_in_m + b_in_h, y_high, sizeof(double) * 3 * m_high);
-    up = 2 * b_in_m + 2 * b_in_h;
+    std::memcpy(b_Xh.host(), X_high, b_Xh.bytes);
+    std::memcpy(b_yh.host(), y_high, b_yh.bytes);
+    up = L.upto(b_pm);
   }
-  HIP_TRY(hipMemcpyAsync(dXm, hp, up, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(L.dev(), L.host(), up, hipMemcpyHostToDevice, s));
   if (mode == RS_SAMPLER_TUPLES) {
-    const size_t to = 2 * b_in_m + 2 * b_in_h + b_pm + b_ph;  // dtup's offset, as in scratch
-    std::memcpy(hp + to, host_tuples, sizeof(int) * H * k);
-    HIP_TRY(hipMemcpyAsync(dtup, hp + to, sizeof(int) * H * k, hipMemcpyHostToDevice, s));
+    std::memcpy(b_tup.host(), host_tuples, b_tup.bytes);
+    HIP_TRY(hipMemcpyAsync(dtup, b_tup.host(), b_tup.bytes, hipMemcpyHostToDevice, s));
   }
   hipLaunchKernelGGL(rsd::k_pack_ppts, dim3((m_med + 255) / 256), dim3(256), 0, s, dXm, dym,
                      static_cast<int>(m_med), pm);
@@ -1676,8 +1654,7 @@ extern "C" int rs_pnp_ransac(rs_ctx *c, const double *X_med, const double *y_med
     hipLaunchKernelGGL(rsd::k_pack_ppts, dim3((m_high + 255) / 256), dim3(256), 0, s, dXh, dyh,
                        static_cast<int>(m_high), ph);
   HIP_TRY(hipMemsetAsync(dcnt, 0, sizeof(int) * Hm, s));
-  const bool timed = c->pnp_timing != 0;
-  if (timed) HIP_TRY(hipEventRecord(c->pnp_ev[0], s));
+  if ((st = c->pnp.mark(0, s))) return st;
   if (k == 3)
     hipLaunchKernelGGL(rsd::k_pnp_solve_p3p, dim3((H + 63) / 64), dim3(64), 0, s, ph,
                        static_cast<int>(m_high), static_cast<int>(H), mode, seed, dtup, dP, ld, dmir);
@@ -1686,7 +1663,7 @@ extern "C" int rs_pnp_ransac(rs_ctx *c, const double *X_med, const double *y_med
                        static_cast<int>(m_high), static_cast<int>(H), k, mode, seed, dtup, dP,
                        ld, 0);
   HIP_TRY(hipGetLastError());
-  if (timed) HIP_TRY(hipEventRecord(c->pnp_ev[1], s));
+  if ((st = c->pnp.mark(1, s))) return st;
   const int64_t groups = (Hm + 63) / 64;
   int64_t nch = std::max<int64_t>(1, std::min<int64_t>((8192 + groups - 1) / groups, (m_med + 63) / 64));
   const int chunk = static_cast<int>((m_med + nch - 1) / nch);
@@ -1699,22 +1676,17 @@ extern "C" int rs_pnp_ransac(rs_ctx *c, const double *X_med, const double *y_med
                      static_cast<int>(nch), thresh, rsd::PxMetric{1.0, 0.0, 1.0}, xmax, umax,
                      dcnt);
   HIP_TRY(hipGetLastError());
-  if (timed) HIP_TRY(hipEventRecord(c->pnp_ev[2], s));
+  if ((st = c->pnp.mark(2, s))) return st;
   hipLaunchKernelGGL(rsd::k_pnp_select_inliers, dim3(1), dim3(1024), 0, s, dcnt,
                      static_cast<int>(Hm), dP, ld, dres,
                      k == 3 ? static_cast<const unsigned char *>(dmir) : nullptr, pm,
                      static_cast<int>(m_med), ph, static_cast<int>(m_high), thresh);
   HIP_TRY(hipGetLastError());
-  std::vector<char> host(sizeof(rsd::PnpDevResult) + sizeof(int64_t) * (m_med + m_high));
+  std::vector<char> host(b_res.bytes);
   HIP_TRY(hipMemcpyAsync(host.data(), dres, host.size(), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (timed) {
-    float a = 0.f, b = 0.f;
-    HIP_TRY(hipEventElapsedTime(&a, c->pnp_ev[0], c->pnp_ev[1]));
-    HIP_TRY(hipEventElapsedTime(&b, c->pnp_ev[1], c->pnp_ev[2]));
-    c->pnp_solve_ms = a;
-    c->pnp_count_ms = b;
-  }
+  if ((st = c->pnp.read(0, 0, 1))) return st;  // solve
+  if ((st = c->pnp.read(1, 1, 2))) return st;  // count
   const auto *r = reinterpret_cast<const rsd::PnpDevResult *>(host.data());
   std::memcpy(out->R, r->R, sizeof(out->R));
   std::memcpy(out->t, r->t, sizeof(out->t));
@@ -1742,16 +1714,16 @@ extern "C" int rs_pnp_count_poses(rs_ctx *c, const double *X, const double *y, i
   if (m < 1 || H < 1 || m > (1 << 26) || H > (1LL << 26)) return fail(RS_EINVAL, "bad dimensions");
   HIP_TRY(hipSetDevice(c->device));
   const int64_t ld = (H + 63) / 64 * 64;
-  const size_t b_in = align256(sizeof(double) * 3 * m), b_p = align256(sizeof(rsd::PPt) * m);
-  const size_t b_P = align256(sizeof(double) * 12 * ld), b_cnt = align256(sizeof(int) * ld);
-  int st = rs::ensure_scratch(c, 2 * b_in + b_p + b_P + b_cnt);
+  rs::Layout L;
+  const auto b_X = L.add<double>(3 * m), b_y = L.add<double>(3 * m);
+  const auto b_p = L.add<rsd::PPt>(m);
+  const auto b_P = L.add<double>(12 * ld);
+  const auto b_cnt = L.add<int>(ld);
+  int st = L.bind(c, 0);
   if (st) return st;
-  char *p = static_cast<char *>(c->scratch);
-  double *dX = reinterpret_cast<double *>(p);
-  double *dy = reinterpret_cast<double *>(p + b_in);
-  auto *pts = reinterpret_cast<rsd::PPt *>(p + 2 * b_in);
-  double *dP = reinterpret_cast<double *>(p + 2 * b_in + b_p);
-  int *dcnt = reinterpret_cast<int *>(p + 2 * b_in + b_p + b_P);
+  double *dX = b_X.dev(), *dy = b_y.dev(), *dP = b_P.dev();
+  auto *pts = b_p.dev();
+  int *dcnt = b_cnt.dev();
   std::vector<double> soa(static_cast<size_t>(12 * ld), 0.0);
   for (int64_t h = 0; h < H; ++h)
     for (int q = 0; q < 12; ++q) soa[static_cast<size_t>(q * ld + h)] = poses[12 * h + q];
@@ -1827,25 +1799,19 @@ extern "C" int rs_pnp_ransac_cv(rs_ctx *c, const double *X, const double *uv, in
   }
   // with an extrinsic guess, hypothesis 0 is the guess and the samples follow
   const int64_t H = max_iters + (guess ? 1 : 0), ld = (H + 63) / 64 * 64;
-  const size_t b_in = align256(sizeof(double) * 3 * m), b_p = align256(sizeof(rsd::PPt) * m);
-  const size_t b_P = align256(sizeof(double) * 12 * ld), b_cnt = align256(sizeof(int) * ld);
-  const size_t b_res = align256(sizeof(rsd::PnpDevResult) + sizeof(int64_t) * m);
-  const size_t b_g = align256(sizeof(double) * 12);
-  int st = rs::ensure_scratch(c, 2 * b_in + b_p + b_P + b_cnt + b_res + b_g);
+  rs::Layout L;
+  const auto b_X = L.add<double>(3 * m), b_y = L.add<double>(3 * m);
+  const auto b_p = L.add<rsd::PPt>(m);
+  const auto b_P = L.add<double>(12 * ld);
+  const auto b_cnt = L.add<int>(ld);
+  const auto b_res = L.add_bytes<rsd::PnpDevResult>(sizeof(rsd::PnpDevResult) + sizeof(int64_t) * m);
+  const auto b_g = L.add<double>(12);
+  int st = L.bind(c, 0);
   if (st) return st;
-  char *p = static_cast<char *>(c->scratch);
-  auto take = [&p](size_t b) {
-    char *q = p;
-    p += b;
-    return q;
-  };
-  double *dX = reinterpret_cast<double *>(take(b_in));
-  double *dy = reinterpret_cast<double *>(take(b_in));
-  auto *pts = reinterpret_cast<rsd::PPt *>(take(b_p));
-  double *dP = reinterpret_cast<double *>(take(b_P));
-  int *dcnt = reinterpret_cast<int *>(take(b_cnt));
-  auto *dres = reinterpret_cast<rsd::PnpDevResult *>(take(b_res));
-  double *dguess = reinterpret_cast<double *>(take(b_g));
+  double *dX = b_X.dev(), *dy = b_y.dev(), *dP = b_P.dev(), *dguess = b_g.dev();
+  auto *pts = b_p.dev();
+  int *dcnt = b_cnt.dev();
+  auto *dres = b_res.dev();
   hipStream_t s = c->stream;
   if (guess) HIP_TRY(hipMemcpyAsync(dguess, guess, sizeof(double) * 12, hipMemcpyHostToDevice, s));
   const rsd::PxMetric mt{fx, sk, fy};
@@ -1909,7 +1875,7 @@ extern "C" int rs_pnp_ransac_cv(rs_ctx *c, const double *X, const double *uv, in
   hipLaunchKernelGGL(rsd::k_pnp_inliers_px, dim3(1), dim3(1024), 0, s, pts, static_cast<int>(m),
                      dP, ld, best, static_cast<int64_t>(good), thresh, mt, dres);
   HIP_TRY(hipGetLastError());
-  std::vector<char> host(sizeof(rsd::PnpDevResult) + sizeof(int64_t) * m);
+  std::vector<char> host(b_res.bytes);
   HIP_TRY(hipMemcpyAsync(host.data(), dres, host.size(), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   const auto *r = reinterpret_cast<const rsd::PnpDevResult *>(host.data());
@@ -1932,12 +1898,11 @@ extern "C" int rs_pnp_refine_lm(rs_ctx *c, const double *X, const double *uv, in
   if (max_jac < 1) return fail(RS_EINVAL, "max_jac must be >= 1");
   if (!(K[8] != 0.0)) return fail(RS_EINVAL, "K[2][2] must be nonzero");
   HIP_TRY(hipSetDevice(c->device));
-  const size_t bx = align256(sizeof(double) * 3 * m), bu = align256(sizeof(double) * 2 * m);
-  int st = rs::ensure_scratch(c, bx + bu + 256);
+  rs::Layout L;
+  const auto b_X = L.add<double>(3 * m), b_u = L.add<double>(2 * m), b_io = L.add<double>(16);
+  int st = L.bind(c, 0);
   if (st) return st;
-  char *base = static_cast<char *>(c->scratch);
-  double *dX = reinterpret_cast<double *>(base), *du = reinterpret_cast<double *>(base + bx);
-  double *dio = reinterpret_cast<double *>(base + bx + bu);
+  double *dX = b_X.dev(), *du = b_u.dev(), *dio = b_io.dev();
   double io[16] = {};
   std::memcpy(io, R_io, sizeof(double) * 9);
   std::memcpy(io + 9, t_io, sizeof(double) * 3);
@@ -1964,10 +1929,9 @@ extern "C" int rs_pnp_refine_lm(rs_ctx *c, const double *X, const double *uv, in
 extern "C" int rs_pnp_timing(rs_ctx *c, int32_t enable, double *solve_ms, double *count_ms) {
   if (!c || !solve_ms || !count_ms) return fail(RS_EINVAL, "null pointer");
   HIP_TRY(hipSetDevice(c->device));
-  if (enable && !c->pnp_ev[0])
-    for (auto &e : c->pnp_ev) HIP_TRY(hipEventCreate(&e));
-  c->pnp_timing = enable ? 1 : 0;
-  *solve_ms = c->pnp_solve_ms;
-  *count_ms = c->pnp_count_ms;
+  const int st = c->pnp.enable(enable != 0);
+  if (st) return st;
+  *solve_ms = c->pnp.ms[0];
+  *count_ms = c->pnp.ms[1];
   return RS_OK;
 }

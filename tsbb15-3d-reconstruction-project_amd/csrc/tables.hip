@@ -16,8 +16,7 @@
 #include <initializer_list>
 #include <vector>
 
-#include "common.h"
-#include "ctx.h"
+#include "host.h"
 #include "device_math.h"
 #include "twoview_math.h"
 
@@ -171,35 +170,6 @@ __global__ __launch_bounds__(256) void k_ba_jacobian(
 
 }  // namespace rsd
 
-using rs::fail;
-using rs::hip_fail;
-
-#define HIP_TRY(expr)                                 \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
-
-namespace {
-
-size_t al(size_t b) { return (b + 255) / 256 * 256; }
-
-int carve(rs_ctx *c, std::initializer_list<size_t> sizes, std::vector<char *> &out) {
-  size_t tot = 0;
-  for (size_t s : sizes) tot += al(s);
-  int st = rs::ensure_scratch(c, tot + 256);
-  if (st) return st;
-  char *p = static_cast<char *>(c->scratch);
-  out.clear();
-  for (size_t s : sizes) {
-    out.push_back(p);
-    p += al(s);
-  }
-  return RS_OK;
-}
-
-}  // namespace
-
 extern "C" int rs_match_observations(rs_ctx *c, const double *obs, const int64_t *obs_point,
                                      int64_t m, const double *queries, int64_t n, double tol,
                                      int64_t *out) {
@@ -209,21 +179,23 @@ extern "C" int rs_match_observations(rs_ctx *c, const double *obs, const int64_t
   if (n == 0) return RS_OK;
   HIP_TRY(hipSetDevice(c->device));
   const int64_t mm = m > 0 ? m : 1;
-  std::vector<char *> b;
-  int st = carve(c, {sizeof(double) * 3 * mm, sizeof(int64_t) * mm, sizeof(double) * 3 * n,
-                     sizeof(int64_t) * n}, b);
+  rs::Layout L;
+  const auto d_obs = L.add<double>(3 * mm);
+  const auto d_op = L.add<int64_t>(mm);
+  const auto d_q = L.add<double>(3 * n);
+  const auto d_out = L.add<int64_t>(n);
+  int st = L.bind(c);
   if (st) return st;
   if (m > 0) {
-    HIP_TRY(hipMemcpyAsync(b[0], obs, sizeof(double) * 3 * m, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(b[1], obs_point, sizeof(int64_t) * m, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_obs.dev(), obs, sizeof(double) * 3 * m, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_op.dev(), obs_point, sizeof(int64_t) * m, hipMemcpyHostToDevice, c->stream));
   }
-  HIP_TRY(hipMemcpyAsync(b[2], queries, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_q.dev(), queries, d_q.bytes, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(rsd::k_match_obs, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0,
-                     c->stream, reinterpret_cast<double *>(b[0]), static_cast<int>(m),
-                     reinterpret_cast<int64_t *>(b[1]), reinterpret_cast<double *>(b[2]),
-                     static_cast<int>(n), tol, reinterpret_cast<int64_t *>(b[3]));
+                     c->stream, d_obs.dev(), static_cast<int>(m), d_op.dev(), d_q.dev(),
+                     static_cast<int>(n), tol, d_out.dev());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, b[3], sizeof(int64_t) * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(out, d_out.dev(), d_out.bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RS_OK;
 }
@@ -234,17 +206,16 @@ extern "C" int rs_e_from_cameras(rs_ctx *c, const double *C1, const double *C2, 
   if (n < 0 || n > (1 << 26)) return fail(RS_EINVAL, "bad sizes");
   if (n == 0) return RS_OK;
   HIP_TRY(hipSetDevice(c->device));
-  std::vector<char *> b;
-  int st = carve(c, {sizeof(double) * 12 * n, sizeof(double) * 12 * n, sizeof(double) * 9 * n}, b);
+  rs::Layout L;
+  const auto dC1 = L.add<double>(12 * n), dC2 = L.add<double>(12 * n), dE = L.add<double>(9 * n);
+  int st = L.bind(c);
   if (st) return st;
-  HIP_TRY(hipMemcpyAsync(b[0], C1, sizeof(double) * 12 * n, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(b[1], C2, sizeof(double) * 12 * n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dC1.dev(), C1, dC1.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dC2.dev(), C2, dC2.bytes, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(rsd::k_e_from_cameras, dim3(static_cast<unsigned>((n + 127) / 128)),
-                     dim3(128), 0, c->stream, reinterpret_cast<double *>(b[0]),
-                     reinterpret_cast<double *>(b[1]), static_cast<int>(n),
-                     reinterpret_cast<double *>(b[2]));
+                     dim3(128), 0, c->stream, dC1.dev(), dC2.dev(), static_cast<int>(n), dE.dev());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(E, b[2], sizeof(double) * 9 * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(E, dE.dev(), dE.bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RS_OK;
 }
@@ -257,23 +228,23 @@ extern "C" int rs_add_new_points(rs_ctx *c, const double *C1, const double *C2,
   if (n < 0 || n > (1 << 26)) return fail(RS_EINVAL, "bad sizes");
   if (n == 0) return RS_OK;
   HIP_TRY(hipSetDevice(c->device));
-  std::vector<char *> b;
-  int st = carve(c, {sizeof(double) * 24, sizeof(double) * 3 * n, sizeof(double) * 3 * n,
-                     sizeof(int32_t) * n, sizeof(double) * 3 * n}, b);
+  rs::Layout L;
+  const auto dC = L.add<double>(24);  // C1 then C2
+  const auto dy1 = L.add<double>(3 * n), dy2 = L.add<double>(3 * n);
+  const auto dmask = L.add<int32_t>(n);
+  const auto dX = L.add<double>(3 * n);
+  int st = L.bind(c);
   if (st) return st;
-  HIP_TRY(hipMemcpyAsync(b[0], C1, sizeof(double) * 12, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(b[0] + sizeof(double) * 12, C2, sizeof(double) * 12,
-                         hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(b[1], y1, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(b[2], y2, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dC.dev(), C1, sizeof(double) * 12, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dC.dev() + 12, C2, sizeof(double) * 12, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dy1.dev(), y1, dy1.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dy2.dev(), y2, dy2.bytes, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(rsd::k_new_points, dim3(static_cast<unsigned>((n + 127) / 128)), dim3(128),
-                     0, c->stream, reinterpret_cast<double *>(b[0]),
-                     reinterpret_cast<double *>(b[1]), reinterpret_cast<double *>(b[2]),
-                     static_cast<int>(n), gate, reinterpret_cast<int32_t *>(b[3]),
-                     reinterpret_cast<double *>(b[4]));
+                     0, c->stream, dC.dev(), dy1.dev(), dy2.dev(), static_cast<int>(n), gate,
+                     dmask.dev(), dX.dev());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(mask, b[3], sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(X, b[4], sizeof(double) * 3 * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(mask, dmask.dev(), dmask.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(X, dX.dev(), dX.bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RS_OK;
 }
@@ -296,24 +267,24 @@ extern "C" int rs_ba_residuals(rs_ctx *c, const double *cams, int64_t nC, const 
   if (st) return st;
   if (n == 0) return RS_OK;
   HIP_TRY(hipSetDevice(c->device));
-  std::vector<char *> b;
   const int64_t pp = nP > 0 ? nP : 1;
-  st = carve(c, {sizeof(double) * 12 * nC, sizeof(double) * 3 * pp, sizeof(int32_t) * n,
-                 sizeof(int32_t) * n, sizeof(double) * 2 * n, sizeof(double) * 2 * n}, b);
+  rs::Layout L;
+  const auto d_cams = L.add<double>(12 * nC), d_pts = L.add<double>(3 * pp);
+  const auto d_ov = L.add<int32_t>(n), d_op = L.add<int32_t>(n);
+  const auto d_uv = L.add<double>(2 * n), d_r = L.add<double>(2 * n);
+  st = L.bind(c);
   if (st) return st;
-  HIP_TRY(hipMemcpyAsync(b[0], cams, sizeof(double) * 12 * nC, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_cams.dev(), cams, d_cams.bytes, hipMemcpyHostToDevice, c->stream));
   if (nP > 0)
-    HIP_TRY(hipMemcpyAsync(b[1], pts, sizeof(double) * 3 * nP, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(b[2], obs_view, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(b[3], obs_point, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(b[4], uv, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_pts.dev(), pts, sizeof(double) * 3 * nP, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_ov.dev(), obs_view, d_ov.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_op.dev(), obs_point, d_op.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_uv.dev(), uv, d_uv.bytes, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(rsd::k_ba_residuals, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256),
-                     0, c->stream, reinterpret_cast<double *>(b[0]),
-                     reinterpret_cast<double *>(b[1]), reinterpret_cast<int32_t *>(b[2]),
-                     reinterpret_cast<int32_t *>(b[3]), reinterpret_cast<double *>(b[4]),
-                     static_cast<int>(n), reinterpret_cast<double *>(b[5]));
+                     0, c->stream, d_cams.dev(), d_pts.dev(), d_ov.dev(), d_op.dev(), d_uv.dev(),
+                     static_cast<int>(n), d_r.dev());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(r, b[5], sizeof(double) * 2 * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(r, d_r.dev(), d_r.bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RS_OK;
 }
@@ -327,24 +298,24 @@ extern "C" int rs_ba_jacobian(rs_ctx *c, const double *cams, int64_t nC, const d
   if (st) return st;
   if (n == 0) return RS_OK;
   HIP_TRY(hipSetDevice(c->device));
-  std::vector<char *> b;
   const int64_t pp = nP > 0 ? nP : 1;
-  st = carve(c, {sizeof(double) * 12 * nC, sizeof(double) * 3 * pp, sizeof(int32_t) * n,
-                 sizeof(int32_t) * n, sizeof(double) * 24 * n, sizeof(double) * 6 * n}, b);
+  rs::Layout L;
+  const auto d_cams = L.add<double>(12 * nC), d_pts = L.add<double>(3 * pp);
+  const auto d_ov = L.add<int32_t>(n), d_op = L.add<int32_t>(n);
+  const auto d_Jc = L.add<double>(24 * n), d_Jp = L.add<double>(6 * n);
+  st = L.bind(c);
   if (st) return st;
-  HIP_TRY(hipMemcpyAsync(b[0], cams, sizeof(double) * 12 * nC, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_cams.dev(), cams, d_cams.bytes, hipMemcpyHostToDevice, c->stream));
   if (nP > 0)
-    HIP_TRY(hipMemcpyAsync(b[1], pts, sizeof(double) * 3 * nP, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(b[2], obs_view, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(b[3], obs_point, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_pts.dev(), pts, sizeof(double) * 3 * nP, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_ov.dev(), obs_view, d_ov.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_op.dev(), obs_point, d_op.bytes, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(rsd::k_ba_jacobian, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256),
-                     0, c->stream, reinterpret_cast<double *>(b[0]),
-                     reinterpret_cast<double *>(b[1]), reinterpret_cast<int32_t *>(b[2]),
-                     reinterpret_cast<int32_t *>(b[3]), static_cast<int>(n),
-                     reinterpret_cast<double *>(b[4]), reinterpret_cast<double *>(b[5]));
+                     0, c->stream, d_cams.dev(), d_pts.dev(), d_ov.dev(), d_op.dev(),
+                     static_cast<int>(n), d_Jc.dev(), d_Jp.dev());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(Jc, b[4], sizeof(double) * 24 * n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(Jp, b[5], sizeof(double) * 6 * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(Jc, d_Jc.dev(), d_Jc.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(Jp, d_Jp.dev(), d_Jp.bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RS_OK;
 }

@@ -20,8 +20,7 @@
 #include <initializer_list>
 #include <vector>
 
-#include "common.h"
-#include "ctx.h"
+#include "host.h"
 #include "device_math.h"
 #include "twoview_math.h"
 
@@ -894,37 +893,7 @@ __global__ __launch_bounds__(64) void k_twoview_gather(const Pt *__restrict__ pt
 // ------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------
-using rs::fail;
-using rs::hip_fail;
-
-#define HIP_TRY(expr)                                 \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
-
-namespace {
-
-size_t al(size_t b) { return (b + 255) / 256 * 256; }
-
-// Carve `count` device buffers of the given byte sizes out of the context scratch.
-int carve(rs_ctx *c, std::initializer_list<size_t> sizes, std::vector<char *> &out) {
-  size_t tot = 0;
-  for (size_t s : sizes) tot += al(s);
-  int st = rs::ensure_scratch(c, tot + 256);
-  if (st) return st;
-  char *p = static_cast<char *>(c->scratch);
-  out.clear();
-  for (size_t s : sizes) {
-    out.push_back(p);
-    p += al(s);
-  }
-  return RS_OK;
-}
-
-int grid(int64_t n) { return static_cast<int>((n + 127) / 128); }
-
-}  // namespace
+using rs::blocks;
 
 static_assert(sizeof(rsd::GsInfo) == sizeof(rs_gs_info), "rs_gs_info layout");
 
@@ -939,22 +908,23 @@ extern "C" int rs_triangulate_optimal(rs_ctx *c, const double *C1, const double 
     for (int64_t i = 0; i < n; ++i)
       if (cam[i] < 0 || cam[i] >= n_cam) return fail(RS_EINVAL, "camera index out of range");
   HIP_TRY(hipSetDevice(c->device));
-  std::vector<char *> b;
-  const size_t bc = sizeof(double) * 12 * n_cam, bx = sizeof(double) * 2 * n;
-  int st = carve(c, {bc, bc, bx, bx, cam ? sizeof(int32_t) * n : 0, sizeof(double) * 3 * n}, b);
+  rs::Layout L;
+  const auto dC1 = L.add<double>(12 * n_cam), dC2 = L.add<double>(12 * n_cam);
+  const auto dx1 = L.add<double>(2 * n), dx2 = L.add<double>(2 * n);
+  const auto dcam = L.add<int32_t>(cam ? n : 0);
+  const auto dX = L.add<double>(3 * n);
+  int st = L.bind(c);
   if (st) return st;
-  HIP_TRY(hipMemcpyAsync(b[0], C1, bc, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(b[1], C2, bc, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(b[2], x1, bx, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(b[3], x2, bx, hipMemcpyHostToDevice, c->stream));
-  if (cam) HIP_TRY(hipMemcpyAsync(b[4], cam, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(rsd::k_triangulate_optimal, dim3(grid(n)), dim3(128), 0, c->stream,
-                     reinterpret_cast<double *>(b[0]), reinterpret_cast<double *>(b[1]),
-                     reinterpret_cast<double *>(b[2]), reinterpret_cast<double *>(b[3]),
-                     cam ? reinterpret_cast<int32_t *>(b[4]) : nullptr, n,
-                     reinterpret_cast<double *>(b[5]));
+  HIP_TRY(hipMemcpyAsync(dC1.dev(), C1, dC1.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dC2.dev(), C2, dC2.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dx1.dev(), x1, dx1.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dx2.dev(), x2, dx2.bytes, hipMemcpyHostToDevice, c->stream));
+  if (cam) HIP_TRY(hipMemcpyAsync(dcam.dev(), cam, dcam.bytes, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(rsd::k_triangulate_optimal, dim3(blocks(n, 128)), dim3(128), 0, c->stream,
+                     dC1.dev(), dC2.dev(), dx1.dev(), dx2.dev(), cam ? dcam.dev() : nullptr, n,
+                     dX.dev());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(X_out, b[5], sizeof(double) * 3 * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(X_out, dX.dev(), dX.bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RS_OK;
 }
@@ -965,18 +935,18 @@ extern "C" int rs_camera_resectioning(rs_ctx *c, const double *P, int64_t B, dou
   if (B < 0 || B > (1LL << 26)) return fail(RS_EINVAL, "bad camera count");
   if (B == 0) return RS_OK;
   HIP_TRY(hipSetDevice(c->device));
-  std::vector<char *> b;
-  int st = carve(c, {sizeof(double) * 12 * B, sizeof(double) * 9 * B, sizeof(double) * 9 * B,
-                     sizeof(double) * 3 * B}, b);
+  rs::Layout L;
+  const auto dP = L.add<double>(12 * B), dK = L.add<double>(9 * B), dR = L.add<double>(9 * B);
+  const auto dt = L.add<double>(3 * B);
+  int st = L.bind(c);
   if (st) return st;
-  HIP_TRY(hipMemcpyAsync(b[0], P, sizeof(double) * 12 * B, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(rsd::k_resection, dim3(grid(B)), dim3(128), 0, c->stream,
-                     reinterpret_cast<double *>(b[0]), B, reinterpret_cast<double *>(b[1]),
-                     reinterpret_cast<double *>(b[2]), reinterpret_cast<double *>(b[3]));
+  HIP_TRY(hipMemcpyAsync(dP.dev(), P, dP.bytes, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(rsd::k_resection, dim3(blocks(B, 128)), dim3(128), 0, c->stream, dP.dev(), B,
+                     dK.dev(), dR.dev(), dt.dev());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(K, b[1], sizeof(double) * 9 * B, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(R, b[2], sizeof(double) * 9 * B, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(t, b[3], sizeof(double) * 3 * B, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(K, dK.dev(), dK.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(R, dR.dev(), dR.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(t, dt.dev(), dt.bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RS_OK;
 }
@@ -988,16 +958,16 @@ extern "C" int rs_essential_from_f(rs_ctx *c, const double *K, int32_t one_k, co
   if (B == 0) return RS_OK;
   HIP_TRY(hipSetDevice(c->device));
   const int64_t nk = one_k ? 1 : B;
-  std::vector<char *> b;
-  int st = carve(c, {sizeof(double) * 9 * nk, sizeof(double) * 9 * B, sizeof(double) * 9 * B}, b);
+  rs::Layout L;
+  const auto dK = L.add<double>(9 * nk), dF = L.add<double>(9 * B), dE = L.add<double>(9 * B);
+  int st = L.bind(c);
   if (st) return st;
-  HIP_TRY(hipMemcpyAsync(b[0], K, sizeof(double) * 9 * nk, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(b[1], F, sizeof(double) * 9 * B, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(rsd::k_essential, dim3(grid(B)), dim3(128), 0, c->stream,
-                     reinterpret_cast<double *>(b[0]), one_k ? 0 : 9,
-                     reinterpret_cast<double *>(b[1]), B, reinterpret_cast<double *>(b[2]));
+  HIP_TRY(hipMemcpyAsync(dK.dev(), K, dK.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dF.dev(), F, dF.bytes, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(rsd::k_essential, dim3(blocks(B, 128)), dim3(128), 0, c->stream, dK.dev(),
+                     one_k ? 0 : 9, dF.dev(), B, dE.dev());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(E, b[2], sizeof(double) * 9 * B, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(E, dE.dev(), dE.bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RS_OK;
 }
@@ -1009,21 +979,21 @@ extern "C" int rs_relative_camera_pose(rs_ctx *c, const double *E, const double 
   if (B < 0 || B > (1LL << 26)) return fail(RS_EINVAL, "bad batch size");
   if (B == 0) return RS_OK;
   HIP_TRY(hipSetDevice(c->device));
-  std::vector<char *> b;
-  int st = carve(c, {sizeof(double) * 9 * B, sizeof(double) * 2 * B, sizeof(double) * 2 * B,
-                     sizeof(double) * 9 * B, sizeof(double) * 3 * B, sizeof(int32_t) * B}, b);
+  rs::Layout L;
+  const auto dE = L.add<double>(9 * B), dy1 = L.add<double>(2 * B), dy2 = L.add<double>(2 * B);
+  const auto dR = L.add<double>(9 * B), dt = L.add<double>(3 * B);
+  const auto dfound = L.add<int32_t>(B);
+  int st = L.bind(c);
   if (st) return st;
-  HIP_TRY(hipMemcpyAsync(b[0], E, sizeof(double) * 9 * B, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(b[1], y1, sizeof(double) * 2 * B, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(b[2], y2, sizeof(double) * 2 * B, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(rsd::k_relative_pose, dim3(grid(4 * B)), dim3(128), 0, c->stream,
-                     reinterpret_cast<double *>(b[0]), reinterpret_cast<double *>(b[1]),
-                     reinterpret_cast<double *>(b[2]), B, reinterpret_cast<double *>(b[3]),
-                     reinterpret_cast<double *>(b[4]), reinterpret_cast<int32_t *>(b[5]));
+  HIP_TRY(hipMemcpyAsync(dE.dev(), E, dE.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dy1.dev(), y1, dy1.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dy2.dev(), y2, dy2.bytes, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(rsd::k_relative_pose, dim3(blocks(4 * B, 128)), dim3(128), 0, c->stream,
+                     dE.dev(), dy1.dev(), dy2.dev(), B, dR.dev(), dt.dev(), dfound.dev());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(R, b[3], sizeof(double) * 9 * B, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(t, b[4], sizeof(double) * 3 * B, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(found, b[5], sizeof(int32_t) * B, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(R, dR.dev(), dR.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(t, dt.dev(), dt.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(found, dfound.dev(), dfound.bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RS_OK;
 }
@@ -1033,14 +1003,15 @@ extern "C" int rs_fmatrix_cameras(rs_ctx *c, const double *F, int64_t B, double 
   if (B < 0 || B > (1LL << 26)) return fail(RS_EINVAL, "bad batch size");
   if (B == 0) return RS_OK;
   HIP_TRY(hipSetDevice(c->device));
-  std::vector<char *> b;
-  int st = carve(c, {sizeof(double) * 9 * B, sizeof(double) * 12 * B}, b);
+  rs::Layout L;
+  const auto dF = L.add<double>(9 * B), dC1 = L.add<double>(12 * B);
+  int st = L.bind(c);
   if (st) return st;
-  HIP_TRY(hipMemcpyAsync(b[0], F, sizeof(double) * 9 * B, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(rsd::k_fmatrix_cameras, dim3(grid(B)), dim3(128), 0, c->stream,
-                     reinterpret_cast<double *>(b[0]), B, reinterpret_cast<double *>(b[1]));
+  HIP_TRY(hipMemcpyAsync(dF.dev(), F, dF.bytes, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(rsd::k_fmatrix_cameras, dim3(blocks(B, 128)), dim3(128), 0, c->stream,
+                     dF.dev(), B, dC1.dev());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(C1, b[1], sizeof(double) * 12 * B, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(C1, dC1.dev(), dC1.bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RS_OK;
 }
@@ -1051,16 +1022,16 @@ extern "C" int rs_fmatrix_from_cameras(rs_ctx *c, const double *C1, const double
   if (B < 0 || B > (1LL << 26)) return fail(RS_EINVAL, "bad batch size");
   if (B == 0) return RS_OK;
   HIP_TRY(hipSetDevice(c->device));
-  std::vector<char *> b;
-  int st = carve(c, {sizeof(double) * 12 * B, sizeof(double) * 12 * B, sizeof(double) * 9 * B}, b);
+  rs::Layout L;
+  const auto dC1 = L.add<double>(12 * B), dC2 = L.add<double>(12 * B), dF = L.add<double>(9 * B);
+  int st = L.bind(c);
   if (st) return st;
-  HIP_TRY(hipMemcpyAsync(b[0], C1, sizeof(double) * 12 * B, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(b[1], C2, sizeof(double) * 12 * B, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(rsd::k_fmatrix_from_cameras, dim3(grid(B)), dim3(128), 0, c->stream,
-                     reinterpret_cast<double *>(b[0]), reinterpret_cast<double *>(b[1]), B,
-                     reinterpret_cast<double *>(b[2]));
+  HIP_TRY(hipMemcpyAsync(dC1.dev(), C1, dC1.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dC2.dev(), C2, dC2.bytes, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(rsd::k_fmatrix_from_cameras, dim3(blocks(B, 128)), dim3(128), 0, c->stream,
+                     dC1.dev(), dC2.dev(), B, dF.dev());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(F, b[2], sizeof(double) * 9 * B, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(F, dF.dev(), dF.bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RS_OK;
 }
@@ -1079,32 +1050,31 @@ extern "C" int rs_gold_standard(rs_ctx *c, const double *F, const double *pl, co
   if (max_iter < 1 || max_iter > 100000) return fail(RS_EINVAL, "max_iter must be in [1, 1e5]");
   HIP_TRY(hipSetDevice(c->device));
   const int64_t tp = total > 0 ? total : 1;
-  std::vector<char *> b;
-  int st = carve(c, {sizeof(double) * 9 * B, sizeof(double) * 2 * tp, sizeof(double) * 2 * tp,
-                     sizeof(int64_t) * (B + 1), sizeof(double) * 3 * tp, sizeof(double) * 3 * tp,
-                     sizeof(double) * rsd::kPerPt * tp, sizeof(double) * 9 * B,
-                     sizeof(double) * 12 * B, sizeof(rs_gs_info) * B}, b);
+  rs::Layout L;
+  const auto dF = L.add<double>(9 * B), dpl = L.add<double>(2 * tp), dpr = L.add<double>(2 * tp);
+  const auto doff = L.add<int64_t>(B + 1);
+  const auto dX = L.add<double>(3 * tp), dXw = L.add<double>(3 * tp);
+  const auto dwork = L.add<double>(rsd::kPerPt * tp);
+  const auto dFg = L.add<double>(9 * B), dC1 = L.add<double>(12 * B);
+  const auto dinfo = L.add<rsd::GsInfo>(B);
+  int st = L.bind(c);
   if (st) return st;
-  HIP_TRY(hipMemcpyAsync(b[0], F, sizeof(double) * 9 * B, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dF.dev(), F, dF.bytes, hipMemcpyHostToDevice, c->stream));
   if (total > 0) {
-    HIP_TRY(hipMemcpyAsync(b[1], pl, sizeof(double) * 2 * total, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(b[2], pr, sizeof(double) * 2 * total, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dpl.dev(), pl, sizeof(double) * 2 * total, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dpr.dev(), pr, sizeof(double) * 2 * total, hipMemcpyHostToDevice, c->stream));
   }
-  HIP_TRY(hipMemcpyAsync(b[3], off, sizeof(int64_t) * (B + 1), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(doff.dev(), off, doff.bytes, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(rsd::k_gold_standard<rsd::kGsT>, dim3(static_cast<unsigned>(B)), dim3(rsd::kGsT), 0,
-                     c->stream, reinterpret_cast<double *>(b[0]),
-                     reinterpret_cast<double *>(b[1]), reinterpret_cast<double *>(b[2]), tp,
-                     reinterpret_cast<int64_t *>(b[3]), max_iter, reinterpret_cast<double *>(b[4]),
-                     reinterpret_cast<double *>(b[5]), reinterpret_cast<double *>(b[6]),
-                     reinterpret_cast<double *>(b[7]), reinterpret_cast<double *>(b[8]),
-                     reinterpret_cast<rsd::GsInfo *>(b[9]), nullptr);
+                     c->stream, dF.dev(), dpl.dev(), dpr.dev(), tp, doff.dev(), max_iter, dX.dev(),
+                     dXw.dev(), dwork.dev(), dFg.dev(), dC1.dev(), dinfo.dev(), nullptr);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(F_gold, b[7], sizeof(double) * 9 * B, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(F_gold, dFg.dev(), dFg.bytes, hipMemcpyDeviceToHost, c->stream));
   if (C1_out)
-    HIP_TRY(hipMemcpyAsync(C1_out, b[8], sizeof(double) * 12 * B, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(C1_out, dC1.dev(), dC1.bytes, hipMemcpyDeviceToHost, c->stream));
   if (X_out && total > 0)
-    HIP_TRY(hipMemcpyAsync(X_out, b[4], sizeof(double) * 3 * total, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(info, b[9], sizeof(rs_gs_info) * B, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(X_out, dX.dev(), sizeof(double) * 3 * total, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(info, dinfo.dev(), dinfo.bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RS_OK;
 }
@@ -1116,28 +1086,27 @@ extern "C" int rs_gs_residuals_fd(rs_ctx *c, const double *x, const double *xp, 
   if (n < 1 || n > (1LL << 20)) return fail(RS_EINVAL, "Wrong size of parameter vector");
   HIP_TRY(hipSetDevice(c->device));
   const int64_t np = 12 + 3 * n, nr = 4 * n;
-  const size_t jb = J ? sizeof(double) * static_cast<size_t>(nr) * np : 0;
-  std::vector<char *> b;
-  int st = carve(c, {sizeof(double) * np, J ? sizeof(double) * np : 0, J ? sizeof(double) * np : 0,
-                     sizeof(double) * 2 * n, sizeof(double) * 2 * n, sizeof(double) * nr, jb},
-                 b);
+  rs::Layout L;
+  const auto d_x = L.add<double>(np), d_xp = L.add<double>(J ? np : 0);
+  const auto d_dx = L.add<double>(J ? np : 0);
+  const auto d_pl = L.add<double>(2 * n), d_pr = L.add<double>(2 * n), d_f = L.add<double>(nr);
+  const auto d_J = L.add<double>(J ? static_cast<size_t>(nr) * np : 0);
+  int st = L.bind(c);
   if (st) return st;
-  HIP_TRY(hipMemcpyAsync(b[0], x, sizeof(double) * np, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_x.dev(), x, d_x.bytes, hipMemcpyHostToDevice, c->stream));
   if (J) {
-    HIP_TRY(hipMemcpyAsync(b[1], xp, sizeof(double) * np, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(b[2], dx, sizeof(double) * np, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(b[6], 0, jb, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_xp.dev(), xp, d_xp.bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_dx.dev(), dx, d_dx.bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(d_J.dev(), 0, d_J.bytes, c->stream));
   }
-  HIP_TRY(hipMemcpyAsync(b[3], pl, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(b[4], pr, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(rsd::k_gs_fd, dim3(static_cast<unsigned>((n + 127) / 128)), dim3(128), 0,
-                     c->stream, reinterpret_cast<double *>(b[0]), reinterpret_cast<double *>(b[1]),
-                     reinterpret_cast<double *>(b[2]), reinterpret_cast<double *>(b[3]),
-                     reinterpret_cast<double *>(b[4]), n, reinterpret_cast<double *>(b[5]),
-                     J ? reinterpret_cast<double *>(b[6]) : nullptr);
+  HIP_TRY(hipMemcpyAsync(d_pl.dev(), pl, d_pl.bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_pr.dev(), pr, d_pr.bytes, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(rsd::k_gs_fd, dim3(blocks(n, 128)), dim3(128), 0, c->stream, d_x.dev(),
+                     d_xp.dev(), d_dx.dev(), d_pl.dev(), d_pr.dev(), n, d_f.dev(),
+                     J ? d_J.dev() : nullptr);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(f, b[5], sizeof(double) * nr, hipMemcpyDeviceToHost, c->stream));
-  if (J) HIP_TRY(hipMemcpyAsync(J, b[6], jb, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(f, d_f.dev(), d_f.bytes, hipMemcpyDeviceToHost, c->stream));
+  if (J) HIP_TRY(hipMemcpyAsync(J, d_J.dev(), d_J.bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RS_OK;
 }
@@ -1163,44 +1132,34 @@ extern "C" int rs_pairs_two_view(rs_ctx *c, const double *p1, const double *p2, 
     if (off[b + 1] < off[b] || off[b + 1] - off[b] > (1 << 24))
       return fail(RS_EINVAL, "offsets must be non-decreasing");
   const int64_t tp = off[B] > 0 ? off[B] : 1;
-  // the stages' buffers after the pair RANSAC's, then the output block (one download)
-  const size_t sz[] = {sizeof(int64_t) * (B + 1), sizeof(int32_t) * B, sizeof(double) * 9 * B,
-                       sizeof(double) * 2 * tp,   sizeof(double) * 2 * tp,
-                       sizeof(double) * 3 * tp,   sizeof(double) * 3 * tp,
-                       sizeof(double) * rsd::kPerPt * tp, sizeof(double) * 9,
-                       sizeof(double) * 2 * B,    sizeof(double) * 2 * B, sizeof(double) * 9 * B};
-  const size_t osz[] = {sizeof(double) * 9 * B, sizeof(rs_gs_info) * B, sizeof(double) * 9 * B,
-                        sizeof(double) * 3 * B, sizeof(int32_t) * B};
-  size_t extra = 0, oblk = 0;
-  for (size_t x : sz) extra += al(x);
-  for (size_t x : osz) oblk += al(x);
+  // the stages' buffers after the pair RANSAC's (L), then the output block (O, one download)
+  rs::Layout L, O;
+  const auto b_goff = L.add<int64_t>(B + 1);
+  const auto b_act = L.add<int32_t>(B);
+  const auto b_Fin = L.add<double>(9 * B);
+  const auto b_pl = L.add<double>(2 * tp), b_pr = L.add<double>(2 * tp);
+  const auto b_X = L.add<double>(3 * tp), b_Xw = L.add<double>(3 * tp);
+  const auto b_work = L.add<double>(rsd::kPerPt * tp);
+  const auto b_K = L.add<double>(9);
+  const auto b_y1 = L.add<double>(2 * B), b_y2 = L.add<double>(2 * B), b_E = L.add<double>(9 * B);
+  const auto o_Fg = O.add<double>(9 * B);
+  const auto o_info = O.add<rsd::GsInfo>(B);
+  const auto o_R = O.add<double>(9 * B), o_t = O.add<double>(3 * B);
+  const auto o_found = O.add<int32_t>(B);
   rs::PairsDev d{};
   int st = rs::pairs_enqueue(c, p1, p2, off, B, H, mode, seed_base, seed_ids, host_tuples,
-                             thresh, extra + oblk, &d);
+                             thresh, L.total() + O.total(), &d);
   if (st) return st;
-  std::vector<char *> b;
-  char *p = d.extra;
-  for (size_t x : sz) {
-    b.push_back(p);
-    p += al(x);
-  }
-  char *ob = p;
-  std::vector<char *> o;
-  for (size_t x : osz) {
-    o.push_back(p);
-    p += al(x);
-  }
-  auto *goff = reinterpret_cast<int64_t *>(b[0]);
-  auto *act = reinterpret_cast<int32_t *>(b[1]);
-  auto *Fin = reinterpret_cast<double *>(b[2]);
-  auto *pl = reinterpret_cast<double *>(b[3]), *pr = reinterpret_cast<double *>(b[4]);
-  auto *dK = reinterpret_cast<double *>(b[8]);
-  auto *dy1 = reinterpret_cast<double *>(b[9]), *dy2 = reinterpret_cast<double *>(b[10]);
-  auto *dE = reinterpret_cast<double *>(b[11]);
-  auto *dFg = reinterpret_cast<double *>(o[0]);
-  auto *dinfo = reinterpret_cast<rsd::GsInfo *>(o[1]);
-  auto *dR = reinterpret_cast<double *>(o[2]), *dt = reinterpret_cast<double *>(o[3]);
-  auto *dfound = reinterpret_cast<int32_t *>(o[4]);
+  L.bind(d.extra, nullptr);
+  O.bind(d.extra + L.total(), nullptr);
+  auto *goff = b_goff.dev();
+  auto *act = b_act.dev();
+  auto *Fin = b_Fin.dev(), *pl = b_pl.dev(), *pr = b_pr.dev();
+  auto *dK = b_K.dev(), *dy1 = b_y1.dev(), *dy2 = b_y2.dev(), *dE = b_E.dev();
+  auto *dFg = o_Fg.dev();
+  auto *dinfo = o_info.dev();
+  auto *dR = o_R.dev(), *dt = o_t.dev();
+  auto *dfound = o_found.dev();
   hipStream_t s = c->stream;
   if (K) {
     HIP_TRY(hipMemcpyAsync(dK, K, sizeof(double) * 9, hipMemcpyHostToDevice, s));
@@ -1212,27 +1171,27 @@ extern "C" int rs_pairs_two_view(rs_ctx *c, const double *p1, const double *p2, 
   hipLaunchKernelGGL(rsd::k_twoview_gather, dim3(static_cast<unsigned>(B)), dim3(64), 0, s,
                      static_cast<const rsd::Pt *>(d.pts), d.off, d.inl, goff, act, tp, pl, pr);
   hipLaunchKernelGGL(rsd::k_gold_standard<rsd::kGsT>, dim3(static_cast<unsigned>(B)), dim3(rsd::kGsT),
-                     0, s, Fin, pl, pr, tp, goff, max_iter, reinterpret_cast<double *>(b[5]),
-                     reinterpret_cast<double *>(b[6]), reinterpret_cast<double *>(b[7]), dFg,
-                     nullptr, dinfo, act);
+                     0, s, Fin, pl, pr, tp, goff, max_iter, b_X.dev(), b_Xw.dev(), b_work.dev(),
+                     dFg, nullptr, dinfo, act);
   if (K) {
-    hipLaunchKernelGGL(rsd::k_essential, dim3(grid(B)), dim3(128), 0, s, dK, 0, dFg, B, dE);
-    hipLaunchKernelGGL(rsd::k_relative_pose, dim3(grid(4 * B)), dim3(128), 0, s, dE, dy1, dy2, B,
-                       dR, dt, dfound, act);
+    hipLaunchKernelGGL(rsd::k_essential, dim3(blocks(B, 128)), dim3(128), 0, s, dK, 0, dFg, B, dE);
+    hipLaunchKernelGGL(rsd::k_relative_pose, dim3(blocks(4 * B, 128)), dim3(128), 0, s, dE, dy1,
+                       dy2, B, dR, dt, dfound, act);
   }
   HIP_TRY(hipGetLastError());
-  std::vector<char> host(static_cast<size_t>(p - ob));
+  std::vector<char> host(O.total());
+  O.bind(O.dev(), host.data());
   HIP_TRY(hipMemcpyAsync(out, d.res, sizeof(rs_pair_result) * B, hipMemcpyDeviceToHost, s));
   if (d.total > 0)
     HIP_TRY(hipMemcpyAsync(inliers, d.inl, sizeof(int32_t) * d.total, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(host.data(), ob, host.size(), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(O.host(), O.dev(), O.total(), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  std::memcpy(F_gold, host.data() + (o[0] - ob), osz[0]);
-  std::memcpy(info, host.data() + (o[1] - ob), osz[1]);
+  std::memcpy(F_gold, o_Fg.host(), o_Fg.bytes);
+  std::memcpy(info, o_info.host(), o_info.bytes);
   if (K) {
-    std::memcpy(R, host.data() + (o[2] - ob), osz[2]);
-    std::memcpy(t, host.data() + (o[3] - ob), osz[3]);
-    std::memcpy(found, host.data() + (o[4] - ob), osz[4]);
+    std::memcpy(R, o_R.host(), o_R.bytes);
+    std::memcpy(t, o_t.host(), o_t.bytes);
+    std::memcpy(found, o_found.host(), o_found.bytes);
   } else {
     for (int64_t i = 0; i < 9 * B; ++i) R[i] = __builtin_nan("");
     for (int64_t i = 0; i < 3 * B; ++i) t[i] = __builtin_nan("");

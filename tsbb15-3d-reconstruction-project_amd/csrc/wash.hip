@@ -35,8 +35,7 @@
 #include <cstring>
 #include <vector>
 
-#include "common.h"
-#include "ctx.h"
+#include "host.h"
 
 namespace rsd {
 
@@ -396,22 +395,11 @@ __global__ __launch_bounds__(64) void k_wash(WashArgs A) {
 
 }  // namespace rsd
 
-using rs::fail;
-using rs::hip_fail;
-
-#define HIP_TRY(expr)                                 \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
-
 namespace {
 
 constexpr int kClasses = 3;
 constexpr int kClassMax[kClasses] = {6, 12, RS_WASH_MAX_TRACK};  // MAXM of k_wash's three branches
 constexpr int kClassTeams[kClasses] = {8, 4, 1};                 // their 64 / T
-
-size_t al(size_t b) { return (b + 255) / 256 * 256; }
 
 // Both entry points: the CSR by point, the classes, one upload, one launch, one download.
 // point_keep is per point (nP); err2, obs_keep and info are filled in mode 0 only.
@@ -442,51 +430,48 @@ int wash_run(rs_ctx *c, int mode, const double *cams, int64_t nC, double *pts, i
 
   // one buffer: [cams | uv | ov | pt_off | pt_obs | list | pts] go up, [pts | err2 | obs_keep |
   // point_keep | point_fail | hyp] come down
-  const size_t D = sizeof(double), I = sizeof(int32_t);
-  const size_t sizes[] = {D * 12 * nC, D * 2 * n, I * n,  I * (nP + 1), I * n,  I * nP,
-                          D * 3 * nP,  D * n,     I * n,  I * nP,       I * nP, I * nP};
-  constexpr int kBufs = sizeof(sizes) / sizeof(sizes[0]);
-  size_t at[kBufs + 1] = {0};
-  for (int k = 0; k < kBufs; ++k) at[k + 1] = at[k] + al(sizes[k]);
+  rs::Layout L;
+  const auto b_cams = L.add<double>(12 * nC), b_uv = L.add<double>(2 * n);
+  const auto b_ov = L.add<int32_t>(n), b_pt_off = L.add<int32_t>(nP + 1);
+  const auto b_pt_obs = L.add<int32_t>(n), b_list = L.add<int32_t>(nP);
+  const auto b_pts = L.add<double>(3 * nP), b_err2 = L.add<double>(n);
+  const auto b_obs_keep = L.add<int32_t>(n), b_point_keep = L.add<int32_t>(nP);
+  const auto b_point_fail = L.add<int32_t>(nP), b_hyp = L.add<int32_t>(nP);
   HIP_TRY(hipSetDevice(c->device));
-  st = rs::ensure_scratch(c, at[kBufs] + 256);
+  st = L.bind(c, 256, L.total() + 256);
   if (st) return st;
-  st = rs::ensure_pinned(c, at[kBufs] + 256);
-  if (st) return st;
-  char *h = static_cast<char *>(c->pinned), *d = static_cast<char *>(c->scratch);
-  std::memcpy(h + at[0], cams, sizes[0]);
-  std::memcpy(h + at[1], uv, sizes[1]);
-  std::memcpy(h + at[2], obs_view, sizes[2]);
-  std::memcpy(h + at[3], pt_off.data(), sizes[3]);
+  std::memcpy(b_cams.host(), cams, b_cams.bytes);
+  std::memcpy(b_uv.host(), uv, b_uv.bytes);
+  std::memcpy(b_ov.host(), obs_view, b_ov.bytes);
+  std::memcpy(b_pt_off.host(), pt_off.data(), b_pt_off.bytes);
   {
-    int32_t *pt_obs = reinterpret_cast<int32_t *>(h + at[4]);
-    int32_t *list = reinterpret_cast<int32_t *>(h + at[5]);
+    int32_t *pt_obs = b_pt_obs.host(), *list = b_list.host();
     std::vector<int32_t> w(pt_off.begin(), pt_off.end() - 1);
     for (int64_t i = 0; i < n; ++i) pt_obs[w[obs_point[i]]++] = static_cast<int32_t>(i);
     int fill[kClasses] = {cls_off[0], cls_off[1], cls_off[2]};
     for (int64_t p = 0; p < nP; ++p) list[fill[cls[p]]++] = static_cast<int32_t>(p);
   }
-  std::memcpy(h + at[6], pts, sizes[6]);
+  std::memcpy(b_pts.host(), pts, b_pts.bytes);
 
   hipStream_t s = c->stream;
-  HIP_TRY(hipMemcpyAsync(d, h, at[7], hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(L.dev(), L.host(), L.upto(b_err2), hipMemcpyHostToDevice, s));
   rsd::WashArgs A;
-  A.cams = reinterpret_cast<const double *>(d + at[0]);
-  A.uv = reinterpret_cast<const double *>(d + at[1]);
-  A.ov = reinterpret_cast<const int32_t *>(d + at[2]);
-  A.pt_off = reinterpret_cast<const int32_t *>(d + at[3]);
-  A.pt_obs = reinterpret_cast<const int32_t *>(d + at[4]);
+  A.cams = b_cams.dev();
+  A.uv = b_uv.dev();
+  A.ov = b_ov.dev();
+  A.pt_off = b_pt_off.dev();
+  A.pt_obs = b_pt_obs.dev();
   A.mode = mode;
   A.t2 = thresh * thresh;
   A.min_views = min_views;
   A.depth_sign = depth_sign;
-  A.pts = reinterpret_cast<double *>(d + at[6]);
-  A.err2 = reinterpret_cast<double *>(d + at[7]);
-  A.obs_keep = reinterpret_cast<int32_t *>(d + at[8]);
-  A.point_keep = reinterpret_cast<int32_t *>(d + at[9]);
-  A.point_fail = reinterpret_cast<int32_t *>(d + at[10]);
-  A.hyp = reinterpret_cast<int32_t *>(d + at[11]);
-  A.list = reinterpret_cast<const int32_t *>(d + at[5]);
+  A.pts = b_pts.dev();
+  A.err2 = b_err2.dev();
+  A.obs_keep = b_obs_keep.dev();
+  A.point_keep = b_point_keep.dev();
+  A.point_fail = b_point_fail.dev();
+  A.hyp = b_hyp.dev();
+  A.list = b_list.dev();
   unsigned grid = 0;
   for (int k = 0; k < kClasses; ++k) {
     A.cls_off[k] = cls_off[k];
@@ -496,16 +481,15 @@ int wash_run(rs_ctx *c, int mode, const double *cams, int64_t nC, double *pts, i
   A.cls_off[kClasses] = cls_off[kClasses];
   if (grid > 0) hipLaunchKernelGGL(rsd::k_wash, dim3(grid), dim3(64), 0, s, A);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h + at[6], d + at[6], at[kBufs] - at[6], hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(b_pts.host(), b_pts.dev(), L.from(b_pts), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
 
-  std::memcpy(pts, h + at[6], sizes[6]);
-  std::memcpy(point_keep, h + at[9], sizes[9]);
+  std::memcpy(pts, b_pts.host(), b_pts.bytes);
+  std::memcpy(point_keep, b_point_keep.host(), b_point_keep.bytes);
   if (mode == 0) {
-    std::memcpy(err2, h + at[7], sizes[7]);
-    std::memcpy(obs_keep, h + at[8], sizes[8]);
-    const int32_t *pf = reinterpret_cast<const int32_t *>(h + at[10]);
-    const int32_t *hy = reinterpret_cast<const int32_t *>(h + at[11]);
+    std::memcpy(err2, b_err2.host(), b_err2.bytes);
+    std::memcpy(obs_keep, b_obs_keep.host(), b_obs_keep.bytes);
+    const int32_t *pf = b_point_fail.host(), *hy = b_hyp.host();
     rs_wash_info r = {0, 0, 0, 0, 0};
     for (int64_t p = 0; p < nP; ++p) {
       r.hypotheses += hy[p];
