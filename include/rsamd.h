@@ -886,6 +886,80 @@ int rs_dense_consistency(rs_ctx *ctx, const double *depth, int32_t V, int64_t h,
 int rs_dense_timing(rs_ctx *ctx, int32_t enable, double *ms);
 
 /* ------------------------------------------------------------------------------------------
+ * The surface stage (surface.hip): depth maps fused into a truncated signed distance volume and
+ * a welded, consistently oriented triangle mesh extracted from it.  The reference project has no
+ * such stage; nothing here restates code of it.  No atomics anywhere: the same inputs give
+ * bitwise the same outputs, whatever the launch shape.
+ *   Conventions are those of the dense stage: P = K C per view (3, 4) row-major, pixel centres
+ * at integers, the depth of X in a view is its third projective coordinate, and depths may be
+ * negative.  A volume is indexed [iz, iy, ix], x fastest; node (ix, iy, iz) lies at
+ * X = origin + voxel (ix, iy, iz).
+ * ------------------------------------------------------------------------------------------ */
+#define RS_SURFACE_MAX_SIDE 2048
+#define RS_SURFACE_MAX_NODES (1LL << 27)
+#define RS_SURFACE_SCAN_CHUNK 2048 /* nodes one workgroup scans (the size boundaries of a test) */
+
+/* TSDF fusion.  depth is (V, h, w) fp64 with NaN for "no depth", weights (V, h, w) float or null
+ * (1 everywhere), P (V, 3, 4).  Per node, the views in index order, all fp64:
+ *   q = P_v [X; 1], z = q2, u = floor(q0 / q2 + 0.5), v = floor(q1 / q2 + 0.5) (the rounding of
+ *   rs_dense_consistency).  View v contributes when 0 <= u <= w - 1 and 0 <= v <= h - 1,
+ *   d = depth[v, v, u] is finite, d z > 0, the weight sample wv is finite and > 0, and
+ *   s = |d| - |z| >= -trunc.  It then adds wv min(1, s / trunc) to acc and wv to wsum.
+ *   With the prior (T0, W0) of the node: W = W0 + wsum, T = (W0 T0 + acc) / W, NaN when W == 0;
+ *   T0 is ignored when W0 is not > 0.  Both are stored as float.
+ * tsdf and weight are (nz, ny, nx) float.  With has_prior != 0 they are read as the prior and
+ * overwritten, so that a later call adds views to a volume that exists; with has_prior == 0 they
+ * are only written.  A depth map is indexed only after the bounds test has passed.
+ * RS_EINVAL before any launch: a side of the volume outside 1..RS_SURFACE_MAX_SIDE,
+ * nx ny nz > RS_SURFACE_MAX_NODES, V outside 1..RS_DENSE_MAX_VIEWS, the image limits of
+ * rs_dense_consistency, a camera, origin or voxel not finite, voxel <= 0, trunc not finite
+ * or <= 0. */
+int rs_surface_integrate(rs_ctx *ctx, const double *depth, const float *weights, int32_t V,
+                         int64_t h, int64_t w, const double *P, const double *origin,
+                         double voxel, int64_t nz, int64_t ny, int64_t nx, double trunc,
+                         int32_t has_prior, float *tsdf, float *weight);
+
+/* Marching tetrahedra on the Kuhn decomposition of every cell.  The 6 x 16 case table follows
+ * from a three-line rule (csrc/surface_table.h holds it), and there are no ambiguous cases: the
+ * mesh is watertight by construction.  What follows fixes every output bit except the last ulps
+ * of the positions.
+ *   Negative node.  tsdf < 0; -0.0 and 0.0 are not negative.
+ *   Valid cell.  All 8 nodes have weight >= min_weight and a finite tsdf.
+ *   Tets.  Tet k (0..5) of a cell is the path 000 -> +e_a -> +e_b -> 111 with (a, b, c) the k-th
+ *   permutation of (x, y, z) in lexicographic order; its corners are numbered 0..3 along the path.
+ *   Edges.  Every tet edge joins a node o to o + e, e one of (dx, dy, dz) = (1,0,0), (0,1,0),
+ *   (0,0,1), (1,1,0), (1,0,1), (0,1,1), (1,1,1), its type 0..6 in that order; o owns the edge.
+ *   The decomposition is translation-consistent, so neighbouring cells share these edges.
+ *   Vertices.  One on an edge iff its two nodes differ in sign and at least one valid cell
+ *   contains the edge.  They are numbered by owner in row-major node order, then by edge type.
+ *   Position: origin + voxel (o + t e), t = fa / (fa - fb) in fp64 from the float values.  With
+ *   fa == 0 the vertex lands on the node; such degenerate triangles are kept, so that the mesh
+ *   stays combinatorially closed.
+ *   Triangles.  Ordered by valid cell (row-major), then by tet, then by the table's order.  One
+ *   corner of the other sign: one triangle on its three edges.  Two against two, n0, n1 the
+ *   negative and p0, p1 the positive corners in path order: the quad (n0,p0), (n0,p1), (n1,p1),
+ *   (n1,p0), split along (n0,p0)-(n1,p1).
+ *   Winding.  The geometric normal points to the positive side.  It comes from the table, never
+ *   from computed coordinates: an entry is derived once with every vertex at its edge midpoint
+ *   and oriented against the vector from the negative corners' centroid to the positive ones'.
+ * vertices is (vcap, 3) fp64 and faces (fcap, 3) int32, provided by the caller (either may be
+ * null with capacity 0).  *nv and *nf are always set, to 0 on an argument error and otherwise to
+ * the mesh's size.  RS_EINVAL, and no mesh written, when nv > vcap, nf > fcap, or nv or 3 nf
+ * exceeds 2^31 - 1: a call with zero capacities learns the sizes, a second one with exact arrays
+ * fetches the mesh.  Also RS_EINVAL: the volume limits of rs_surface_integrate, min_weight not
+ * finite or <= 0, a negative capacity. */
+int rs_surface_extract(rs_ctx *ctx, const float *tsdf, const float *weight, int64_t nz,
+                       int64_t ny, int64_t nx, const double *origin, double voxel,
+                       double min_weight, double *vertices, int64_t vcap, int32_t *faces,
+                       int64_t fcap, int64_t *nv, int64_t *nf);
+
+/* HIP events around the kernels of the next surface calls (enable != 0).  Returns the last timed
+ * calls' device ms: slot 0 integrate, 1 classify (cells and nodes), 2 scan (both scans), 3 emit
+ * (vertices and faces); -1 where none (tools/bench_surface.py). */
+#define RS_SURFACE_TIMING_SLOTS 4
+int rs_surface_timing(rs_ctx *ctx, int32_t enable, double *ms);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU (RCCL over xGMI).  One process per GPU; the unique id travels out of band.
  * ---------------------------------------------------------------------------------------- */
 #define RS_COMM_ID_BYTES 128

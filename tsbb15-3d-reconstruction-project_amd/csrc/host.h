@@ -116,6 +116,9 @@ struct rs_ctx {
   // rs_dense_timing: around the kernel of the next dense calls (dense.hip): plane sweep,
   // consistency
   rs::StageTimer<2, RS_DENSE_TIMING_SLOTS> dense{-1.0};
+  // rs_surface_timing: around the kernels of the next surface calls (surface.hip): integrate,
+  // classify, scan, emit
+  rs::StageTimer<5, RS_SURFACE_TIMING_SLOTS> surface{-1.0};
 };
 
 namespace rs {

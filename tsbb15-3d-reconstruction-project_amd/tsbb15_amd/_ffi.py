@@ -216,6 +216,13 @@ _SIGS = {
     "rs_dense_consistency": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_int64, C.c_int64, _dp,
                                        _dp, C.c_double, _u8p]),
     "rs_dense_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "rs_surface_integrate": (C.c_int, [C.c_void_p, _dp, _fp, C.c_int32, C.c_int64, C.c_int64, _dp,
+                                       _dp, C.c_double, C.c_int64, C.c_int64, C.c_int64,
+                                       C.c_double, C.c_int32, _fp, _fp]),
+    "rs_surface_extract": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int64, C.c_int64, C.c_int64, _dp,
+                                     C.c_double, C.c_double, _dp, C.c_int64, _i32p, C.c_int64,
+                                     _i64p, _i64p]),
+    "rs_surface_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
     "rs_np_shard_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.POINTER(C.c_void_p)]),
     "rs_np_shard_destroy": (C.c_int, [C.c_void_p]),

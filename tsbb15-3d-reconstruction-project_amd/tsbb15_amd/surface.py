@@ -1,0 +1,311 @@
+"""The surface stage (HIP kernels of surface.hip): depth maps fused into a truncated signed
+distance volume, a triangle mesh extracted from it, and the mesh written as PLY.  The reference
+project's final artefact is a .ply of vertices without a face, written by an outside tool; it
+has no such stage and nothing here restates code of it.
+
+  * ``integrate``       TSDF fusion of V depth maps into a volume (rs_surface_integrate)
+  * ``extract``         marching tetrahedra: welded vertices and oriented faces
+                        (rs_surface_extract)
+  * ``bounds``          origin and dims of a volume that encloses a cloud (host)
+  * ``vertex_normals``  area-weighted normals (host)
+  * ``save_ply`` / ``load_ply``   binary little-endian PLY (host)
+  * ``reconstruct``     ``dense.fuse`` -> ``integrate`` -> ``extract``
+
+Conventions are those of ``dense``: cameras are the project's normalised (3, 4) ``C``,
+``P = K @ C``, pixel centres at integers, the depth of X in a view is ``C[2] @ [X; 1]`` and may
+be negative.  A volume is indexed ``[iz, iy, ix]``; its node (ix, iy, iz) lies at
+``origin + voxel * (ix, iy, iz)``.  The contract of both kernels stands in include/rsamd.h.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _ffi, dense
+
+_d = _ffi.C.c_double
+_f = _ffi.C.c_float
+_i32 = _ffi.C.c_int32
+
+MAX_SIDE = 2048
+MAX_NODES = 1 << 27
+MAX_VIEWS = dense.MAX_VIEWS
+STAGES = ("integrate", "classify", "scan", "emit")
+
+
+def _ctx(ctx):
+    return (ctx or _ffi.default_context()).handle
+
+
+def _grid(origin, voxel, dims):
+    origin = _ffi.f64c(origin).reshape(-1)
+    if origin.shape != (3,) or not np.all(np.isfinite(origin)):
+        raise ValueError('origin must be three finite numbers')
+    voxel = float(voxel)
+    if not np.isfinite(voxel) or not voxel > 0.0:
+        raise ValueError('voxel must be finite and positive')
+    try:
+        dims = tuple(int(n) for n in dims)
+    except TypeError:
+        raise ValueError('dims must be (nz, ny, nx)') from None
+    if len(dims) != 3:
+        raise ValueError('dims must be (nz, ny, nx)')
+    if min(dims) < 1 or max(dims) > MAX_SIDE:
+        raise ValueError('each side of the volume must be in 1..2048')
+    if dims[0] * dims[1] * dims[2] > MAX_NODES:
+        raise ValueError('a volume of more than 2^27 nodes')
+    return origin, voxel, dims
+
+
+def _volume(a, name, dims=None):
+    a = np.asarray(a)
+    if a.dtype != np.float32 or a.ndim != 3 or (dims is not None and a.shape != dims):
+        raise ValueError(f'{name} must be a float32 volume' +
+                         (f' of shape {dims}' if dims is not None else ' (nz, ny, nx)'))
+    return np.ascontiguousarray(a)
+
+
+def integrate(depth_maps, cams, K, origin, voxel, dims, trunc, weights=None, tsdf=None,
+              weight=None, ctx=None):
+    """TSDF fusion (rs_surface_integrate).  depth_maps is (V, h, w) float64 with NaN for "no
+    depth", cams (V, 3, 4), ``weights`` (V, h, w) float32 or None for 1 everywhere.
+
+    Per node X and view v, in index order and in fp64: q = P_v [X; 1], z = q[2], the pixel is
+    (floor(q0 / z + 0.5), floor(q1 / z + 0.5)).  The view contributes when the pixel is inside,
+    its depth d is finite, d z > 0, its weight wv is finite and > 0 and s = |d| - |z| >= -trunc;
+    it adds wv min(1, s / trunc) to acc and wv to wsum.  W = W0 + wsum and
+    T = (W0 T0 + acc) / W, NaN when W == 0.
+
+    Returns (tsdf, weight), float32 (nz, ny, nx).  Given a running ``tsdf`` and ``weight`` (both
+    or neither) the views are added to that volume; the arrays passed in are not modified.
+
+    ValueError before any launch: a side of the volume outside 1..2048, more than 2^27 nodes, V
+    outside 1..128, the image limits of ``dense.consistency``, cameras, origin or voxel not
+    finite, voxel or trunc <= 0, shapes that do not match, a running volume of the wrong shape
+    or dtype."""
+    K = dense._calibration(K)
+    depth = _ffi.f64c(depth_maps)
+    cams = dense._cameras(cams, 'cams')
+    if depth.ndim != 3 or len(depth) != len(cams):
+        raise ValueError('depth_maps must be (V, h, w), one per camera')
+    V, h, w = depth.shape
+    if not 1 <= V <= MAX_VIEWS:
+        raise ValueError('1 to 128 views')
+    if min(h, w) < 1 or max(h, w) > dense.MAX_SIDE or h * w > dense.MAX_PIXELS or \
+            V * h * w > dense.MAX_VOLUME:
+        raise ValueError('depth maps of more than 2^26 pixels each or 2^28 in all')
+    origin, voxel, dims = _grid(origin, voxel, dims)
+    trunc = float(trunc)
+    if not np.isfinite(trunc) or not trunc > 0.0:
+        raise ValueError('trunc must be finite and positive')
+    if weights is not None:
+        weights = np.asarray(weights)
+        if weights.dtype != np.float32 or weights.shape != depth.shape:
+            raise ValueError('weights must be float32 of the depth maps\' shape')
+        weights = np.ascontiguousarray(weights)
+    if (tsdf is None) != (weight is None):
+        raise ValueError('a running volume is tsdf and weight together')
+    prior = tsdf is not None
+    if prior:
+        tsdf = _volume(tsdf, 'tsdf', dims).copy()
+        weight = _volume(weight, 'weight', dims).copy()
+    else:
+        tsdf, weight = np.empty(dims, np.float32), np.empty(dims, np.float32)
+    P = np.ascontiguousarray(K @ cams)
+    _ffi.check(_ffi.lib().rs_surface_integrate(
+        _ctx(ctx), _ffi.ptr(depth, _d), _ffi.ptr(weights, _f) if weights is not None else None,
+        V, h, w, _ffi.ptr(P, _d), _ffi.ptr(origin, _d), voxel, dims[0], dims[1], dims[2], trunc,
+        int(prior), _ffi.ptr(tsdf, _f), _ffi.ptr(weight, _f)))
+    return tsdf, weight
+
+
+def extract(tsdf, weight, origin, voxel, min_weight=2.0, ctx=None):
+    """Marching tetrahedra on the Kuhn decomposition of every cell (rs_surface_extract).
+
+    A cell is valid when all 8 nodes have weight >= min_weight and a finite tsdf; a node is
+    negative iff tsdf < 0.  A vertex sits on a tet edge whose nodes differ in sign and that a
+    valid cell contains, at origin + voxel (o + t e) with t = fa / (fa - fb); vertices are
+    numbered by owning node in row-major order, then by edge type, and faces by cell, tet and
+    the case table's order.  The geometric normal of a face points to the positive side.
+
+    Returns (vertices (Nv, 3) float64, faces (Nf, 3) int32); both are empty for a volume
+    without a sign change in a valid cell.  The ABI is called twice: once with zero capacities
+    for the sizes and once with exact arrays.
+
+    ValueError before any launch: tsdf or weight not a 3-D float32 volume or of different
+    shapes, the volume limits of ``integrate``, origin or voxel not finite, voxel <= 0,
+    min_weight not finite or <= 0."""
+    tsdf = _volume(tsdf, 'tsdf')
+    weight = _volume(weight, 'weight', tsdf.shape)
+    origin, voxel, dims = _grid(origin, voxel, tsdf.shape)
+    min_weight = float(min_weight)
+    if not np.isfinite(min_weight) or not min_weight > 0.0:
+        raise ValueError('min_weight must be finite and positive')
+    lib, h = _ffi.lib(), _ctx(ctx)
+    nv, nf = _ffi.C.c_int64(-1), _ffi.C.c_int64(-1)
+
+    def call(vertices, faces):
+        return lib.rs_surface_extract(
+            h, _ffi.ptr(tsdf, _f), _ffi.ptr(weight, _f), dims[0], dims[1], dims[2],
+            _ffi.ptr(origin, _d), voxel, min_weight,
+            _ffi.ptr(vertices, _d) if len(vertices) else None, len(vertices),
+            _ffi.ptr(faces, _i32) if len(faces) else None, len(faces),
+            _ffi.C.byref(nv), _ffi.C.byref(nf))
+
+    vertices, faces = np.empty((0, 3)), np.empty((0, 3), np.int32)
+    st = call(vertices, faces)
+    if st != 0 and nv.value <= 0 and nf.value <= 0:
+        _ffi.check(st)                     # an error, not "the mesh does not fit"
+    if nv.value > 0 or nf.value > 0:
+        if nv.value > 2**31 - 1 or 3 * nf.value > 2**31 - 1:
+            _ffi.check(st)
+        vertices = np.empty((nv.value, 3))
+        faces = np.empty((nf.value, 3), np.int32)
+        _ffi.check(call(vertices, faces))
+    return vertices, faces
+
+
+def bounds(points, voxel, margin=0.0):
+    """(origin (3,), dims (nz, ny, nx)) of the smallest volume of `voxel` spacing whose nodes
+    enclose the finite points of an (N, 3) cloud -- the cloud of ``dense.fuse`` for instance --
+    with `margin` (world units) around it."""
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    pts = pts[np.all(np.isfinite(pts), axis=1)]
+    voxel, margin = float(voxel), float(margin)
+    if not len(pts):
+        raise ValueError('no finite point')
+    if not np.isfinite(voxel) or not voxel > 0.0 or not np.isfinite(margin) or margin < 0.0:
+        raise ValueError('voxel must be finite and positive, margin finite and not negative')
+    lo, hi = pts.min(axis=0) - margin, pts.max(axis=0) + margin
+    n = np.ceil((hi - lo) / voxel).astype(np.int64) + 1      # nodes per axis, x y z
+    return lo, (int(n[2]), int(n[1]), int(n[0]))
+
+
+def vertex_normals(vertices, faces):
+    """Unit vertex normals (Nv, 3): the sum of the adjacent faces' normals, each weighted by the
+    face's area.  A vertex without a face of non-zero area gets a zero normal.  Host numpy."""
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    fn = np.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])   # |fn| = 2 area
+    n = np.zeros_like(v)
+    for k in range(3):
+        np.add.at(n, f[:, k], fn)
+    length = np.linalg.norm(n, axis=1, keepdims=True)
+    return np.divide(n, length, out=np.zeros_like(n), where=length > 0)
+
+
+def save_ply(path, vertices, faces=None, normals=None, colors=None):
+    """Binary little-endian PLY: float x y z, optional float nx ny nz, optional uchar red green
+    blue, and the faces as ``list uchar int vertex_indices`` (an ``element face 0`` without
+    faces).  colors are uint8, or floats in [0, 1] as ``cloud`` gives them."""
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    f = np.zeros((0, 3), np.int32) if faces is None else np.asarray(faces).reshape(-1, 3)
+    fields = [(n, '<f4') for n in 'xyz']
+    props = [f'property float {n}' for n in 'xyz']
+    if normals is not None:
+        normals = np.asarray(normals, dtype=np.float64).reshape(-1, 3)
+        if len(normals) != len(v):
+            raise ValueError('one normal per vertex')
+        fields += [(n, '<f4') for n in ('nx', 'ny', 'nz')]
+        props += [f'property float {n}' for n in ('nx', 'ny', 'nz')]
+    if colors is not None:
+        colors = np.asarray(colors).reshape(-1, 3)
+        if len(colors) != len(v):
+            raise ValueError('one colour per vertex')
+        if colors.dtype != np.uint8:
+            colors = np.clip(np.rint(colors.astype(np.float64) * 255.0), 0, 255).astype(np.uint8)
+        fields += [(n, 'u1') for n in ('red', 'green', 'blue')]
+        props += [f'property uchar {n}' for n in ('red', 'green', 'blue')]
+    if len(f) and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError('a face index is out of range')
+    rec = np.zeros(len(v), dtype=fields)
+    for k, n in enumerate('xyz'):
+        rec[n] = v[:, k]
+    if normals is not None:
+        for k, n in enumerate(('nx', 'ny', 'nz')):
+            rec[n] = normals[:, k]
+    if colors is not None:
+        for k, n in enumerate(('red', 'green', 'blue')):
+            rec[n] = colors[:, k]
+    frec = np.zeros(len(f), dtype=[('n', 'u1'), ('i', '<i4', (3,))])
+    frec['n'] = 3
+    frec['i'] = f
+    header = ['ply', 'format binary_little_endian 1.0', f'element vertex {len(v)}'] + props + \
+        [f'element face {len(f)}', 'property list uchar int vertex_indices', 'end_header']
+    with open(path, 'wb') as fh:
+        fh.write(('\n'.join(header) + '\n').encode('ascii'))
+        fh.write(rec.tobytes())
+        fh.write(frec.tobytes())
+
+
+def load_ply(path):
+    """What ``save_ply`` writes, read back: a dict with vertices (Nv, 3) float64, faces (Nf, 3)
+    int32, and normals (float64) and colors (uint8) or None.  Only that layout is understood:
+    binary little-endian, float and uchar vertex properties, triangles."""
+    with open(path, 'rb') as fh:
+        data = fh.read()
+    end = data.find(b'end_header\n')
+    if not data.startswith(b'ply\n') or end < 0:
+        raise ValueError('not a PLY file')
+    lines = data[:end].decode('ascii').split('\n')
+    body = data[end + len(b'end_header\n'):]
+    if lines[1].strip() != 'format binary_little_endian 1.0':
+        raise ValueError('only binary little-endian PLY is read')
+    counts, fields, element = {}, [], None
+    kinds = {'float': '<f4', 'uchar': 'u1'}
+    for line in lines[2:]:
+        tok = line.split()
+        if not tok or tok[0] == 'comment':
+            continue
+        if tok[0] == 'element':
+            element = tok[1]
+            counts[element] = int(tok[2])
+        elif tok[0] == 'property' and element == 'vertex':
+            if tok[1] not in kinds:
+                raise ValueError(f'vertex property type {tok[1]} is not read')
+            fields.append((tok[2], kinds[tok[1]]))
+        elif tok[0] == 'property' and element == 'face':
+            if tok[1:4] != ['list', 'uchar', 'int']:
+                raise ValueError('faces must be list uchar int')
+    nv, nf = counts.get('vertex', 0), counts.get('face', 0)
+    vdt = np.dtype(fields)
+    fdt = np.dtype([('n', 'u1'), ('i', '<i4', (3,))])
+    if len(body) < nv * vdt.itemsize + nf * fdt.itemsize:
+        raise ValueError('the PLY file is truncated')
+    rec = np.frombuffer(body, dtype=vdt, count=nv)
+    frec = np.frombuffer(body, dtype=fdt, count=nf, offset=nv * vdt.itemsize)
+    if nf and np.any(frec['n'] != 3):
+        raise ValueError('only triangles are read')
+    names = rec.dtype.names or ()
+
+    def cols(keys, dtype):
+        if not all(k in names for k in keys):
+            return None
+        return np.stack([rec[k] for k in keys], axis=1).astype(dtype)
+
+    return {"vertices": cols('xyz', np.float64), "faces": frec['i'].astype(np.int32).reshape(-1, 3),
+            "normals": cols(('nx', 'ny', 'nz'), np.float64),
+            "colors": cols(('red', 'green', 'blue'), np.uint8)}
+
+
+def reconstruct(images, cams, K, depths, origin, voxel, dims, trunc, min_weight=2, ctx=None,
+                **fuse_kw):
+    """Posed images to a mesh: ``dense.fuse(..., return_maps=True)``, the depth set to NaN where
+    ``keep`` is false, ``integrate`` with ``count`` as the weight, ``extract``.  ``fuse_kw`` goes
+    to ``dense.fuse``.  Returns (vertices, faces, tsdf, weight)."""
+    fuse_kw.pop('return_maps', None)
+    maps = dense.fuse(images, cams, K, depths, return_maps=True, ctx=ctx, **fuse_kw)[-1]
+    depth = np.where(maps["keep"], maps["depth"], np.nan)
+    tsdf, weight = integrate(depth, cams, K, origin, voxel, dims, trunc,
+                             weights=maps["count"].astype(np.float32), ctx=ctx)
+    vertices, faces = extract(tsdf, weight, origin, voxel, min_weight=min_weight, ctx=ctx)
+    return vertices, faces, tsdf, weight
+
+
+def timing(enable, ctx=None):
+    """Enable / disable HIP events around the kernels of the next surface calls
+    (rs_surface_timing); returns the last timed calls' {integrate, classify, scan, emit: device
+    ms}, -1 where none."""
+    ctx = ctx or _ffi.default_context()
+    ms = np.zeros(len(STAGES))
+    _ffi.check(_ffi.lib().rs_surface_timing(ctx.handle, int(enable), _ffi.ptr(ms, _d)))
+    return dict(zip(STAGES, ms.tolist()))
