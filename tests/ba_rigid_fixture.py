@@ -54,6 +54,39 @@ def ring_problem(nC=42, nP=60, seed=0, noise=1e-4):
     return dict(cams=cams, pts=pts, ov=ov, op=op, uv=uv)
 
 
+# The rings of tests/test_ba_shapes_cpu.py and tests/test_gpu_ba_large.py: cameras -> (points,
+# observations).  nP >= nC - 1, so every track length 2 .. nC occurs.  Each camera count is the
+# smallest that reaches a branch of k_ba_chol / k_ba_final (or the largest that stays below it);
+# test_ba_shapes_cpu.py has the table.
+LARGE_RINGS = {22: (40, 461), 23: (40, 464), 43: (60, 1134), 44: (60, 1159), 45: (60, 1186),
+               88: (100, 4019), 128: (130, 8264)}
+LARGE_FREE12 = (22, 23, 45, 88, 128)
+LARGE_RIGID = (43, 44, 88, 128)
+_rings = {}
+
+
+def large_ring(nC):
+    """``ring_problem(nC, LARGE_RINGS[nC][0])``, built once and read-only."""
+    if nC not in _rings:
+        P = ring_problem(nC, LARGE_RINGS[nC][0])
+        for a in P.values():
+            a.setflags(write=False)
+        _rings[nC] = P
+    return _rings[nC]
+
+
+def short_track_ring(nC, keep=4):
+    """``large_ring(nC)`` with every track cut to its first ``keep`` views (point j starts at
+    view j % nC): a chain around the ring in which most pairs of cameras share no point, so most
+    pair blocks of the reduced system are zero.  Every camera is still observed."""
+    P = large_ring(nC)
+    sel = (P["ov"].astype(np.int64) - P["op"] % nC) % nC < keep
+    out = dict(cams=P["cams"], pts=P["pts"], ov=P["ov"][sel], op=P["op"][sel], uv=P["uv"][sel])
+    for a in out.values():
+        a.setflags(write=False)
+    return out
+
+
 def depths(prob):
     c = prob["cams"][prob["ov"]]
     return np.einsum('nj,nj->n', c[:, 2, :3], prob["pts"][prob["op"]]) + c[:, 2, 3]

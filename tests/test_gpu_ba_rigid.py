@@ -5,8 +5,10 @@ dense solve.
 
 Shapes.  2x20: one free camera, a 6 x 6 system inside one 12-wide block column.  4x30: three
 free cameras (odd: half a block column of padding).  5x40, 7x70: the shapes of
-tests/test_gpu_ba.py.  ring 42x60: 41 free cameras, 246 columns, past the 240-column LDS tile of
-the Cholesky panel.  3x676 fully visible: camera rows longer than an LDS tile.
+tests/test_gpu_ba.py.  ring 42x60: 41 free cameras, an odd count, 246 columns padded to 252; the
+last block column starts at 240, exactly the end of the 240-column LDS tile of the Cholesky
+panel, so the tile is filled once and never passed (tests/test_gpu_ba_large.py has the rings that
+pass it).  3x676 fully visible: camera rows longer than an LDS tile.
 
 Bars.  One step (and the 3-step runs): the step of the returned 3 x 4 cameras and of the points
 within STEP_BAR = 1e-8 of the largest step component (the reference's Schur route and a dense
@@ -197,7 +199,8 @@ def test_single_camera_equals_bundle_adjust_bitwise(ctx):
 
 
 # ------------------------------------------------------------------------------------------
-# 5. 41 free cameras: an odd count, and more columns than the Cholesky panel's LDS tile
+# 5. 41 free cameras: an odd count, 246 columns padded to 252, and the last block column
+#    starting exactly at the end of the Cholesky panel's LDS tile (one full tile, one pass)
 # ------------------------------------------------------------------------------------------
 def test_ring_of_42_cameras(ctx):
     if "ring" not in _cache:

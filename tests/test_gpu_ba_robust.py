@@ -6,7 +6,8 @@ linear references.
 
 Shapes (dirty: ba_robust_fixture, wash_fixture's displacement rule).  2x20: one free camera.
 4x30: three free cameras, an odd count, a padded rigid system.  7x70.  Ring 42x60, rigid: 246
-columns, past the 240-column Cholesky tile.  3x676 fully visible: camera rows longer than the
+columns padded to 252, one full 240-column Cholesky tile (the second pass over the tile is run by
+tests/test_gpu_ba_large.py, 44 cameras).  3x676 fully visible: camera rows longer than the
 256-observation LDS tile, so the weights of k_ba_camera<6, true> are staged over three tiles.
 
 Bars.  Steps (max_iter 1 and 3, start sigma 1e-3, f_scale 3e-4): STEP_BAR = 1e-8 of the largest
