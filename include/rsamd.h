@@ -259,6 +259,16 @@ int rs_f8_plan_lane_waits(rs_f8_plan *plan, int64_t *waits);
  * run that was not pruned reports K = npad and no survivors.  Results are those of the
  * unpruned count in every field; rs_f8_plan_counts recounts after a pruned run. */
 int rs_f8_plan_prune_stats(rs_f8_plan *plan, int64_t out[4]);
+/* The carried bound (fp32 counting, RSAMD_PRUNE=1, RSAMD_CARRY=1): a run on a stream lane whose
+ * previous run had the same H and threshold over the same points has no sample; its L (as
+ * rs_f8_plan_prune_stats reports it) is that run's best count less a gap (RSAMD_CARRY_GAP).  Such
+ * a run is exact when the best full count among its survivors reaches L, which is checked on the
+ * device; otherwise every hypothesis is counted again without pruning (the run "fell back").
+ * Results are those of the unpruned count either way.  out = {runs carried since the plan was
+ * created, runs among them that fell back, whether the last run was carried, whether it fell
+ * back}.  set_points, a retarget, rs_f8_plan_set_count_precision and a run with another H or
+ * threshold end the carry: the next run on each lane takes a sample again. */
+int rs_f8_plan_carry_stats(rs_f8_plan *plan, int64_t out[4]);
 /* The counting stages' own per-hypothesis counts of the last run, with no recount (test &
  * diagnostics).  After a pruned run: the full count of a sample hypothesis or a survivor, and
  * for a dropped hypothesis K minus its certified outliers among the first K points, an upper

@@ -52,6 +52,9 @@ struct SolveArgs {
   double gT, gDe, gDn;  // their inputs: (t/s)^2 and the fp32 error bounds of e and m
   int *pw;       // pruned count: the run's kPruneWords words zeroed, may be null
   int *gdone_b;  // ... and the rest stage's per-group finish counters
+  // carried run (above k_f8_count32q, "Carried bound"): the check stage's storage zeroed, its
+  // counts, per-group finish counters and c* word; all null otherwise
+  int *counts_fb, *gdone_fb, *fbw;
 };
 
 // One run's selection tail (candidates, reference statistics, replay, S_RANSAC).
@@ -71,6 +74,12 @@ struct TailArgs {
   F8DevResult *res;   // HBM result (header + S_RANSAC)
   F8DevResult *hres;  // pinned host header slot (device mapping), may be null
   int *hinl;          // pinned host S_RANSAC (int32, device mapping), may be null
+  int *carry;         // the lane's carry word: the run's c* is left there, may be null
+  // carried run: the prune words, the check stage's counts and c* word, the plan's fallback
+  // counter; the tail takes c* and the counts from the check stage's storage when the run fell
+  // back (carry_fell_back); all null otherwise
+  const int *pw, *counts_fb, *fbw;
+  int *n_fb;
 };
 
 hipError_t launch_pack_points(const double *p1, const double *p2, int n, Pt *pts,
@@ -121,6 +130,11 @@ struct PruneArgs {
   int g_first;   // hypothesis groups counted in full by the sample stage
   int margin;    // m: K = roundup8(n - L + m)
   int min_skip;  // fewer points than this to skip: K = npad, nothing is pruned
+  // carried run: L = *carry - gap instead of status[0] (null: the sample's L); cf: the run's
+  // status word c_f, which the check stage reads and never writes
+  const int *carry;
+  int gap;
+  const int *cf;
 };
 // sh: the shape of the groups past g_first over the whole window (the prefix stage cuts its
 // slices from K on the device); H is the run's hypothesis count
@@ -136,6 +150,14 @@ hipError_t launch_f8_count32q_rest(const float4 *ptsq, const Pt *pts, int n, int
                                    const Count32qShape &bound, const GuardW &g, int *counts,
                                    hipStream_t s, int *status, const float4 *G4,
                                    const PruneArgs &pa);
+// The check stage of a carried run: a whole-window count of all H hypotheses into counts / gdone /
+// fbw (the check stage's own storage) when the run fell back (K < npad and c_f < L, read from
+// pa.pw and pa.cf, which no wave of this launch writes); otherwise every workgroup returns at once
+hipError_t launch_f8_count32q_check(const float4 *ptsq, const Pt *pts, int n, int H,
+                                    const float *F32soa, const double *Fsoa, int64_t ld,
+                                    const Count32qShape &sh, const GuardW &g, int *counts,
+                                    hipStream_t s, int *gdone, int *fbw, const float4 *G4,
+                                    const PruneArgs &pa);
 hipError_t launch_f8_count(const Pt *pts, int n, int H, const double *Fsoa, int64_t ld,
                            int chunk, double thr2, int *counts, hipStream_t s,
                            const int *Hdev = nullptr, const int *Hmap = nullptr);

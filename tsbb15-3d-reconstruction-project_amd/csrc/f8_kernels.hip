@@ -73,6 +73,11 @@ __device__ __forceinline__ void solve_one(const SolveArgs &a, int h) {
     }
     if ((h & 63) == 0) a.gdone_b[h >> 6] = 0;
   }
+  if (a.counts_fb) {  // a carried run's check stage accumulates into storage of its own
+    a.counts_fb[h] = 0;
+    if ((h & 63) == 0) a.gdone_fb[h >> 6] = 0;
+    if (h == 0) a.fbw[0] = 0;
+  }
   int idx[8];
   if (mode == RSD_SAMPLER_PHILOX) {
     floyd_sample<8>(seed, hyp_offset + static_cast<uint64_t>(h), n, idx);
@@ -310,6 +315,43 @@ __global__ __launch_bounds__(256) void k_f8_count(const Pt *__restrict__ pts, in
 // (20.2), C5 3.81-3.83 ms against 4.71-4.77 ms (0.81).  RSAMD_PRUNE=0 stays inside the parent's
 // range in both sessions.  n / 8 as the least skip worth pruning for never bound at C2 or C5
 // (both prune, both gain) and stays as first set.
+//
+// Carried bound (RSAMD_CARRY; the plan decides on the host which runs take it, f8_plan.hip).  The
+// sample stage exists only to produce L: it scores 2 % of the plane in a launch of its own on
+// the lane's serial chain, and its L is weak (the best of 2048 hypotheses).  The points of a plan
+// change only through set_points or a retarget, so the c* of the lane's runs are draws from one
+// distribution, and the c* of the lane's previous run less a gap g is a far better guess L_g.  A
+// guess is no bound, but it is verified exactly after the fact.  Let c_f be the largest full count
+// among the survivors of a run screened against L_g (every group, no sample).  If c* >= L_g, every
+// hypothesis with count >= c* - 1 >= L_g - 1 survived (the survivor rule above holds for any L
+// whatever: c' + (n - K) >= its full count), so c_f = c* >= L_g.  Conversely c_f >= L_g gives
+// c* >= c_f >= L_g.  So the run is exact if and only if c_f >= L_g, and then status[0] = c_f = c*
+// and the tail sees what it would have seen; otherwise nothing is known and the run is counted
+// again without pruning.  When K = npad (L_g <= 1 or too little to skip) nothing was dropped and
+// the run is exact whatever L_g.  Three launches in stream order, every decision on the device:
+//   prefix  (kCountPrefix, g_first = 0) L_g = *carry - gap, read from the lane's carry word, which
+//           the tail of the lane's previous run wrote in an earlier launch on the same stream
+//           (cand_stats_block: it holds that run's final c*); K, the screen and the survivor list
+//           as above
+//   rest    (kCountRest) unchanged: the survivors over the whole window, c_f into status[0]
+//   check   (kCountCheck) carry_fell_back, K < npad and status[0] < L_g, read from pw[] and
+//           status[0], which no wave of this launch writes: if false every workgroup returns at
+//           once (a grid of one slice per resident wave); if true a whole-window count of all H
+//           hypotheses into storage of its own (counts_fb, gdone_fb, c* in fbw[0], zeroed by the
+//           solve as counts is)
+// The tail makes the same test and takes c*, the counts and max_count_fast from the check stage's
+// storage when it holds, leaves c* in the lane's carry word for the lane's next run, and counts
+// the fallbacks.  rs_f8_plan_counts / stage_counts follow the same choice.  No cross-lane event,
+// no host read and no host wait: the word is per lane and stream order covers it.
+// Measured against the parent commit's library (profiles/carry/ab.txt, tools/carry_ab.sh; the
+// CPU model is tools/carry_model.py): C2 bench value 1.676-1.727e9 against 1.520-1.557e9
+// hypotheses/s (1.10 x, five interleaved rounds, every line of one arm outside the other's range),
+// the count between the timing events 62.3-65.3 us against 70.4-71.9 us; kernel trace of the bench:
+// the sample (12.7 us x 300) is gone but for each lane's first run, the check is 5.9 us (2.6 alone)
+// and was empty in all 298 carried runs, prefix and rest are unchanged (43.9 and 28.2 us): the
+// sample's L at C2 is within 40 of c* already, so the gain is the launch, not the bound.  C5
+// 2.09-2.13 ms against 2.34-2.36 ms.  The gap g = max(16, n / 50) is from the sweep recorded
+// beside kCarryGapDiv (f8_plan.hip).
 // ----------------------------------------------------------------------------------------
 
 // The float64 test of k_f8_count (pixel units) for one (hypothesis, point).
@@ -345,6 +387,16 @@ __device__ __forceinline__ void group_done_max(int *counts, int *gdone, int *sta
 // Stages of the pruned count (k_f8_count32q's MODE): the whole window, the prefix [0, K) of the
 // groups past the sample (screened), the survivors over the whole window again.
 constexpr int kCountWhole = 0, kCountPrefix = 1, kCountRest = 2;
+// ... and the check stage of a carried run: the whole window again, into storage of its own, only
+// when the carried bound turned out to be above c*
+constexpr int kCountCheck = 3;
+
+// A carried run fell back: it pruned (K = pw[2] < npad) against a bound L = pw[3] that the best
+// full count among its survivors, c_f = cf[0], did not reach.  Written by the prefix and rest
+// stages; the check stage and the tail only read them.
+__device__ __forceinline__ bool carry_fell_back(const int *pw, const int *cf, int npad) {
+  return pw[2] < npad && cf[0] < pw[3];
+}
 
 // group_done_max of a windowed stage: gd counts the window's `target` points of the group, the
 // lane's final count is counts[hc] (valid lanes), and the group's max goes to cword.  The
@@ -511,10 +563,16 @@ __global__ __launch_bounds__(BT) void k_f8_count32q(const float4 *__restrict__ p
   // every stage with win for npad; rest / Lq: the prefix stage's points past the window (-1:
   // none skipped, the exact count; else the screening loop) and L
   int win = npad, hoff = 0, rest = -1, Lq = 0;
+  constexpr bool kWhole = MODE == kCountWhole || MODE == kCountCheck;
+  if constexpr (MODE == kCountCheck) {
+    // uniform over the grid, before any barrier: nothing to do unless the run fell back
+    if (!carry_fell_back(pa.pw, pa.cf, npad)) return;
+  }
   if constexpr (MODE == kCountPrefix) {
     // K from L = status[0], the sample stage's best full count, which no wave of this launch
-    // writes (the group maxima go to pw[0]): every wave computes the same K
-    Lq = status[0];
+    // writes (the group maxima go to pw[0]): every wave computes the same K.  A carried run has
+    // no sample: its L is the lane's carry word less the gap, written by an earlier launch
+    Lq = pa.carry ? *pa.carry - pa.gap : status[0];
     int K = max(8, (n - Lq + pa.margin + 7) / 8 * 8);
     if (Lq <= 1 || K > npad - pa.min_skip) K = npad;  // too little to skip: the whole count
     if (bx == 0 && threadIdx.x == 0) {
@@ -663,7 +721,7 @@ __global__ __launch_bounds__(BT) void k_f8_count32q(const float4 *__restrict__ p
       continue;
     }
 #endif
-    if constexpr (MODE == kCountWhole) {
+    if constexpr (kWhole) {
       if (h < H) atomicAdd(&counts[h], cnt);
       if (gdone) group_done_max(counts, gdone, status, grp, p1 - p0, npad, h, H);
     } else {
@@ -688,7 +746,7 @@ __global__ __launch_bounds__(BT) void k_f8_count32q(const float4 *__restrict__ p
         const int grp = g0 + k, h = grp * 64 + lane;
         const int c = __hip_atomic_load(&s_cnt[k * 64 + lane], __ATOMIC_RELAXED,
                                         __HIP_MEMORY_SCOPE_WORKGROUP);
-        if constexpr (MODE == kCountWhole) {
+        if constexpr (kWhole) {
           if (h < H) atomicAdd(&counts[h], c);
           if (gdone) group_done_max(counts, gdone, status, grp, len, npad, h, H);
         } else {
@@ -803,7 +861,8 @@ __device__ void replay_inliers(const Pt *__restrict__ pts, int n, const int *cou
                                const double *__restrict__ Fsoa, int64_t ld, int *status,
                                double thresh, F8DevResult *__restrict__ res,
                                F8DevResult *__restrict__ hres, const int *cfast,
-                               const int *spec, const int *spec_j, int *__restrict__ hinl);
+                               const int *spec, const int *spec_j, int *__restrict__ hinl,
+                               int cmax);
 
 // Candidates + their reference-order statistics, one block per slice of hypotheses:
 // every hypothesis of the slice with fast count >= max(c* - slack, 1) is appended in index
@@ -823,9 +882,11 @@ __device__ void cand_stats_block(const TailArgs &a, int bid, int nblocks) {
   const int n = a.n, H = a.H, slack = a.slack, per_block = a.per_block;
   const double *__restrict__ Fsoa = a.Fsoa;
   const int64_t ld = a.ld;
-  const int *__restrict__ counts = a.counts;
   const int *__restrict__ status = a.status;
   int *__restrict__ status_rw = a.status;
+  // a carried run that fell back: c* and the counts are the check stage's
+  const bool fb = a.pw && carry_fell_back(a.pw, status, (n + 7) / 8 * 8);
+  const int *__restrict__ counts = fb ? a.counts_fb : a.counts;
   const double thresh = a.thresh;
   int *__restrict__ bc = a.status + 4;
   int *__restrict__ cand = a.cand;
@@ -841,7 +902,12 @@ __device__ void cand_stats_block(const TailArgs &a, int bid, int nblocks) {
   __shared__ int lcand[kLocalCands];
   __shared__ int qoff[kRegPts][NW];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int cmax = status[0];
+  const int cmax = fb ? a.fbw[0] : status[0];
+  if (bid == 0 && tid == 0) {
+    // the lane's next run reads the word in a later launch on the same stream
+    if (a.carry) *a.carry = cmax;
+    if (fb) atomicAdd(a.n_fb, 1);
+  }
   const int thr = max(cmax - slack, 1);
   const int b0 = bid * per_block, b1 = min(H, b0 + per_block);
   int *seg = cand + static_cast<int64_t>(bid) * per_block;
@@ -976,7 +1042,7 @@ __device__ void cand_stats_block(const TailArgs &a, int bid, int nblocks) {
   __syncthreads();
   if (!last_s) return;
   replay_inliers(pts, n, counts, nblocks, per_block, bc, cand, ccount, cstd, cnorm, Fsoa, ld,
-                 status_rw, thresh, a.res, a.hres, a.cfast, a.spec, a.spec_j, a.hinl);
+                 status_rw, thresh, a.res, a.hres, a.cfast, a.spec, a.spec_j, a.hinl, cmax);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -1003,7 +1069,8 @@ __device__ void replay_inliers(const Pt *__restrict__ pts, int n, const int *cou
                                const double *__restrict__ Fsoa, int64_t ld, int *status,
                                double thresh, F8DevResult *__restrict__ res,
                                F8DevResult *__restrict__ hres, const int *cfast,
-                               const int *spec, const int *spec_j, int *__restrict__ hinl) {
+                               const int *spec, const int *spec_j, int *__restrict__ hinl,
+                               int cmax) {
   int *status_out = status;
   __shared__ int pref[kSelectBlocks + 1];
   __shared__ int woff[kTailThreads / 64];
@@ -1091,7 +1158,7 @@ __device__ void replay_inliers(const Pt *__restrict__ pts, int n, const int *cou
     }
     mismatch = wave_sum_i(mismatch);
     if (lane == 0) {
-      const int cfast_max = status[0];
+      const int cfast_max = cmax;  // c* of the counts the tail read (cand_stats_block)
       double fw[9];
       if (best >= 0) {
 #pragma unroll
@@ -1398,6 +1465,17 @@ hipError_t launch_f8_count32q_rest(const float4 *ptsq, const Pt *pts, int n, int
   hipLaunchKernelGGL((k_f8_count32q<kCountBT, kCountRest>), dim3(static_cast<unsigned>(blocks)),
                      dim3(kCountBT), 0, s, ptsq, pts, n, H, F32soa, Fsoa, ld, int64_t{0}, g, counts,
                      nullptr, status, G4, nullptr, pa);
+  return hipGetLastError();
+}
+
+hipError_t launch_f8_count32q_check(const float4 *ptsq, const Pt *pts, int n, int H,
+                                    const float *F32soa, const double *Fsoa, int64_t ld,
+                                    const Count32qShape &sh, const GuardW &g, int *counts,
+                                    hipStream_t s, int *gdone, int *fbw, const float4 *G4,
+                                    const PruneArgs &pa) {
+  hipLaunchKernelGGL((k_f8_count32q<kCountBT, kCountCheck>), dim3(static_cast<unsigned>(sh.blocks)),
+                     dim3(kCountBT), 0, s, ptsq, pts, n, H, F32soa, Fsoa, ld, sh.per_wave, g, counts,
+                     gdone, fbw, G4, nullptr, pa);
   return hipGetLastError();
 }
 

@@ -9,7 +9,9 @@
 //   k_f8_count32x    counts of run k (+ fused c*): one launch, or with the pruned count
 //                    (RSAMD_PRUNE=1, the fp32 path) three in a row on the same lane -- sample,
 //                    prefix, rest (f8_kernels.hip above k_f8_count32q) -- with no host decision
-//                    and no event between them
+//                    and no event between them; a run whose lane last ran the same H and
+//                    threshold over the same points (RSAMD_CARRY=1) has prefix, rest, check
+//                    instead, its bound from that run's c* in the lane's carry word
 //
 // and leaves run k's tail pending on that lane: it rides along with the lane's next solve, or
 // is flushed alone by rs_f8_plan_result / set_points / destroy (plan_flush, the only place the
@@ -74,6 +76,12 @@ struct RunBufs {
   int *d_surv = nullptr;
   int *d_gdone_b = nullptr;
   bool staged = false;
+  // carried run (no sample; L from the lane's carry word): the check stage's counts, per-group
+  // finish counters and c* word; carried: the set's last run was such a run
+  int *d_counts_fb = nullptr;
+  int *d_gdone_fb = nullptr;
+  int *d_fbw = nullptr;
+  bool carried = false;
   double thresh = 0.0;         // the last run's threshold (rs_f8_plan_counts' recount)
   // host tuples (parity mode fed from the host) are staged in a pinned buffer owned by the
   // set, so the caller's array may go away as soon as rs_f8_plan_run returns; ev_copy marks
@@ -94,6 +102,17 @@ constexpr int kPruneDefault = 1;
 constexpr int kPruneSampleDefault = 32;
 constexpr int kPruneMarginDiv = 30;   // m = max(16, n / 30)
 constexpr int kPruneMinSkipDiv = 8;   // prune only when at least n / 8 points are skipped
+// rs_f8_plan::carry and the gap unless RSAMD_CARRY / RSAMD_CARRY_GAP are set: a lane's run takes
+// L = (c* of the lane's previous run) - g, g = max(kCarryGapMin, n / kCarryGapDiv), instead of a
+// sample's (above k_f8_count32q, "Carried bound").  profiles/carry/ab.txt, C2, two rounds, bench
+// value in 1e9 hypotheses/s: g = n/50 / n/25 / n/16 / n/10 gave 1.705-1.713 / 1.647-1.671 /
+// 1.628-1.641 / 1.558-1.575, no fallback in 298 carried runs at any of them, hence n / 50.  The
+// floor is for small n, where c* spreads like sqrt(n) and not like n: tools/carry_model.py
+// (profiles/carry/model.txt) has c* 160-170 over 8 runs at N = 257, one fallback in 7 at g = 5
+// and none at 16 (the floor of the margin m)
+constexpr int kCarryDefault = 1;
+constexpr int kCarryGapDiv = 50;
+constexpr int kCarryGapMin = 16;
 
 int env_int(const char *name, int dflt) {
   const char *v = std::getenv(name);
@@ -161,6 +180,19 @@ struct rs_f8_plan {
   int prune_sample = kPruneSampleDefault;   // RSAMD_PRUNE_SAMPLE: hypothesis groups of the sample
   int prune_margin = -1;                    // RSAMD_PRUNE_MARGIN: m of K = roundup8(n - L + m)
   int prune_min_skip = -1;                  // RSAMD_PRUNE_MINSKIP: prune only if >= this many points go
+  // Carried bound (fp32 path, pruning on; derivation above k_f8_count32q): a run on a lane whose
+  // previous run had the same H and threshold over the same points takes L from that run's c*,
+  // left in d_carry[lane] by its tail, less the gap; no sample stage, a check stage that counts
+  // everything again only if the bound turned out to be above c*.  carry_ok[l]: lane l's word
+  // holds the c* of a run with carry_H / carry_thresh over the resident points
+  int carry = kCarryDefault;                // RSAMD_CARRY
+  int carry_gap = 0;                        // RSAMD_CARRY_GAP (may be negative: every run falls back)
+  bool carry_gap_set = false;
+  int *d_carry = nullptr;                   // kLanes carry words, then the fallback counter
+  bool carry_ok[kLanes] = {};
+  int64_t carry_H = 0;
+  double carry_thresh = 0.0;
+  int64_t n_carried = 0;                    // runs carried since the plan was created
   int *d_full = nullptr;      // rs_f8_plan_counts after a pruned run: the full counts (ld ints)
   int nospec = 0;             // RSAMD_NOSPEC=1 (test hook): the replay extracts S_RANSAC itself
   uint64_t *d_ts = nullptr;   // RSAMD_TSTAMP=<file>: wave timeline of the counting kernel
@@ -174,6 +206,7 @@ static void plan_free(rs_f8_plan *p) {
   (void)hipFree(p->d_pts);
   (void)hipFree(p->d_pts32q);
   (void)hipFree(p->d_full);
+  (void)hipFree(p->d_carry);
   if (p->d_ts) {
     (void)rsd::set_count_timeline(nullptr);
     (void)hipFree(p->d_ts);
@@ -197,6 +230,9 @@ static void plan_free(rs_f8_plan *p) {
     (void)hipFree(b.d_pw);
     (void)hipFree(b.d_surv);
     (void)hipFree(b.d_gdone_b);
+    (void)hipFree(b.d_counts_fb);
+    (void)hipFree(b.d_gdone_fb);
+    (void)hipFree(b.d_fbw);
     if (b.h_tuples) (void)hipHostFree(b.h_tuples);
     if (b.ev_copy) (void)hipEventDestroy(b.ev_copy);
   }
@@ -279,7 +315,12 @@ extern "C" int rs_f8_plan_create(rs_ctx *c, int64_t n, int64_t max_hyp, rs_f8_pl
     ALLOC(b.d_pw, sizeof(int) * rsd::kPruneWords);
     ALLOC(b.d_surv, sizeof(int) * p->ld);
     ALLOC(b.d_gdone_b, sizeof(int) * (p->ld / 64));
+    ALLOC(b.d_counts_fb, sizeof(int) * p->ld);
+    ALLOC(b.d_gdone_fb, sizeof(int) * (p->ld / 64));
+    ALLOC(b.d_fbw, sizeof(int));
   }
+  ALLOC(p->d_carry, sizeof(int) * (rs_f8_plan::kLanes + 1));
+  if (e == hipSuccess) e = hipMemset(p->d_carry, 0, sizeof(int) * (rs_f8_plan::kLanes + 1));
 #undef ALLOC
   for (int k = 0; k < rs_f8_plan::kSlots; ++k) {
     if (e == hipSuccess)
@@ -297,6 +338,9 @@ extern "C" int rs_f8_plan_create(rs_ctx *c, int64_t n, int64_t max_hyp, rs_f8_pl
   p->prune_sample = std::max(1, env_int("RSAMD_PRUNE_SAMPLE", kPruneSampleDefault));
   p->prune_margin = env_int("RSAMD_PRUNE_MARGIN", -1);
   p->prune_min_skip = env_int("RSAMD_PRUNE_MINSKIP", -1);
+  p->carry = env_int("RSAMD_CARRY", kCarryDefault) != 0;
+  p->carry_gap_set = std::getenv("RSAMD_CARRY_GAP") != nullptr;
+  p->carry_gap = std::max(-(1 << 24), std::min(1 << 24, env_int("RSAMD_CARRY_GAP", 0)));
   p->ts_path = std::getenv("RSAMD_TSTAMP");
   if (p->ts_path) {
     p->overlap = false;  // one device-global timeline buffer: one counting launch at a time
@@ -317,6 +361,12 @@ extern "C" int rs_f8_plan_create(rs_ctx *c, int64_t n, int64_t max_hyp, rs_f8_pl
 }
 
 static int plan_flush(rs_f8_plan *p);
+
+// The carry words no longer describe what the next run counts (new points, another counting
+// kernel, another H or threshold): both lanes start again from a sample run
+static void carry_drop(rs_f8_plan *p) {
+  for (bool &ok : p->carry_ok) ok = false;
+}
 
 // A new population for an existing plan (the drop-in's calls, one pair after another): the
 // per-point buffers are reallocated only when n exceeds what they hold; the per-hypothesis
@@ -358,6 +408,7 @@ static int plan_retarget(rs_f8_plan *p, int64_t n) {
   }
   p->n = n;
   p->fp32_ok = false;  // set_points decides it for the new points
+  carry_drop(p);
   return RS_OK;
 }
 
@@ -440,6 +491,7 @@ extern "C" int rs_f8_plan_set_points(rs_f8_plan *p, const double *p1, const doub
   if (!p || !p1 || !p2) return fail(RS_EINVAL, "null pointer");
   int st = plan_flush(p);  // runs in flight read the resident points
   if (st) return st;
+  carry_drop(p);
   rs_ctx *c = p->ctx;
   const int64_t n = p->n;
   const size_t b = sizeof(double) * 2 * n;
@@ -477,6 +529,12 @@ static rsd::PruneArgs prune_args(const rs_f8_plan *p, const RunBufs &b) {
   pa.g_first = std::min(p->prune_sample, 1 << 24);
   pa.margin = p->prune_margin >= 0 ? std::min(p->prune_margin, n) : std::max(16, n / kPruneMarginDiv);
   pa.min_skip = std::max(8, p->prune_min_skip >= 0 ? p->prune_min_skip : n / kPruneMinSkipDiv);
+  if (b.carried) {  // no sample: every group is screened against the lane's carried bound
+    pa.g_first = 0;
+    pa.carry = p->d_carry + b.lane;
+    pa.gap = p->carry_gap_set ? p->carry_gap : std::max(kCarryGapMin, n / kCarryGapDiv);
+    pa.cf = b.d_status;
+  }
   return pa;
 }
 
@@ -578,11 +636,21 @@ static int plan_run(rs_f8_plan *p, int64_t H, int32_t mode, uint64_t seed, uint6
   // the pruned count's stages, when the run has hypotheses past the sample
   const int h0 = static_cast<int>(std::min<int64_t>(H, 64LL * std::min(p->prune_sample, 1 << 24)));
   const bool staged = fp32 && p->prune && h0 < h;
+  // ... without the sample when the lane's carry word holds the c* of a run like this one (the
+  // decision is the host's alone: H and the threshold of the run that left the word)
+  if (!(fp32 && H == p->carry_H && thresh == p->carry_thresh)) carry_drop(p);
+  const bool carried = staged && p->carry && p->carry_ok[lane];
   b.staged = staged;
+  b.carried = carried;
   b.thresh = thresh;
   if (staged) {
     sa.pw = b.d_pw;
     sa.gdone_b = b.d_gdone_b;
+  }
+  if (carried) {
+    sa.counts_fb = b.d_counts_fb;
+    sa.gdone_fb = b.d_gdone_fb;
+    sa.fbw = b.d_fbw;
   }
   if (excl && tl >= 2) {
     HIP_TRY(hipEventRecord(ev_end, lane_stream(p, other)));
@@ -600,7 +668,22 @@ static int plan_run(rs_f8_plan *p, int64_t H, int32_t mode, uint64_t seed, uint6
     HIP_TRY(hipStreamWaitEvent(ms, ev_end, 0));
   }
   if (tl >= 1) HIP_TRY(hipEventRecord(ev[0], ms));
-  if (staged) {
+  if (carried) {
+    // prefix of every group against L = the lane's carry word - gap -> the survivors over the
+    // whole window (c_f in status[0]) -> check: everything again into the set's fallback storage
+    // if c_f < L, else an empty launch of one slice per resident wave; all on the device
+    const rsd::GuardW gw{thresh * thresh};
+    const rsd::PruneArgs pa = prune_args(p, b);
+    const rsd::Count32qShape sh1 = rsd::count32q_shape(n, h, p->q_waves, p->q_slices);
+    HIP_TRY(rsd::launch_f8_count32q_prefix(p->d_pts32q, p->d_pts, n, h, b.d_F32, b.d_F, p->ld, sh1,
+                                           gw, b.d_counts, ms, b.d_gdone, b.d_status, b.d_G4, pa));
+    HIP_TRY(rsd::launch_f8_count32q_rest(p->d_pts32q, p->d_pts, n, h, b.d_F32, b.d_F, p->ld,
+                                         p->q_waves, sh1, gw, b.d_counts, ms, b.d_status, b.d_G4, pa));
+    const rsd::Count32qShape shc = rsd::count32q_shape(n, h, p->q_waves, 1);
+    HIP_TRY(rsd::launch_f8_count32q_check(p->d_pts32q, p->d_pts, n, h, b.d_F32, b.d_F, p->ld, shc,
+                                          gw, b.d_counts_fb, ms, b.d_gdone_fb, b.d_fbw, b.d_G4, pa));
+    ++p->n_carried;
+  } else if (staged) {
     // sample (whole window, c* of its groups = L in status[0]) -> prefix [0, K) of the other
     // groups screened, K from L on the device, survivors listed -> the survivors over the whole
     // window; all three in stream order on this lane, no host decision
@@ -651,6 +734,18 @@ static int plan_run(rs_f8_plan *p, int64_t H, int32_t mode, uint64_t seed, uint6
   ta.res = b.d_res;
   ta.hres = p->h_slot_dev[slot];
   ta.hinl = p->h_inl_dev[slot];
+  if (fp32) {  // this run's c* for the lane's next run, should that be one like it
+    ta.carry = p->d_carry + lane;
+    p->carry_H = H;
+    p->carry_thresh = thresh;
+    p->carry_ok[lane] = true;
+  }
+  if (carried) {
+    ta.pw = b.d_pw;
+    ta.counts_fb = b.d_counts_fb;
+    ta.fbw = b.d_fbw;
+    ta.n_fb = p->d_carry + rs_f8_plan::kLanes;
+  }
   p->tail_pending[lane] = true;
   p->busy[lane] = true;
   p->last_lane = lane;
@@ -824,6 +919,19 @@ extern "C" int rs_f8_plan_candidates(rs_f8_plan *p, rs_f8_candidate *out, int64_
   return RS_OK;
 }
 
+// Whether the last run (complete: after plan_wait) was carried and fell back, by the test the
+// check stage and the tail made on the device (carry_fell_back in f8_kernels.hip)
+static int last_fell_back(rs_f8_plan *p, bool *fb) {
+  const RunBufs &b = p->last();
+  *fb = false;
+  if (!b.carried) return RS_OK;
+  int pw[rsd::kPruneWords] = {}, cf = 0;
+  HIP_TRY(hipMemcpy(pw, b.d_pw, sizeof(pw), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&cf, b.d_status, sizeof(int), hipMemcpyDeviceToHost));
+  *fb = pw[2] < (p->n + 7) / 8 * 8 && cf < pw[3];
+  return RS_OK;
+}
+
 extern "C" int rs_f8_plan_counts(rs_f8_plan *p, int32_t *counts, int64_t H) {
   if (!p || !counts) return fail(RS_EINVAL, "null pointer");
   int st = plan_wait(p);
@@ -834,7 +942,11 @@ extern "C" int rs_f8_plan_counts(rs_f8_plan *p, int32_t *counts, int64_t H) {
   int pw[rsd::kPruneWords] = {};
   if (b.staged) HIP_TRY(hipMemcpy(pw, b.d_pw, sizeof(pw), hipMemcpyDeviceToHost));
   const int n = static_cast<int>(p->n);
-  if (b.staged && pw[2] < (n + 7) / 8 * 8) {
+  bool fb = false;
+  if ((st = last_fell_back(p, &fb))) return st;
+  if (fb) {
+    src = b.d_counts_fb;  // the check stage counted every hypothesis in full
+  } else if (b.staged && pw[2] < (n + 7) / 8 * 8) {
     // a pruned run leaves prefix upper bounds for the hypotheses it dropped: the full counts come
     // from the whole-window kernel over the run's models, still in the buffer set (a
     // diagnostic accessor; nothing else is in flight after plan_wait)
@@ -859,7 +971,25 @@ extern "C" int rs_f8_plan_stage_counts(rs_f8_plan *p, int32_t *counts, int64_t H
   int st = plan_wait(p);
   if (st) return st;
   if (H > p->last_H) return fail(RS_EINVAL, "H exceeds the last run");
-  HIP_TRY(hipMemcpy(counts, p->last().d_counts, sizeof(int) * H, hipMemcpyDeviceToHost));
+  bool fb = false;
+  if ((st = last_fell_back(p, &fb))) return st;
+  HIP_TRY(hipMemcpy(counts, fb ? p->last().d_counts_fb : p->last().d_counts, sizeof(int) * H,
+                    hipMemcpyDeviceToHost));
+  return RS_OK;
+}
+
+extern "C" int rs_f8_plan_carry_stats(rs_f8_plan *p, int64_t *out) {
+  if (!p || !out) return fail(RS_EINVAL, "null pointer");
+  int st = plan_wait(p);
+  if (st) return st;
+  bool fb = false;
+  if ((st = last_fell_back(p, &fb))) return st;
+  int nfb = 0;
+  HIP_TRY(hipMemcpy(&nfb, p->d_carry + rs_f8_plan::kLanes, sizeof(int), hipMemcpyDeviceToHost));
+  out[0] = p->n_carried;
+  out[1] = nfb;
+  out[2] = p->last().carried ? 1 : 0;
+  out[3] = fb ? 1 : 0;
   return RS_OK;
 }
 
@@ -937,6 +1067,7 @@ extern "C" int rs_f8_plan_set_count_precision(rs_f8_plan *p, int32_t fp64) {
   int st = plan_flush(p);  // runs in flight use the current kernel's buffers
   if (st) return st;
   p->use_fp32 = fp64 == 0;
+  carry_drop(p);
   return RS_OK;
 }
 

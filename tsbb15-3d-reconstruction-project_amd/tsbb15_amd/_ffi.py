@@ -133,6 +133,7 @@ _SIGS = {
     "rs_f8_plan_set_timing": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "rs_f8_plan_lane_waits": (C.c_int, [C.c_void_p, _i64p]),
     "rs_f8_plan_prune_stats": (C.c_int, [C.c_void_p, _i64p]),
+    "rs_f8_plan_carry_stats": (C.c_int, [C.c_void_p, _i64p]),
     "rs_f8_plan_stage_counts": (C.c_int, [C.c_void_p, _i32p, C.c_int64]),
     "rs_f8_plan_set_count_precision": (C.c_int, [C.c_void_p, C.c_int32]),
     "rs_f8_ransac_np": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64, _u32p, _i32p,
@@ -704,6 +705,14 @@ class F8Plan:
         out = (C.c_int64 * 4)()
         check(lib().rs_f8_plan_prune_stats(self._h, out))
         return {"L": out[0], "K": out[1], "survivors": out[2], "npad": out[3]}
+
+    def carry_stats(self):
+        """The carried bound: runs carried since the plan was created, those among them that fell
+        back to a whole count, and whether the last run was carried / fell back."""
+        out = (C.c_int64 * 4)()
+        check(lib().rs_f8_plan_carry_stats(self._h, out))
+        return {"carried": out[0], "fallbacks": out[1], "last_carried": bool(out[2]),
+                "last_fell_back": bool(out[3])}
 
     def kernel_ms(self, last_n=1):
         """Device times of the last run, or averaged over the last ``last_n`` runs."""
