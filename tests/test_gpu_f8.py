@@ -294,3 +294,92 @@ def test_selection_and_count_shapes_match_golden(ctx, monkeypatch, knobs):
     cands = plan.candidates()
     assert any(c.index == r.best_index for c in cands)
     plan.close()
+
+
+def _rec(plan, h):
+    """Everything the plan returns for its last run, floats as bytes (NaN compares equal)."""
+    r, inl = plan.result()
+    head = (int(r.best_index), int(r.best_count), int(r.max_count_fast), int(r.n_candidates),
+            int(r.guard_mismatch), np.array([*r.F[:], r.best_std, r.best_norm]).tobytes())
+    cands = sorted((c.index, c.count, np.array([c.std_d, c.norm_d, *c.F[:]]).tobytes())
+                   for c in plan.candidates())
+    return (head, inl.tolist(), cands, plan.counts(h).tobytes(), plan.models(h).tobytes())
+
+
+def _nine_runs(ctx, monkeypatch, env, n, max_hyp, h):
+    """Nine Philox runs on a plan created under ``env``: thresholds 1.5 x5 then 2.0 x4 (sample runs,
+    carried runs and a carry drop on the default plan; all four buffer sets and result slots used
+    and wrapped), records after runs 1, 4, 5 and 9."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    p1, p2, _ = synth.two_view(n, 0.3, seed=21)
+    plan = _ffi.F8Plan(ctx, n, max_hyp)
+    for k in env:
+        monkeypatch.delenv(k)
+    out = []
+    try:
+        plan.set_points(p1, p2)
+        for i in range(9):
+            plan.run(h, mode=_ffi.SAMPLER_PHILOX, seed=5, hyp_offset=i * h,
+                     thresh=1.5 if i < 5 else 2.0)
+            if i + 1 in (1, 4, 5, 9):
+                out.append(_rec(plan, h))
+    finally:
+        plan.close()
+    return out
+
+
+@pytest.mark.parametrize("n,max_hyp,h,env", [
+    (8, 1, 1, {}), (9, 64, 64, {}), (17, 65, 65, {}), (600, 4000, 4000, {}),
+    (600, 4000, 4000, {"RSAMD_NOSPEC": "1"}),   # the replay extracts S_RANSAC itself
+])
+def test_arena_neighbours(ctx, monkeypatch, n, max_hyp, h, env):
+    """The plan's buffers lie side by side in its arenas, so a write past the end of one lands in
+    a neighbour and not in allocator slack: everything the default plan returns equals, bit for
+    bit, what a one-lane unpruned plan and a float64-count plan return for the same calls."""
+    got = _nine_runs(ctx, monkeypatch, env, n, max_hyp, h)
+    assert len(got) == 4
+    for ref in ({"RSAMD_OVERLAP": "0", "RSAMD_PRUNE": "0"}, {"RSAMD_COUNT": "fp64"}):
+        want = _nine_runs(ctx, monkeypatch, ref, n, max_hyp, h)
+        for k, (x, y) in enumerate(zip(got, want)):
+            assert x == y, (ref, k)
+
+
+def _ransac_np(ctx, p1, p2, H, key, pos):
+    """rs_f8_ransac_np on ``ctx``: (everything it returns, floats as bytes), advanced (key, pos)."""
+    C = _ffi.C
+    p1, p2 = _ffi.f64c(p1), _ffi.f64c(p2)
+    n = p1.shape[1]
+    key = np.array(key, dtype=np.uint32, copy=True)
+    p = C.c_int32(int(pos))
+    r, inl, k = _ffi.F8Result(), np.empty(n, dtype=np.int64), C.c_int64(0)
+    _ffi.check(_ffi.lib().rs_f8_ransac_np(
+        ctx.handle, _ffi.ptr(p1, C.c_double), _ffi.ptr(p2, C.c_double), n, int(H),
+        _ffi.ptr(key, C.c_uint32), C.byref(p), 1.5, C.byref(r), _ffi.ptr(inl, C.c_int64), n,
+        C.byref(k)))
+    rec = (int(r.best_index), int(r.best_count), int(r.max_count_fast), int(r.n_candidates),
+           int(r.guard_mismatch), np.array([*r.F[:], r.best_std, r.best_norm]).tobytes(),
+           inl[:k.value].tolist(), key.tobytes(), p.value)
+    return rec, key, p.value
+
+
+def test_retarget_regrows_arena(ctx):
+    """One context's cached plan retargeted to smaller and larger populations (2000 and 2501 regrow
+    the per-point arenas, 2501 just past the 2000 + 500 growth step) against a fresh context per
+    call: F, index, counts, std, norm, S_RANSAC and the advanced (key, pos), bit for bit."""
+    H = 500
+    one = _ffi.Context(ctx.device)
+    try:
+        key, pos = _ffi.np_seed(0)
+        for k, n in enumerate((600, 8, 2000, 601, 2501)):
+            p1, p2, _ = synth.two_view(n, 0.3, seed=30 + k)
+            fresh = _ffi.Context(ctx.device)
+            try:
+                want, _, _ = _ransac_np(fresh, p1, p2, H, key, pos)
+            finally:
+                fresh.close()
+            got, key, pos = _ransac_np(one, p1, p2, H, key, pos)
+            assert got == want, n
+            assert len(got[6]) == got[1]
+    finally:
+        one.close()

@@ -4,26 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "f8_types.h"
+
 namespace rsd {
-
-// One correspondence, AoS 32 B: left image (x1, y1) = p1 column, right image (x2, y2) = p2
-// column (fun.getFFromLabCode(p1, p2), convention p1^T F p2 = 0, lab3.py:195-196).
-struct Pt {
-  double x1, y1, x2, y2;
-};
-
-// Similarity frame of the fp32 counting kernel: x~ = (x - c_i) / s per image i, one common
-// scale s so both line-length terms scale by s^2 and the min() test is frame invariant.
-struct Frame {
-  double s, cx1, cy1, cx2, cy2;
-};
-
-// Per-hypothesis decision (k_f8_count32q): constants live with each model (G4,
-// written by the solve); only the float64 re-test threshold is global.
-struct GuardW {
-  double thr2_px;
-};
-
 
 // ----------------------------------------------------------------------------------------
 // Philox4x32-10 counter-based generator (throughput-mode sampler).

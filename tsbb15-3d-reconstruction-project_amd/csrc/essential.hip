@@ -1346,9 +1346,10 @@ extern "C" int rs_e5_ransac(rs_ctx *c, const double *p1, const double *p2, int64
     }();
     const rsd::Count32qShape sh =
         rsd::count32q_shape(static_cast<int>(n), static_cast<int>(H), kE5CountWaves, slices);
-    HIP_TRY(rsd::launch_f8_count32q(dpq, dp, static_cast<int>(n), static_cast<int>(H), dF32, dFd, ld, sh,
-                                    rsd::GuardW{thresh * thresh}, dc, s, dgdone, dcmax, dG4,
-                                    dcmax + 2));  // (c* into dcmax[0] as groups complete)
+    // (c* into dcmax[0] as groups complete)
+    const rsd::CountArgs ca{dpq, dp, static_cast<int>(n), static_cast<int>(H), dF32, dFd, ld,
+                            rsd::GuardW{thresh * thresh}, dc, dgdone, dcmax, dG4, dcmax + 2};
+    HIP_TRY(rsd::launch_f8_count32q(rsd::kCountWhole, ca, sh, 0, rsd::PruneArgs{}, s));
   } else {
     HIP_TRY(hipMemsetAsync(dc, 0, sizeof(int) * H, s));
     // chunking of k_f8_count: >= 8 units of work per SIMD, chunks of >= 64 points (sized for

@@ -11,29 +11,7 @@
 
 namespace rsd {
 
-
-// Grid of the selection passes; the status buffer holds 4 words + kSelectBlocks counts.
-constexpr int kSelectBlocks = 256;
-constexpr int kStatusWords = 4 + kSelectBlocks;
 constexpr int kTailThreads = 512;  // workgroup of the fused tail + solve launch
-
-// Device-resident result of one F run; copied back to the host in one transfer together
-// with the first n_inliers entries of `inliers`.
-struct F8DevResult {
-  double F[9];
-  int64_t best_index;
-  int64_t best_count;
-  double best_std;
-  double best_norm;
-  int64_t max_count_fast;
-  int64_t n_candidates;
-  int64_t guard_mismatch;
-  int64_t n_inliers;
-  int64_t best_cand;
-  int64_t inl_row;  // -1: S_RANSAC in inliers[]; else the select block whose spec row holds it
-
-  int64_t inliers[];
-};
 
 // One run's solve (k_f8_solve / the solve half of k_f8_tail_solve).
 struct SolveArgs {
@@ -71,9 +49,8 @@ struct TailArgs {
   int *spec, *spec_j;  // per block: S_RANSAC of its first candidate (n ints), that index
   int nospec;          // RSAMD_NOSPEC=1: no speculative lists (the replay extracts S_RANSAC)
   double *cstd, *cnorm;
-  F8DevResult *res;   // HBM result (header + S_RANSAC)
-  F8DevResult *hres;  // pinned host header slot (device mapping), may be null
-  int *hinl;          // pinned host S_RANSAC (int32, device mapping), may be null
+  F8DevResult *hres;  // pinned host header slot (device mapping)
+  int *hinl;          // pinned host S_RANSAC (int32, device mapping)
   int *carry;         // the lane's carry word: the run's c* is left there, may be null
   // carried run: the prune words, the check stage's counts and c* word, the plan's fallback
   // counter; the tail takes c* and the counts from the check stage's storage when the run fell
@@ -112,17 +89,11 @@ hipError_t preload_f8();  // the F-RANSAC kernels' code object onto the current 
 // pts (and with fr the point-pair layout ptsq) from the (2, n) arrays in one launch
 hipError_t launch_pack_points_both(const double *p1, const double *p2, int n, Pt *pts,
                                    const Frame *fr, float4 *ptsq, hipStream_t s);
-hipError_t launch_f8_count32q(const float4 *ptsq, const Pt *pts, int n, int H,
-                              const float *F32soa, const double *Fsoa, int64_t ld,
-                              const Count32qShape &sh, const GuardW &g, int *counts,
-                              hipStream_t s, int *gdone, int *status, const float4 *G4,
-                              const int *Hdev = nullptr);
 // Pruned count (derivation above k_f8_count32q): after a full count of the first g_first
 // hypothesis groups has left L in status[0], the prefix stage screens the other groups over the
 // points [0, K) only (certified outliers, no inlier count), K from L on the device, and lists
 // the hypotheses that can still reach L - 1 (surv); the rest stage counts those over the whole
-// window through the list.  Per-run words:
-constexpr int kPruneWords = 4;  // [0] cA (max count when K = npad), [1] survivors, [2] K, [3] L
+// window through the list.  The run's words: kPruneWords (f8_types.h).
 struct PruneArgs {
   int *pw;       // the run's words
   int *surv;     // survivor hypothesis ids (ld ints)
@@ -136,28 +107,32 @@ struct PruneArgs {
   int gap;
   const int *cf;
 };
-// sh: the shape of the groups past g_first over the whole window (the prefix stage cuts its
-// slices from K on the device); H is the run's hypothesis count
-hipError_t launch_f8_count32q_prefix(const float4 *ptsq, const Pt *pts, int n, int H,
-                                     const float *F32soa, const double *Fsoa, int64_t ld,
-                                     const Count32qShape &sh, const GuardW &g, int *counts,
-                                     hipStream_t s, int *gdone, int *status, const float4 *G4,
-                                     const PruneArgs &pa);
-// waves: the resident waves the grid is sized for (the survivor count is on the device), at
-// most the grid of `bound`, the shape of all H hypotheses the prefix stage counted
-hipError_t launch_f8_count32q_rest(const float4 *ptsq, const Pt *pts, int n, int H,
-                                   const float *F32soa, const double *Fsoa, int64_t ld, int waves,
-                                   const Count32qShape &bound, const GuardW &g, int *counts,
-                                   hipStream_t s, int *status, const float4 *G4,
-                                   const PruneArgs &pa);
-// The check stage of a carried run: a whole-window count of all H hypotheses into counts / gdone /
-// fbw (the check stage's own storage) when the run fell back (K < npad and c_f < L, read from
-// pa.pw and pa.cf, which no wave of this launch writes); otherwise every workgroup returns at once
-hipError_t launch_f8_count32q_check(const float4 *ptsq, const Pt *pts, int n, int H,
-                                    const float *F32soa, const double *Fsoa, int64_t ld,
-                                    const Count32qShape &sh, const GuardW &g, int *counts,
-                                    hipStream_t s, int *gdone, int *fbw, const float4 *G4,
-                                    const PruneArgs &pa);
+// What one launch of k_f8_count32q reads and writes.  counts / gdone / status are the stage's
+// own: the check stage of a carried run takes the set's fallback storage (counts_fb, gdone_fb and
+// the word fbw) there.  gdone and status may be null (no fused c*), Hdev too (H hypotheses).
+struct CountArgs {
+  const float4 *ptsq;
+  const Pt *pts;
+  int n, H;
+  const float *F32soa;
+  const double *Fsoa;
+  int64_t ld;
+  GuardW g;
+  int *counts, *gdone, *status;
+  const float4 *G4;
+  const int *Hdev;
+};
+// The stages (k_f8_count32q's MODE).  kCountWhole: H hypotheses over the whole window, pa unused.
+// kCountPrefix: sh is the shape of the groups past pa.g_first over the whole window (the stage
+// cuts its slices from K on the device), H the run's hypothesis count.  kCountRest: the survivors
+// over the whole window; the grid is sized for `waves` resident waves (the survivor count is on
+// the device), at most the grid of sh, the shape of the H hypotheses the prefix stage screened.
+// kCountCheck, the last stage of a carried run: a whole-window count of all H hypotheses when the
+// run fell back (K < npad and c_f < L, read from pa.pw and pa.cf, which no wave of this launch
+// writes); otherwise every workgroup returns at once.
+constexpr int kCountWhole = 0, kCountPrefix = 1, kCountRest = 2, kCountCheck = 3;
+hipError_t launch_f8_count32q(int mode, const CountArgs &a, const Count32qShape &sh, int waves,
+                              const PruneArgs &pa, hipStream_t s);
 hipError_t launch_f8_count(const Pt *pts, int n, int H, const double *Fsoa, int64_t ld,
                            int chunk, double thr2, int *counts, hipStream_t s,
                            const int *Hdev = nullptr, const int *Hmap = nullptr);

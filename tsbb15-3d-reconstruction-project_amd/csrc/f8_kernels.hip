@@ -384,12 +384,10 @@ __device__ __forceinline__ void group_done_max(int *counts, int *gdone, int *sta
   if ((threadIdx.x & 63) == 0 && v > 0) atomicMax(&status[0], v);
 }
 
-// Stages of the pruned count (k_f8_count32q's MODE): the whole window, the prefix [0, K) of the
-// groups past the sample (screened), the survivors over the whole window again.
-constexpr int kCountWhole = 0, kCountPrefix = 1, kCountRest = 2;
-// ... and the check stage of a carried run: the whole window again, into storage of its own, only
-// when the carried bound turned out to be above c*
-constexpr int kCountCheck = 3;
+// Stages of the pruned count (k_f8_count32q's MODE, f8_kernels.h): kCountWhole the whole window,
+// kCountPrefix the prefix [0, K) of the groups past the sample (screened), kCountRest the survivors
+// over the whole window again, and kCountCheck, the check stage of a carried run: the whole window
+// again, into storage of its own, only when the carried bound turned out to be above c*
 
 // A carried run fell back: it pruned (K = pw[2] < npad) against a bound L = pw[3] that the best
 // full count among its survivors, c_f = cf[0], did not reach.  Written by the prefix and rest
@@ -859,8 +857,7 @@ __device__ void replay_inliers(const Pt *__restrict__ pts, int n, const int *cou
                                int per_block, const int *bc, const int *cand, const int *ccount,
                                const double *cstd, const double *cnorm,
                                const double *__restrict__ Fsoa, int64_t ld, int *status,
-                               double thresh, F8DevResult *__restrict__ res,
-                               F8DevResult *__restrict__ hres, const int *cfast,
+                               double thresh, F8DevResult *__restrict__ hres, const int *cfast,
                                const int *spec, const int *spec_j, int *__restrict__ hinl,
                                int cmax);
 
@@ -1042,7 +1039,7 @@ __device__ void cand_stats_block(const TailArgs &a, int bid, int nblocks) {
   __syncthreads();
   if (!last_s) return;
   replay_inliers(pts, n, counts, nblocks, per_block, bc, cand, ccount, cstd, cnorm, Fsoa, ld,
-                 status_rw, thresh, a.res, a.hres, a.cfast, a.spec, a.spec_j, a.hinl, cmax);
+                 status_rw, thresh, a.hres, a.cfast, a.spec, a.spec_j, a.hinl, cmax);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -1060,15 +1057,13 @@ __device__ __forceinline__ uint64_t key_norm(double v) {  // "y > norm" is false
 // One kTailThreads workgroup (the last cand_stats block to finish): wave 0 replays
 // fun.py:320-328 over the candidates in global index order (segments in block order), 64 per
 // coalesced load; then the whole workgroup extracts S_RANSAC = flatnonzero(d < t) of the
-// winner in order.  The result header goes to res (HBM) and, when given, to hres (the run's
-// pinned host slot, written through the host mapping: no copy pass); the inlier list stays
-// in res->inliers (HBM).
+// winner in order.  The result header goes to hres (the run's pinned host slot) and the inlier
+// list to hinl (the slot's pinned list), both written through the host mapping: no copy pass.
 __device__ void replay_inliers(const Pt *__restrict__ pts, int n, const int *counts, int nb,
                                int per_block, const int *bc, const int *cand, const int *ccount,
                                const double *cstd, const double *cnorm,
                                const double *__restrict__ Fsoa, int64_t ld, int *status,
-                               double thresh, F8DevResult *__restrict__ res,
-                               F8DevResult *__restrict__ hres, const int *cfast,
+                               double thresh, F8DevResult *__restrict__ hres, const int *cfast,
                                const int *spec, const int *spec_j, int *__restrict__ hinl,
                                int cmax) {
   int *status_out = status;
@@ -1168,23 +1163,16 @@ __device__ void replay_inliers(const Pt *__restrict__ pts, int n, const int *cou
         for (int k = 0; k < 9; ++k) fw[k] = 0.0;
       }
       const bool spec_ok = best >= 0 && brow >= 0;
-      F8DevResult *outs[2] = {res, hres};
-      for (int o = 0; o < 2; ++o) {
-        F8DevResult *r = outs[o];
-        if (!r) continue;
-        r->n_candidates = nc;
-        r->max_count_fast = cfast_max;
-        r->guard_mismatch = mismatch;
-        r->best_index = best >= 0 ? bh : -1;
-        r->best_count = best >= 0 ? bcount : 0;
-        r->best_std = best >= 0 ? bsv : 0.0;
-        r->best_norm = best >= 0 ? bnv : 0.0;
-        r->best_cand = best;
-        r->inl_row = spec_ok ? brow : -1;
-        if (spec_ok) r->n_inliers = bcount;
+      hres->n_candidates = nc;
+      hres->max_count_fast = cfast_max;
+      hres->guard_mismatch = mismatch;
+      hres->best_index = best >= 0 ? bh : -1;
+      hres->best_count = best >= 0 ? bcount : 0;
+      hres->best_std = best >= 0 ? bsv : 0.0;
+      hres->best_norm = best >= 0 ? bnv : 0.0;
+      if (spec_ok) hres->n_inliers = bcount;
 #pragma unroll
-        for (int k = 0; k < 9; ++k) r->F[k] = fw[k];
-      }
+      for (int k = 0; k < 9; ++k) hres->F[k] = fw[k];
 #pragma unroll
       for (int k = 0; k < 9; ++k) fsh[k] = fw[k];
       status_out[1] = nc;
@@ -1195,13 +1183,11 @@ __device__ void replay_inliers(const Pt *__restrict__ pts, int n, const int *cou
     }
   }
   __syncthreads();
-  // the winner's S_RANSAC is its block's speculative list (rs_f8_plan_result reads it from
-  // hinl, or copies the row: inl_row); otherwise extract it here
+  // the winner's S_RANSAC is its block's speculative list: copy it to the pinned host buffer,
+  // where rs_f8_plan_result reads it (no copy pass after the run); otherwise extract it here
   if (spec_row_s >= 0) {
-    if (hinl) {  // the list to the pinned host buffer (no copy pass after the run)
-      const int *row = spec + static_cast<int64_t>(spec_row_s) * n;
-      for (int i = tid; i < nin_s; i += kTailThreads) hinl[i] = ld_agent(&row[i]);
-    }
+    const int *row = spec + static_cast<int64_t>(spec_row_s) * n;
+    for (int i = tid; i < nin_s; i += kTailThreads) hinl[i] = ld_agent(&row[i]);
     return;
   }
   const bool have = have_s != 0;
@@ -1225,16 +1211,10 @@ __device__ void replay_inliers(const Pt *__restrict__ pts, int n, const int *cou
       base_s = acc;
     }
     __syncthreads();
-    if (take) {
-      res->inliers[woff[w] + before] = i;
-      if (hinl) hinl[woff[w] + before] = i;
-    }
+    if (take) hinl[woff[w] + before] = i;
     __syncthreads();
   }
-  if (tid == 0) {
-    res->n_inliers = base_s;
-    if (hres) hres->n_inliers = base_s;
-  }
+  if (tid == 0) hres->n_inliers = base_s;
 }
 
 // ----------------------------------------------------------------------------------------
@@ -1433,50 +1413,30 @@ Count32qShape count32q_shape(int n, int H, int waves, int slices_per_wave) {
   return sh;
 }
 
-hipError_t launch_f8_count32q(const float4 *ptsq, const Pt *pts, int n, int H,
-                              const float *F32soa, const double *Fsoa, int64_t ld,
-                              const Count32qShape &sh, const GuardW &g, int *counts,
-                              hipStream_t s, int *gdone, int *status, const float4 *G4,
-                              const int *Hdev) {
-  hipLaunchKernelGGL((k_f8_count32q<kCountBT, kCountWhole>), dim3(static_cast<unsigned>(sh.blocks)),
-                     dim3(kCountBT), 0, s, ptsq, pts, n, H, F32soa, Fsoa, ld, sh.per_wave, g, counts,
-                     gdone, status, G4, Hdev, PruneArgs{});
+template <int MODE>
+static hipError_t count32q(const CountArgs &a, int64_t blocks, int64_t per_wave, const PruneArgs &pa,
+                           hipStream_t s) {
+  constexpr bool kWhole = MODE == kCountWhole, kRest = MODE == kCountRest;
+  hipLaunchKernelGGL((k_f8_count32q<kCountBT, MODE>), dim3(static_cast<unsigned>(blocks)),
+                     dim3(kCountBT), 0, s, a.ptsq, a.pts, a.n, a.H, a.F32soa, a.Fsoa, a.ld, per_wave,
+                     a.g, a.counts, kRest ? nullptr : a.gdone, a.status, a.G4,
+                     kWhole ? a.Hdev : nullptr, kWhole ? PruneArgs{} : pa);
   return hipGetLastError();
 }
 
-hipError_t launch_f8_count32q_prefix(const float4 *ptsq, const Pt *pts, int n, int H,
-                                     const float *F32soa, const double *Fsoa, int64_t ld,
-                                     const Count32qShape &sh, const GuardW &g, int *counts,
-                                     hipStream_t s, int *gdone, int *status, const float4 *G4,
-                                     const PruneArgs &pa) {
-  hipLaunchKernelGGL((k_f8_count32q<kCountBT, kCountPrefix>), dim3(static_cast<unsigned>(sh.blocks)),
-                     dim3(kCountBT), 0, s, ptsq, pts, n, H, F32soa, Fsoa, ld, sh.per_wave, g, counts,
-                     gdone, status, G4, nullptr, pa);
-  return hipGetLastError();
-}
-
-hipError_t launch_f8_count32q_rest(const float4 *ptsq, const Pt *pts, int n, int H,
-                                   const float *F32soa, const double *Fsoa, int64_t ld, int waves,
-                                   const Count32qShape &bound, const GuardW &g, int *counts,
-                                   hipStream_t s, int *status, const float4 *G4,
-                                   const PruneArgs &pa) {
-  const int64_t blocks = std::max<int64_t>(
-      1, std::min<int64_t>(bound.blocks, (waves + kCountBT / 64 - 1) / (kCountBT / 64)));
-  hipLaunchKernelGGL((k_f8_count32q<kCountBT, kCountRest>), dim3(static_cast<unsigned>(blocks)),
-                     dim3(kCountBT), 0, s, ptsq, pts, n, H, F32soa, Fsoa, ld, int64_t{0}, g, counts,
-                     nullptr, status, G4, nullptr, pa);
-  return hipGetLastError();
-}
-
-hipError_t launch_f8_count32q_check(const float4 *ptsq, const Pt *pts, int n, int H,
-                                    const float *F32soa, const double *Fsoa, int64_t ld,
-                                    const Count32qShape &sh, const GuardW &g, int *counts,
-                                    hipStream_t s, int *gdone, int *fbw, const float4 *G4,
-                                    const PruneArgs &pa) {
-  hipLaunchKernelGGL((k_f8_count32q<kCountBT, kCountCheck>), dim3(static_cast<unsigned>(sh.blocks)),
-                     dim3(kCountBT), 0, s, ptsq, pts, n, H, F32soa, Fsoa, ld, sh.per_wave, g, counts,
-                     gdone, fbw, G4, nullptr, pa);
-  return hipGetLastError();
+hipError_t launch_f8_count32q(int mode, const CountArgs &a, const Count32qShape &sh, int waves,
+                              const PruneArgs &pa, hipStream_t s) {
+  switch (mode) {
+    case kCountWhole: return count32q<kCountWhole>(a, sh.blocks, sh.per_wave, pa, s);
+    case kCountPrefix: return count32q<kCountPrefix>(a, sh.blocks, sh.per_wave, pa, s);
+    case kCountCheck: return count32q<kCountCheck>(a, sh.blocks, sh.per_wave, pa, s);
+    case kCountRest: {
+      const int64_t blocks = std::max<int64_t>(
+          1, std::min<int64_t>(sh.blocks, (waves + kCountBT / 64 - 1) / (kCountBT / 64)));
+      return count32q<kCountRest>(a, blocks, int64_t{0}, pa, s);
+    }
+  }
+  return hipErrorInvalidValue;
 }
 
 int select_per_block(int H) { return (H + kSelectBlocks - 1) / kSelectBlocks; }
