@@ -895,6 +895,60 @@ int rs_dense_consistency(rs_ctx *ctx, const double *depth, int32_t V, int64_t h,
 #define RS_DENSE_TIMING_SLOTS 2
 int rs_dense_timing(rs_ctx *ctx, int32_t enable, double *ms);
 
+/* Semi-global aggregation of the plane-sweep volume (dense_sgm.hip): Hirschmueller's path
+ * recursion over the (D, h, w) volume v of rs_dense_plane_sweep, then the winner of the summed
+ * cost.  Everything is fp32 and every line below is one rounded operation; there is no
+ * multiplication, so nothing can contract, and tests/dense_sgm_ref.py restates it bit for bit.
+ *   1. Cost.  c(p, k) = 1.0f - v(p, k) where v is valid, 1.0f where v is NaN: an invalid
+ *      hypothesis costs what an uncorrelated one does, and still passes messages.
+ *   2. Directions r = (dx, dy), in this order: (1,0) (-1,0) (0,1) (0,-1) (1,1) (-1,-1) (1,-1)
+ *      (-1,1).  paths is 4 (the first four) or 8.
+ *   3. Path.  For direction r and pixel p with predecessor q = p - r: L_r(p, k) = c(p, k) when q
+ *      is outside the image.  Otherwise, with m = min_k L_r(q, k),
+ *        t = min(L_r(q, k), m + p2, L_r(q, k-1) + p1, L_r(q, k+1) + p1),
+ *      the k-1 and k+1 terms only inside 0..D-1, and L_r(p, k) = (c(p, k) + t) - m.
+ *   4. Sum.  S(p, k) = (((L_0 + L_1) + L_2) + ...) in direction order.
+ *   5. Winner.  index(p) = the smallest k with minimal S among the valid hypotheses of p (v not
+ *      NaN); -1 where p has none, which is the -1 set of rs_dense_plane_sweep.
+ *   6. Offset.  With b = S(index - 1), a = S(index + 1), den = (b - 2 S(index)) + a:
+ *      delta = clamp((0.5f (b - a)) / den, -0.5, 0.5) when both neighbours exist and are valid
+ *      and den > 0, else 0.  The sign convention is that of rs_dense_plane_sweep's delta.
+ *   7. Score.  score(p) = v(p, index), the winner's own ZNCC; NaN at index -1.
+ * No atomics, one launch per direction in order: the same inputs give bitwise the same outputs.
+ *
+ * rs_dense_aggregate: volume (D, h, w) float on the host; index (h, w) int32, delta and score
+ * (h, w) float; agg (D, h, w) float receives S when not null, and the other outputs do not depend
+ * on that.  RS_EINVAL before any launch: a null pointer other than agg, D outside
+ * 1..RS_DENSE_SGM_MAX_DEPTHS, a side outside 1..RS_DENSE_MAX_SIDE,
+ * D h w > RS_DENSE_SGM_MAX_VOLUME (the volume, c and S live in scratch at once), paths not 4 or 8,
+ * p1 or p2 not finite, or not 0 <= p1 <= p2. */
+#define RS_DENSE_SGM_MAX_DEPTHS 256
+#define RS_DENSE_SGM_MAX_VOLUME (1LL << 27)
+int rs_dense_aggregate(rs_ctx *ctx, const float *volume, int64_t D, int64_t h, int64_t w,
+                       float p1, float p2, int32_t paths, int32_t *index, float *delta,
+                       float *score, float *agg);
+
+/* rs_dense_plane_sweep followed by the aggregation above without a visit to the host: the sweep
+ * kernel writes its volume to device scratch, the aggregation and the winner run on it there, and
+ * only the four maps come down, plus volume and agg (both (D, h, w) float) when not null.  index,
+ * delta and score are those of the aggregation; nvalid is the winner-takes-all winner's number of
+ * sources, exactly as rs_dense_plane_sweep gives it (it is not the count of the aggregated
+ * winner).  volume is bitwise that of rs_dense_plane_sweep.  RS_EINVAL before any launch: every
+ * limit of rs_dense_plane_sweep and of rs_dense_aggregate (D <= RS_DENSE_SGM_MAX_DEPTHS and
+ * D h w <= RS_DENSE_SGM_MAX_VOLUME whether or not a volume is asked for). */
+int rs_dense_plane_sweep_sgm(rs_ctx *ctx, const uint8_t *ref, int64_t h, int64_t w,
+                             const uint8_t *src, int32_t S, const double *A, const double *b,
+                             const double *depths, int64_t D, int32_t patch, double min_var,
+                             float p1, float p2, int32_t paths, int32_t *index, float *delta,
+                             float *score, uint8_t *nvalid, float *volume, float *agg);
+
+/* HIP events between the stages of the next aggregation calls (enable != 0).  Returns the last
+ * timed calls' device ms: slot 0 the sweep kernel (rs_dense_plane_sweep_sgm only), slot 1 the
+ * aggregation (cost, one launch per direction, S back to the volume's layout), slot 2 the
+ * winner; -1 where none (tools/bench_dense_sgm.py).  rs_dense_timing does not see these calls. */
+#define RS_DENSE_SGM_TIMING_SLOTS 3
+int rs_dense_sgm_timing(rs_ctx *ctx, int32_t enable, double *ms);
+
 /* ------------------------------------------------------------------------------------------
  * The surface stage (surface.hip): depth maps fused into a truncated signed distance volume and
  * a welded, consistently oriented triangle mesh extracted from it.  The reference project has no

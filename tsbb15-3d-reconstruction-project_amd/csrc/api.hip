@@ -125,6 +125,7 @@ extern "C" int rs_ctx_destroy(rs_ctx *c) {
   c->feat.destroy();
   c->cloud.destroy();
   c->dense.destroy();
+  c->dense_sgm.destroy();
   c->surface.destroy();
   if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
   if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -240,13 +240,9 @@ void launch_sweep(dim3 grid, hipStream_t s, const uint8_t *ref, const uint8_t *s
 
 }  // namespace
 
-extern "C" int rs_dense_plane_sweep(rs_ctx *c, const uint8_t *ref, int64_t h, int64_t w,
-                                    const uint8_t *src, int32_t S, const double *A,
-                                    const double *b, const double *depths, int64_t D,
-                                    int32_t patch, double min_var, int32_t *index, float *delta,
-                                    float *score, uint8_t *nvalid, float *volume) {
-  if (!c || !ref || !src || !A || !b || !depths || !index || !delta || !score || !nvalid)
-    return fail(RS_EINVAL, "null pointer");
+int rs::dense_sweep_check(int64_t h, int64_t w, int32_t S, const double *A, const double *b,
+                          const double *depths, int64_t D, int32_t patch, double min_var,
+                          bool with_volume) {
   if (patch < 3 || patch > RS_DENSE_MAX_PATCH || patch % 2 == 0)
     return fail(RS_EINVAL, "patch must be odd, in 3..11");
   if (S < 1 || S > RS_DENSE_MAX_SOURCES) return fail(RS_EINVAL, "1 to 8 source views");
@@ -254,7 +250,7 @@ extern "C" int rs_dense_plane_sweep(rs_ctx *c, const uint8_t *ref, int64_t h, in
   if (h <= patch || w <= patch || h > RS_DENSE_MAX_SIDE || w > RS_DENSE_MAX_SIDE)
     return fail(RS_EINVAL, "each image side must be above patch and at most 16384");
   if (h * w > RS_DENSE_MAX_PIXELS) return fail(RS_EINVAL, "more than 2^26 pixels");
-  if (volume && D * h * w > RS_DENSE_MAX_VOLUME)
+  if (with_volume && D * h * w > RS_DENSE_MAX_VOLUME)
     return fail(RS_EINVAL, "a cost volume of more than 2^28 entries");
   if (!std::isfinite(min_var) || !(min_var > 0.0))
     return fail(RS_EINVAL, "min_var must be finite and positive");
@@ -266,6 +262,44 @@ extern "C" int rs_dense_plane_sweep(rs_ctx *c, const uint8_t *ref, int64_t h, in
     if ((depths[k] > 0.0) != (depths[0] > 0.0))
       return fail(RS_EINVAL, "depths must all have one sign");
   }
+  return RS_OK;
+}
+
+void rs::dense_sweep_launch(hipStream_t s, const uint8_t *ref, const uint8_t *src, int64_t h,
+                            int64_t w, int32_t S, const double *A, const double *b,
+                            const double *depths, int64_t D, int32_t patch, double min_var,
+                            int32_t *index, float *delta, float *score, uint8_t *nvalid,
+                            float *volume) {
+  rsd::DenseWarp W;
+  std::memset(&W, 0, sizeof(W));
+  std::memcpy(W.A, A, sizeof(double) * 9 * S);
+  std::memcpy(W.b, b, sizeof(double) * 3 * S);
+  const double n = static_cast<double>(patch) * patch;
+  const double thr = min_var * n * n;
+  const dim3 grid(static_cast<unsigned>((w + rsd::kDenseTX - 1) / rsd::kDenseTX),
+                  static_cast<unsigned>((h + rsd::kDenseTY - 1) / rsd::kDenseTY));
+#define RS_DENSE_LAUNCH(R)                                                                      \
+  launch_sweep<R>(grid, s, ref, src, static_cast<int>(h), static_cast<int>(w), S, W, depths,   \
+                  static_cast<int>(D), thr, index, delta, score, nvalid, volume)
+  switch (patch / 2) {
+    case 1: RS_DENSE_LAUNCH(1); break;
+    case 2: RS_DENSE_LAUNCH(2); break;
+    case 3: RS_DENSE_LAUNCH(3); break;
+    case 4: RS_DENSE_LAUNCH(4); break;
+    default: RS_DENSE_LAUNCH(5); break;
+  }
+#undef RS_DENSE_LAUNCH
+}
+
+extern "C" int rs_dense_plane_sweep(rs_ctx *c, const uint8_t *ref, int64_t h, int64_t w,
+                                    const uint8_t *src, int32_t S, const double *A,
+                                    const double *b, const double *depths, int64_t D,
+                                    int32_t patch, double min_var, int32_t *index, float *delta,
+                                    float *score, uint8_t *nvalid, float *volume) {
+  if (!c || !ref || !src || !A || !b || !depths || !index || !delta || !score || !nvalid)
+    return fail(RS_EINVAL, "null pointer");
+  int st = rs::dense_sweep_check(h, w, S, A, b, depths, D, patch, min_var, volume != nullptr);
+  if (st) return st;
 
   const size_t hw = static_cast<size_t>(h * w);
   // [ref | src | depths] go up, [index | delta | score | nvalid | volume] come down
@@ -277,40 +311,19 @@ extern "C" int rs_dense_plane_sweep(rs_ctx *c, const uint8_t *ref, int64_t h, in
   const auto b_nvalid = L.add<uint8_t>(hw);
   const auto b_volume = L.add<float>(volume ? hw * D : 0);
   HIP_TRY(hipSetDevice(c->device));
-  int st = L.bind(c);
-  if (st) return st;
+  if ((st = L.bind(c))) return st;
   hipStream_t s = c->stream;
   HIP_TRY(hipMemcpyAsync(b_ref.dev(), ref, b_ref.bytes, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(b_src.dev(), src, b_src.bytes, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(b_depths.dev(), depths, b_depths.bytes, hipMemcpyHostToDevice, s));
 
-  rsd::DenseWarp W;
-  std::memset(&W, 0, sizeof(W));
-  std::memcpy(W.A, A, sizeof(double) * 9 * S);
-  std::memcpy(W.b, b, sizeof(double) * 3 * S);
-  const double n = static_cast<double>(patch) * patch;
-  const double thr = min_var * n * n;
-  const dim3 grid(static_cast<unsigned>((w + rsd::kDenseTX - 1) / rsd::kDenseTX),
-                  static_cast<unsigned>((h + rsd::kDenseTY - 1) / rsd::kDenseTY));
-  const uint8_t *d_ref = b_ref.dev(), *d_src = b_src.dev();
-  const double *d_depths = b_depths.dev();
   int32_t *d_index = b_index.dev();
   float *d_delta = b_delta.dev(), *d_score = b_score.dev();
   uint8_t *d_nvalid = b_nvalid.dev();
   float *d_volume = volume ? b_volume.dev() : nullptr;
   if ((st = c->dense.mark(0, s))) return st;
-#define RS_DENSE_LAUNCH(R)                                                                      \
-  launch_sweep<R>(grid, s, d_ref, d_src, static_cast<int>(h), static_cast<int>(w), S, W,       \
-                  d_depths, static_cast<int>(D), thr, d_index, d_delta, d_score, d_nvalid,     \
-                  d_volume)
-  switch (patch / 2) {
-    case 1: RS_DENSE_LAUNCH(1); break;
-    case 2: RS_DENSE_LAUNCH(2); break;
-    case 3: RS_DENSE_LAUNCH(3); break;
-    case 4: RS_DENSE_LAUNCH(4); break;
-    default: RS_DENSE_LAUNCH(5); break;
-  }
-#undef RS_DENSE_LAUNCH
+  rs::dense_sweep_launch(s, b_ref.dev(), b_src.dev(), h, w, S, A, b, b_depths.dev(), D, patch,
+                         min_var, d_index, d_delta, d_score, d_nvalid, d_volume);
   HIP_TRY(hipGetLastError());
   if ((st = c->dense.mark(1, s))) return st;
   HIP_TRY(hipMemcpyAsync(index, d_index, b_index.bytes, hipMemcpyDeviceToHost, s));

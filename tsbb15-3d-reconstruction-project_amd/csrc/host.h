@@ -116,6 +116,9 @@ struct rs_ctx {
   // rs_dense_timing: around the kernel of the next dense calls (dense.hip): plane sweep,
   // consistency
   rs::StageTimer<2, RS_DENSE_TIMING_SLOTS> dense{-1.0};
+  // rs_dense_sgm_timing: between the stages of the next aggregation calls (dense_sgm.hip):
+  // sweep, aggregate, select
+  rs::StageTimer<4, RS_DENSE_SGM_TIMING_SLOTS> dense_sgm{-1.0};
   // rs_surface_timing: around the kernels of the next surface calls (surface.hip): integrate,
   // classify, scan, emit
   rs::StageTimer<5, RS_SURFACE_TIMING_SLOTS> surface{-1.0};
@@ -221,5 +224,16 @@ struct PairsDev {
 int pairs_enqueue(rs_ctx *c, const double *p1, const double *p2, const int64_t *off, int64_t B,
                   int64_t H, int32_t mode, uint64_t seed_base, const int64_t *seed_ids,
                   const int32_t *host_tuples, double thresh, size_t extra, PairsDev *d);
+// The plane sweep's argument rules (rs_dense_plane_sweep's RS_EINVAL list; `with_volume`: the
+// D h w limit applies) and the launch of its kernel k_dense_sweep<patch / 2> on device buffers
+// (dense.hip); A and b are host arrays, volume may be null.
+int dense_sweep_check(int64_t h, int64_t w, int32_t S, const double *A, const double *b,
+                      const double *depths, int64_t D, int32_t patch, double min_var,
+                      bool with_volume);
+void dense_sweep_launch(hipStream_t s, const uint8_t *ref, const uint8_t *src, int64_t h,
+                        int64_t w, int32_t S, const double *A, const double *b,
+                        const double *depths, int64_t D, int32_t patch, double min_var,
+                        int32_t *index, float *delta, float *score, uint8_t *nvalid,
+                        float *volume);
 int fmatrix_stls_lsq(rs_ctx *c, const double *pl, const double *pr, int64_t n, double *F_out);
 }  // namespace rs

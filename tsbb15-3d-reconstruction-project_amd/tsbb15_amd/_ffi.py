@@ -217,6 +217,13 @@ _SIGS = {
     "rs_dense_consistency": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_int64, C.c_int64, _dp,
                                        _dp, C.c_double, _u8p]),
     "rs_dense_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "rs_dense_aggregate": (C.c_int, [C.c_void_p, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_float,
+                                     C.c_float, C.c_int32, _i32p, _fp, _fp, _fp]),
+    "rs_dense_plane_sweep_sgm": (C.c_int, [C.c_void_p, _u8p, C.c_int64, C.c_int64, _u8p,
+                                           C.c_int32, _dp, _dp, _dp, C.c_int64, C.c_int32,
+                                           C.c_double, C.c_float, C.c_float, C.c_int32, _i32p,
+                                           _fp, _fp, _u8p, _fp, _fp]),
+    "rs_dense_sgm_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
     "rs_surface_integrate": (C.c_int, [C.c_void_p, _dp, _fp, C.c_int32, C.c_int64, C.c_int64, _dp,
                                        _dp, C.c_double, C.c_int64, C.c_int64, C.c_int64,
                                        C.c_double, C.c_int32, _fp, _fp]),

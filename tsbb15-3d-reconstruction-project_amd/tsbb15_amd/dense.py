@@ -4,6 +4,10 @@ it to an outside tool; nothing here restates code of it.
 
   * ``plane_sweep``    winner-takes-all ZNCC plane sweep of one reference view against up to
                        eight source views (rs_dense_plane_sweep)
+  * ``aggregate``      semi-global aggregation of a sweep's cost volume and the winner of the
+                       summed cost (rs_dense_aggregate)
+  * ``plane_sweep_sgm`` the sweep and the aggregation in one call, the volume staying on the
+                       device (rs_dense_plane_sweep_sgm)
   * ``refine_depth``   index + sub-index offset -> depth, linear in 1 / depth (host)
   * ``consistency``    per pixel, the number of other views whose depth map agrees
                        (rs_dense_consistency)
@@ -35,6 +39,9 @@ MAX_PIXELS = 1 << 26
 MAX_VOLUME = 1 << 28
 MAX_VIEWS = 128
 STAGES = ("plane_sweep", "consistency")
+SGM_MAX_DEPTHS = 256
+SGM_MAX_VOLUME = 1 << 27
+SGM_STAGES = ("sweep", "aggregate", "select")
 
 
 def _ctx(ctx):
@@ -128,6 +135,28 @@ def plane_sweep(ref_image, ref_cam, src_images, src_cams, K, depths, patch=7, mi
     image not 2-D uint8, mixed shapes, cameras not finite, K's last row not (0, 0, 1), a
     singular reference camera, min_var not finite or <= 0, depths zero, non-finite or of mixed
     sign."""
+    ref, src, A, b, depths, patch, min_var = _sweep_args(
+        ref_image, ref_cam, src_images, src_cams, K, depths, patch, min_var)
+    (h, w), D = ref.shape, len(depths)
+    if return_volume and D * h * w > MAX_VOLUME:
+        raise ValueError('a cost volume of more than 2^28 entries')
+    index = np.empty((h, w), np.int32)
+    delta, score = np.empty((h, w), np.float32), np.empty((h, w), np.float32)
+    nvalid = np.empty((h, w), np.uint8)
+    volume = np.empty((D, h, w), np.float32) if return_volume else None
+    _ffi.check(_ffi.lib().rs_dense_plane_sweep(
+        _ctx(ctx), _ffi.ptr(ref, _u8), h, w, _ffi.ptr(src, _u8), len(src), _ffi.ptr(A, _d),
+        _ffi.ptr(b, _d), _ffi.ptr(depths, _d), D, patch, min_var, _ffi.ptr(index, _i32),
+        _ffi.ptr(delta, _f), _ffi.ptr(score, _f), _ffi.ptr(nvalid, _u8),
+        _ffi.ptr(volume, _f) if return_volume else None))
+    if return_volume:
+        return index, delta, score, nvalid, volume
+    return index, delta, score, nvalid
+
+
+def _sweep_args(ref_image, ref_cam, src_images, src_cams, K, depths, patch, min_var):
+    """The checked arguments of a sweep: (ref, src (S, h, w), A, b, depths, patch, min_var);
+    ValueError as ``plane_sweep`` lists them, but for the volume's size."""
     ref = _image(ref_image, 'ref_image')
     srcs = [_image(s, 'a source image') for s in src_images]
     if not 1 <= len(srcs) <= MAX_SOURCES:
@@ -146,27 +175,98 @@ def plane_sweep(ref_image, ref_cam, src_images, src_cams, K, depths, patch=7, mi
     if not np.isfinite(min_var) or not min_var > 0.0:
         raise ValueError('min_var must be finite and positive')
     depths = _depths(depths)
-    D = len(depths)
-    if return_volume and D * h * w > MAX_VOLUME:
-        raise ValueError('a cost volume of more than 2^28 entries')
     A, b = plane_warps(ref_cam, src_cams, K)
     if len(A) != len(srcs):
         raise ValueError('one camera per source image')
     if not (np.all(np.isfinite(A)) and np.all(np.isfinite(b))):
         raise ValueError('the plane warps are not finite')
-    src = np.ascontiguousarray(np.stack(srcs))
+    return ref, np.ascontiguousarray(np.stack(srcs)), A, b, depths, patch, min_var
+
+
+def _sgm_args(D, h, w, p1, p2, paths):
+    """(p1, p2, paths) checked against the aggregation's limits for a (D, h, w) volume."""
+    if not 1 <= D <= SGM_MAX_DEPTHS:
+        raise ValueError('1 to 256 depth hypotheses for the aggregation')
+    if min(h, w) < 1 or max(h, w) > MAX_SIDE:
+        raise ValueError('each image side must be in 1..16384')
+    if D * h * w > SGM_MAX_VOLUME:
+        raise ValueError('a volume of more than 2^27 entries for the aggregation')
+    if paths not in (4, 8):
+        raise ValueError('paths must be 4 or 8')
+    p1, p2 = np.float32(p1), np.float32(p2)
+    if not (np.isfinite(p1) and np.isfinite(p2) and 0.0 <= p1 <= p2):
+        raise ValueError('p1 and p2 must be finite with 0 <= p1 <= p2')
+    return float(p1), float(p2), int(paths)
+
+
+def aggregate(volume, p1=0.1, p2=1.0, paths=8, return_aggregated=False, ctx=None):
+    """Semi-global aggregation of a sweep's cost volume and the winner of the summed cost
+    (rs_dense_aggregate; the definition stands in include/rsamd.h).
+
+    ``volume`` is (D, h, w) float32 with NaN for invalid hypotheses, as ``plane_sweep`` returns
+    it.  The cost 1 - volume (1 where NaN) is passed along ``paths`` = 4 or 8 directions with
+    the penalties ``p1`` for a step of one plane and ``p2`` for a larger jump (float32), and the
+    direction sums are added in a fixed order into S.
+
+    Returns (index, delta, score[, S]): index (h, w) int32 the valid hypothesis of smallest S
+    (the smallest k on ties), -1 where the pixel has none -- the same -1 set as the sweep's;
+    delta (h, w) float32 the parabola vertex of S through the winner and its neighbours in
+    [-0.5, 0.5], 0 where a neighbour is missing or invalid, with ``plane_sweep``'s sign, so
+    ``refine_depth`` applies unchanged; score (h, w) float32 the winner's own entry of
+    ``volume`` (NaN at -1); S (D, h, w) float32 only with ``return_aggregated``.
+
+    ValueError before any launch: a volume not 3-D float32, D outside 1..256, a side above
+    16384, D h w > 2^27, paths not 4 or 8, p1 or p2 not finite or not 0 <= p1 <= p2."""
+    volume = np.asarray(volume)
+    if volume.dtype != np.float32 or volume.ndim != 3:
+        raise ValueError('volume must be a (D, h, w) float32 array')
+    D, h, w = volume.shape
+    p1, p2, paths = _sgm_args(D, h, w, p1, p2, paths)
+    volume = np.ascontiguousarray(volume)
+    index = np.empty((h, w), np.int32)
+    delta, score = np.empty((h, w), np.float32), np.empty((h, w), np.float32)
+    agg = np.empty((D, h, w), np.float32) if return_aggregated else None
+    _ffi.check(_ffi.lib().rs_dense_aggregate(
+        _ctx(ctx), _ffi.ptr(volume, _f), D, h, w, p1, p2, paths, _ffi.ptr(index, _i32),
+        _ffi.ptr(delta, _f), _ffi.ptr(score, _f),
+        _ffi.ptr(agg, _f) if return_aggregated else None))
+    return (index, delta, score, agg) if return_aggregated else (index, delta, score)
+
+
+def plane_sweep_sgm(ref_image, ref_cam, src_images, src_cams, K, depths, patch=7, min_var=4.0,
+                    p1=0.1, p2=1.0, paths=8, return_volume=False, return_aggregated=False,
+                    ctx=None):
+    """``plane_sweep`` followed by ``aggregate`` in one call (rs_dense_plane_sweep_sgm): the
+    volume goes from the sweep kernel to the aggregation in device memory and comes down only
+    when asked for.
+
+    Returns (index, delta, score, nvalid[, volume][, S]).  index, delta and score are those of
+    ``aggregate`` on the sweep's volume; nvalid is the winner-takes-all winner's number of
+    sources, exactly ``plane_sweep``'s; volume is bitwise ``plane_sweep``'s.
+
+    ValueError before any launch: everything ``plane_sweep`` and ``aggregate`` list; D <= 256
+    and D h w <= 2^27 hold whether or not a volume is returned."""
+    ref, src, A, b, depths, patch, min_var = _sweep_args(
+        ref_image, ref_cam, src_images, src_cams, K, depths, patch, min_var)
+    (h, w), D = ref.shape, len(depths)
+    p1, p2, paths = _sgm_args(D, h, w, p1, p2, paths)
     index = np.empty((h, w), np.int32)
     delta, score = np.empty((h, w), np.float32), np.empty((h, w), np.float32)
     nvalid = np.empty((h, w), np.uint8)
     volume = np.empty((D, h, w), np.float32) if return_volume else None
-    _ffi.check(_ffi.lib().rs_dense_plane_sweep(
-        _ctx(ctx), _ffi.ptr(ref, _u8), h, w, _ffi.ptr(src, _u8), len(srcs), _ffi.ptr(A, _d),
-        _ffi.ptr(b, _d), _ffi.ptr(depths, _d), D, patch, min_var, _ffi.ptr(index, _i32),
-        _ffi.ptr(delta, _f), _ffi.ptr(score, _f), _ffi.ptr(nvalid, _u8),
-        _ffi.ptr(volume, _f) if return_volume else None))
+    agg = np.empty((D, h, w), np.float32) if return_aggregated else None
+    _ffi.check(_ffi.lib().rs_dense_plane_sweep_sgm(
+        _ctx(ctx), _ffi.ptr(ref, _u8), h, w, _ffi.ptr(src, _u8), len(src), _ffi.ptr(A, _d),
+        _ffi.ptr(b, _d), _ffi.ptr(depths, _d), D, patch, min_var, p1, p2, paths,
+        _ffi.ptr(index, _i32), _ffi.ptr(delta, _f), _ffi.ptr(score, _f), _ffi.ptr(nvalid, _u8),
+        _ffi.ptr(volume, _f) if return_volume else None,
+        _ffi.ptr(agg, _f) if return_aggregated else None))
+    out = (index, delta, score, nvalid)
     if return_volume:
-        return index, delta, score, nvalid, volume
-    return index, delta, score, nvalid
+        out += (volume,)
+    if return_aggregated:
+        out += (agg,)
+    return out
 
 
 def refine_depth(index, delta, depths):
@@ -229,10 +329,12 @@ def depth_points(depth, cam, K):
 
 
 def fuse(images, cams, K, depths, neighbours=2, patch=7, min_var=4.0, min_views=2,
-         rel_tol=0.01, return_maps=False, ctx=None):
+         rel_tol=0.01, return_maps=False, smooth=None, ctx=None):
     """Dense cloud of V posed views: every view is swept against its ``neighbours`` nearest
     views by index on either side, the depths are refined, ``consistency`` counts the agreeing
-    views over all V maps, and the pixels with count >= min_views are kept.
+    views over all V maps, and the pixels with count >= min_views are kept.  ``smooth`` =
+    (p1, p2) or (p1, p2, paths) sweeps every view with ``plane_sweep_sgm`` instead of
+    ``plane_sweep``; None is the winner-takes-all sweep.
 
     Returns (points (N, 3), grey (N,) in [0, 1], view (N,) int32), view by view in row-major
     pixel order -- ready for ``cloud.surface_normals`` and, with the grey repeated into three
@@ -242,11 +344,16 @@ def fuse(images, cams, K, depths, neighbours=2, patch=7, min_var=4.0, min_views=
     V = len(cams)
     if len(images) != V:
         raise ValueError('one image per camera')
+    sweep, sweep_kw = plane_sweep, {}
+    if smooth is not None:
+        if len(smooth) not in (2, 3):
+            raise ValueError('smooth must be (p1, p2) or (p1, p2, paths)')
+        sweep, sweep_kw = plane_sweep_sgm, dict(zip(("p1", "p2", "paths"), smooth))
     maps = {"index": [], "delta": [], "depth": []}
     for i in range(V):
         nb = [j for j in range(i - neighbours, i + neighbours + 1) if j != i and 0 <= j < V]
-        index, delta, _, _ = plane_sweep(images[i], cams[i], [images[j] for j in nb], cams[nb],
-                                         K, depths, patch=patch, min_var=min_var, ctx=ctx)
+        index, delta, _, _ = sweep(images[i], cams[i], [images[j] for j in nb], cams[nb],
+                                   K, depths, patch=patch, min_var=min_var, ctx=ctx, **sweep_kw)
         maps["index"].append(index)
         maps["delta"].append(delta)
         maps["depth"].append(refine_depth(index, delta, depths))
@@ -275,3 +382,14 @@ def timing(enable, ctx=None):
     ms = np.zeros(len(STAGES))
     _ffi.check(_ffi.lib().rs_dense_timing(ctx.handle, int(enable), _ffi.ptr(ms, _d)))
     return dict(zip(STAGES, ms.tolist()))
+
+
+def sgm_timing(enable, ctx=None):
+    """Enable / disable HIP events between the stages of the next ``aggregate`` and
+    ``plane_sweep_sgm`` calls (rs_dense_sgm_timing); returns the last timed calls' {sweep,
+    aggregate, select: device ms}, -1 where none.  ``aggregate`` has no sweep and leaves that
+    slot alone."""
+    ctx = ctx or _ffi.default_context()
+    ms = np.zeros(len(SGM_STAGES))
+    _ffi.check(_ffi.lib().rs_dense_sgm_timing(ctx.handle, int(enable), _ffi.ptr(ms, _d)))
+    return dict(zip(SGM_STAGES, ms.tolist()))

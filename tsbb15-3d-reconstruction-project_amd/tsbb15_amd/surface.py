@@ -291,7 +291,8 @@ def reconstruct(images, cams, K, depths, origin, voxel, dims, trunc, min_weight=
                 **fuse_kw):
     """Posed images to a mesh: ``dense.fuse(..., return_maps=True)``, the depth set to NaN where
     ``keep`` is false, ``integrate`` with ``count`` as the weight, ``extract``.  ``fuse_kw`` goes
-    to ``dense.fuse``.  Returns (vertices, faces, tsdf, weight)."""
+    to ``dense.fuse``: ``smooth=(p1, p2)`` there picks the depth maps' winners after semi-global
+    aggregation.  Returns (vertices, faces, tsdf, weight)."""
     fuse_kw.pop('return_maps', None)
     maps = dense.fuse(images, cams, K, depths, return_maps=True, ctx=ctx, **fuse_kw)[-1]
     depth = np.where(maps["keep"], maps["depth"], np.nan)
