@@ -1024,6 +1024,79 @@ int rs_surface_extract(rs_ctx *ctx, const float *tsdf, const float *weight, int6
 int rs_surface_timing(rs_ctx *ctx, int32_t enable, double *ms);
 
 /* ------------------------------------------------------------------------------------------
+ * Colour for the mesh (surface_texture.hip): the mesh rendered into a z-buffer per view, and a
+ * colour per vertex from the views that see it.  The reference project has no such code; nothing
+ * here restates code of it.  Both entry points are bitwise reproducible from run to run: the only
+ * atomics are a minimum, which commutes, and the counter of a list whose order cannot matter.
+ *   Conventions are those above: P = K C per view (3, 4) row-major, pixel centres at integers,
+ * images uint8, at most RS_DENSE_MAX_VIEWS views and the image limits of rs_dense_consistency.
+ * Every camera is turned so that "in front" means a positive third coordinate: with
+ * s_v = sign(det(P_v[:, :3])) the rules below read s_v P_v for P.  Negating a camera flips s_v
+ * and so changes nothing at all: cameras with negative depths give the positive scene's result
+ * bit for bit.
+ * ------------------------------------------------------------------------------------------ */
+/* A face whose clipped bounding box holds more pixels than this is drawn by a whole wave, lanes
+ * across the box, and not by the lane that found it (the size boundaries of a test).  The value
+ * is measured: DESIGN.md section 16. */
+#ifndef RS_SURFACE_RASTER_SMALL
+#define RS_SURFACE_RASTER_SMALL 32
+#endif
+/* Entries of the list of such faces, (face, view) pairs.  A face that finds the list full is
+ * drawn by its own lane after all: slower, the same bits. */
+#define RS_SURFACE_TEXTURE_LIST_CAP (1 << 20)
+
+/* The z-buffers of a mesh: depth is (V, h, w) float, NaN where no face covers the pixel.
+ * vertices is (nv, 3) fp64, faces (nf, 3) int32, P (V, 3, 4).  All arithmetic is fp64.
+ *   Per view and face, with X_i the face's vertices: q_i = P [X_i; 1], z_i = q_i2.  The face is
+ *   drawn iff all nine components of q are finite and all three z_i > 0: a face that crosses the
+ *   camera plane is skipped, not clipped.  x_i = q_i0 / z_i, y_i = q_i1 / z_i,
+ *   A = (x1 - x0)(y2 - y0) - (x2 - x0)(y1 - y0); the face is skipped when A is 0 or not finite.
+ *   Both windings are drawn, there is no back-face culling: an open mesh occludes from both sides.
+ *   Candidate pixels are the integer (px, py) in [ceil(min x), floor(max x)] x
+ *   [ceil(min y), floor(max y)], intersected with the image.  With
+ *     b0 = ((x2 - x1)(py - y1) - (y2 - y1)(px - x1)) / A,
+ *     b1 = ((x0 - x2)(py - y2) - (y0 - y2)(px - x2)) / A,
+ *     b2 = ((x1 - x0)(py - y0) - (y1 - y0)(px - x0)) / A,
+ *   each from its own edge function, the pixel is covered iff b0, b1, b2 >= 0.  Its depth is
+ *   perspective-correct, zeta = 1 / (b0 / z0 + b1 / z1 + b2 / z2), rounded once to float, and the
+ *   pixel keeps the minimum over all the faces that cover it.
+ * RS_EINVAL before any launch: nv or 3 nf outside 0..2^31 - 1, a face index outside 0..nv - 1,
+ * V outside 1..RS_DENSE_MAX_VIEWS, the image limits of rs_dense_consistency, a camera that is not
+ * finite or whose det(P[:, :3]) is zero or not finite. */
+int rs_surface_render_depth(rs_ctx *ctx, const double *vertices, int64_t nv,
+                            const int32_t *faces, int64_t nf, const double *P, int32_t V,
+                            int64_t h, int64_t w, float *depth);
+
+/* A colour per vertex.  The z-buffers are rendered as above and stay in device memory; images is
+ * (V, h, w, channels) uint8 with channels 1 or 3, normals (nv, 3) fp64 or null.  Per vertex X,
+ * the views in index order, all fp64:
+ *   q = P_v [X; 1], z = q2; the view is skipped unless q is finite and z > 0.  u = q0 / z,
+ *   v = q1 / z; the vertex is inside iff 0 <= u <= w - 1 and 0 <= v <= h - 1.  x0 = floor(u),
+ *   y0 = floor(v), x1 = min(x0 + 1, w - 1), y1 = min(y0 + 1, h - 1): the footprint of the dense
+ *   stage's bilinear rule.  far is the largest finite z-buffer value among the footprint's four
+ *   pixels; without one the vertex is not visible, and otherwise it is visible iff
+ *   z <= far (1 + rel_tol).  With normals, g = (n . (c_v - X)) / |c_v - X| with the camera centre
+ *   c_v = -M_v^-1 p_v, P_v = [M_v | p_v]; the view contributes iff g > min_cos, with weight g.
+ *   Without normals the weight g is 1 and min_cos is not read.  Per channel, with fx = u - x0 and
+ *   fy = v - y0: top = I[y0, x0] + fx (I[y0, x1] - I[y0, x0]), bot likewise on row y1,
+ *   s = top + fy (bot - top); acc += g s, wsum += g, count += 1.
+ * colors is (nv, channels) fp64, acc / (255 wsum), and 0 where count, (nv) int32, is 0.  depth is
+ * null or (V, h, w) float and then receives the z-buffers of rs_surface_render_depth.
+ * RS_EINVAL before any launch: what rs_surface_render_depth lists, channels not 1 or 3, rel_tol
+ * not finite or negative, min_cos not finite. */
+int rs_surface_colorize(rs_ctx *ctx, const double *vertices, int64_t nv, const int32_t *faces,
+                        int64_t nf, const uint8_t *images, int32_t channels, const double *P,
+                        int32_t V, int64_t h, int64_t w, const double *normals, double rel_tol,
+                        double min_cos, double *colors, int32_t *count, float *depth);
+
+/* HIP events around the kernels of the next two calls above (enable != 0).  Returns the last
+ * timed calls' device ms: slot 0 raster_small (the fill and the lane-per-face kernel), 1
+ * raster_large (the wave-per-face kernel and +inf to NaN), 2 gather (rs_surface_colorize only);
+ * -1 where none (tools/bench_texture.py).  rs_surface_timing does not see these calls. */
+#define RS_SURFACE_TEXTURE_TIMING_SLOTS 3
+int rs_surface_texture_timing(rs_ctx *ctx, int32_t enable, double *ms);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU (RCCL over xGMI).  One process per GPU; the unique id travels out of band.
  * ---------------------------------------------------------------------------------------- */
 #define RS_COMM_ID_BYTES 128

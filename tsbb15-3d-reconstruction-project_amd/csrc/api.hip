@@ -127,6 +127,7 @@ extern "C" int rs_ctx_destroy(rs_ctx *c) {
   c->dense.destroy();
   c->dense_sgm.destroy();
   c->surface.destroy();
+  c->texture.destroy();
   if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;

@@ -122,6 +122,9 @@ struct rs_ctx {
   // rs_surface_timing: around the kernels of the next surface calls (surface.hip): integrate,
   // classify, scan, emit
   rs::StageTimer<5, RS_SURFACE_TIMING_SLOTS> surface{-1.0};
+  // rs_surface_texture_timing: around the kernels of the next mesh-colouring calls
+  // (surface_texture.hip): raster_small, raster_large, gather
+  rs::StageTimer<4, RS_SURFACE_TEXTURE_TIMING_SLOTS> texture{-1.0};
 };
 
 namespace rs {

@@ -231,6 +231,12 @@ _SIGS = {
                                      C.c_double, C.c_double, _dp, C.c_int64, _i32p, C.c_int64,
                                      _i64p, _i64p]),
     "rs_surface_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "rs_surface_render_depth": (C.c_int, [C.c_void_p, _dp, C.c_int64, _i32p, C.c_int64, _dp,
+                                          C.c_int32, C.c_int64, C.c_int64, _fp]),
+    "rs_surface_colorize": (C.c_int, [C.c_void_p, _dp, C.c_int64, _i32p, C.c_int64, _u8p,
+                                      C.c_int32, _dp, C.c_int32, C.c_int64, C.c_int64, _dp,
+                                      C.c_double, C.c_double, _dp, _i32p, _fp]),
+    "rs_surface_texture_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
     "rs_np_shard_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.POINTER(C.c_void_p)]),
     "rs_np_shard_destroy": (C.c_int, [C.c_void_p]),

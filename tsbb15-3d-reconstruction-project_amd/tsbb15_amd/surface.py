@@ -9,7 +9,10 @@ has no such stage and nothing here restates code of it.
   * ``bounds``          origin and dims of a volume that encloses a cloud (host)
   * ``vertex_normals``  area-weighted normals (host)
   * ``save_ply`` / ``load_ply``   binary little-endian PLY (host)
-  * ``reconstruct``     ``dense.fuse`` -> ``integrate`` -> ``extract``
+  * ``reconstruct``     ``dense.fuse`` -> ``integrate`` -> ``extract`` (-> ``vertex_colors``)
+  * ``render_depth``    the mesh rendered into a z-buffer per view (rs_surface_render_depth,
+                        surface_texture.hip)
+  * ``vertex_colors``   a colour per vertex from the views that see it (rs_surface_colorize)
 
 Conventions are those of ``dense``: cameras are the project's normalised (3, 4) ``C``,
 ``P = K @ C``, pixel centres at integers, the depth of X in a view is ``C[2] @ [X; 1]`` and may
@@ -30,6 +33,9 @@ MAX_SIDE = 2048
 MAX_NODES = 1 << 27
 MAX_VIEWS = dense.MAX_VIEWS
 STAGES = ("integrate", "classify", "scan", "emit")
+TEXTURE_STAGES = ("raster_small", "raster_large", "gather")
+RASTER_SMALL = 32            # RS_SURFACE_RASTER_SMALL
+TEXTURE_LIST_CAP = 1 << 20   # RS_SURFACE_TEXTURE_LIST_CAP
 
 
 def _ctx(ctx):
@@ -287,19 +293,131 @@ def load_ply(path):
             "colors": cols(('red', 'green', 'blue'), np.uint8)}
 
 
+def _mesh(vertices, faces):
+    vertices = _ffi.f64c(vertices)
+    if vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError('vertices must be (Nv, 3)')
+    faces = np.asarray(faces)
+    if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype.kind not in 'iu':
+        raise ValueError('faces must be (Nf, 3) integers')
+    if len(vertices) > 2**31 - 1 or 3 * len(faces) > 2**31 - 1:
+        raise ValueError('nv and 3 nf must be at most 2^31 - 1')
+    if len(faces) and (faces.min() < 0 or faces.max() >= len(vertices)):
+        raise ValueError('a face index is out of range')
+    return vertices, np.ascontiguousarray(faces, dtype=np.int32)
+
+
+def _views(cams, K, h, w):
+    """P = K C of every view after the limits of ``dense.consistency``; the turn to positive
+    depths and the test of det P[:, :3] are the ABI's."""
+    K = dense._calibration(K)
+    cams = dense._cameras(cams, 'cams')
+    V = len(cams)
+    if not 1 <= V <= MAX_VIEWS:
+        raise ValueError('1 to 128 views')
+    if min(h, w) < 1 or max(h, w) > dense.MAX_SIDE or h * w > dense.MAX_PIXELS or \
+            V * h * w > dense.MAX_VOLUME:
+        raise ValueError('images of more than 2^26 pixels each or 2^28 in all')
+    return np.ascontiguousarray(K @ cams)
+
+
+def render_depth(vertices, faces, cams, K, shape, ctx=None):
+    """The z-buffers of a mesh (rs_surface_render_depth): (V, h, w) float32 for ``shape`` (h, w),
+    NaN where no face covers the pixel.  vertices (Nv, 3), faces (Nf, 3), cams (V, 3, 4).
+
+    Every camera is turned so that depths are positive, P = s K C with s = sign det(K C)[:, :3].
+    Per view and face, in fp64: q_i = P [X_i; 1]; the face is drawn iff q is finite and all three
+    z_i = q_i2 > 0 -- a face that crosses the camera plane is skipped, not clipped -- and its
+    projected area is neither 0 nor infinite.  Both windings are drawn.  A pixel centre (px, py)
+    of the bounding box is covered iff its three barycentric coordinates, each from its own edge
+    function, are >= 0; its depth is 1 / (b0 / z0 + b1 / z1 + b2 / z2) rounded to float32, and
+    the pixel keeps the smallest.  Bitwise reproducible, whatever the order of the faces.
+
+    ValueError before any launch: Nv or 3 Nf above 2^31 - 1, a face index out of range, V outside
+    1..128, the image limits of ``dense.consistency``, a camera that is not finite or has
+    det(K C)[:, :3] zero."""
+    vertices, faces = _mesh(vertices, faces)
+    try:
+        h, w = (int(n) for n in shape)
+    except (TypeError, ValueError):
+        raise ValueError('shape must be (h, w)') from None
+    P = _views(cams, K, h, w)
+    depth = np.empty((len(P), h, w), np.float32)
+    _ffi.check(_ffi.lib().rs_surface_render_depth(
+        _ctx(ctx), _ffi.ptr(vertices, _d), len(vertices), _ffi.ptr(faces, _i32), len(faces),
+        _ffi.ptr(P, _d), len(P), h, w, _ffi.ptr(depth, _f)))
+    return depth
+
+
+def vertex_colors(vertices, faces, images, cams, K, normals=None, rel_tol=0.01, min_cos=0.0,
+                  return_depth=False, ctx=None):
+    """A colour per mesh vertex from the views that see it (rs_surface_colorize).  images is
+    (V, h, w) or (V, h, w, 3) uint8, normals (Nv, 3) or None.
+
+    The z-buffers of ``render_depth`` are the occluder.  Per vertex and view, in index order and
+    fp64: the view is skipped unless the vertex lies in front and projects to (u, v) inside
+    [0, w - 1] x [0, h - 1].  It is visible iff its depth z <= far (1 + rel_tol), far the largest
+    finite z-buffer value among the four pixels of the bilinear footprint of (u, v).  With
+    normals the view contributes iff g = n . (c - X) / |c - X| > min_cos, c the camera centre,
+    with weight g; without them the weight is 1.  The colour is the weighted mean of the
+    bilinear samples, divided by 255.
+
+    Returns (colors (Nv, ch) float64 in [0, 1], count (Nv,) int32: the views that contributed;
+    the colour is 0 where it is 0), and the z-buffers (V, h, w) float32 as a third item when
+    ``return_depth`` is set.  Bitwise reproducible.
+
+    ValueError before any launch: what ``render_depth`` lists, images not uint8 of such a shape
+    or not one per camera, normals not (Nv, 3), rel_tol not finite or negative, min_cos not
+    finite."""
+    vertices, faces = _mesh(vertices, faces)
+    images = np.asarray(images)
+    if images.dtype != np.uint8 or images.ndim not in (3, 4) or \
+            (images.ndim == 4 and images.shape[3] != 3):
+        raise ValueError('images must be uint8 (V, h, w) or (V, h, w, 3)')
+    images = np.ascontiguousarray(images)
+    V, h, w = images.shape[:3]
+    ch = 1 if images.ndim == 3 else 3
+    P = _views(cams, K, h, w)
+    if len(P) != V:
+        raise ValueError('one image per camera')
+    if normals is not None:
+        normals = _ffi.f64c(normals)
+        if normals.shape != vertices.shape:
+            raise ValueError('normals must be (Nv, 3)')
+    rel_tol, min_cos = float(rel_tol), float(min_cos)
+    if not np.isfinite(rel_tol) or rel_tol < 0.0 or not np.isfinite(min_cos):
+        raise ValueError('rel_tol must be finite and not negative, min_cos finite')
+    nv = len(vertices)
+    colors, count = np.empty((nv, ch)), np.empty(nv, np.int32)
+    depth = np.empty((V, h, w), np.float32) if return_depth else None
+    _ffi.check(_ffi.lib().rs_surface_colorize(
+        _ctx(ctx), _ffi.ptr(vertices, _d), nv, _ffi.ptr(faces, _i32), len(faces),
+        _ffi.ptr(images, _ffi.C.c_uint8), ch, _ffi.ptr(P, _d), V, h, w,
+        _ffi.ptr(normals, _d) if normals is not None else None, rel_tol, min_cos,
+        _ffi.ptr(colors, _d), _ffi.ptr(count, _i32),
+        _ffi.ptr(depth, _f) if return_depth else None))
+    return (colors, count, depth) if return_depth else (colors, count)
+
+
 def reconstruct(images, cams, K, depths, origin, voxel, dims, trunc, min_weight=2, ctx=None,
-                **fuse_kw):
+                colors=False, **fuse_kw):
     """Posed images to a mesh: ``dense.fuse(..., return_maps=True)``, the depth set to NaN where
     ``keep`` is false, ``integrate`` with ``count`` as the weight, ``extract``.  ``fuse_kw`` goes
     to ``dense.fuse``: ``smooth=(p1, p2)`` there picks the depth maps' winners after semi-global
-    aggregation.  Returns (vertices, faces, tsdf, weight)."""
+    aggregation.  Returns (vertices, faces, tsdf, weight), and with ``colors=True``
+    (vertices, faces, tsdf, weight, colors): the first item of ``vertex_colors`` on the same
+    images, with the mesh's ``vertex_normals``."""
     fuse_kw.pop('return_maps', None)
     maps = dense.fuse(images, cams, K, depths, return_maps=True, ctx=ctx, **fuse_kw)[-1]
     depth = np.where(maps["keep"], maps["depth"], np.nan)
     tsdf, weight = integrate(depth, cams, K, origin, voxel, dims, trunc,
                              weights=maps["count"].astype(np.float32), ctx=ctx)
     vertices, faces = extract(tsdf, weight, origin, voxel, min_weight=min_weight, ctx=ctx)
-    return vertices, faces, tsdf, weight
+    if not colors:
+        return vertices, faces, tsdf, weight
+    col = vertex_colors(vertices, faces, images, cams, K,
+                        normals=vertex_normals(vertices, faces), ctx=ctx)[0]
+    return vertices, faces, tsdf, weight, col
 
 
 def timing(enable, ctx=None):
@@ -310,3 +428,13 @@ def timing(enable, ctx=None):
     ms = np.zeros(len(STAGES))
     _ffi.check(_ffi.lib().rs_surface_timing(ctx.handle, int(enable), _ffi.ptr(ms, _d)))
     return dict(zip(STAGES, ms.tolist()))
+
+
+def texture_timing(enable, ctx=None):
+    """The same for the next ``render_depth`` and ``vertex_colors`` calls
+    (rs_surface_texture_timing): {raster_small, raster_large, gather: device ms}, -1 where none.
+    ``timing`` does not see these calls."""
+    ctx = ctx or _ffi.default_context()
+    ms = np.zeros(len(TEXTURE_STAGES))
+    _ffi.check(_ffi.lib().rs_surface_texture_timing(ctx.handle, int(enable), _ffi.ptr(ms, _d)))
+    return dict(zip(TEXTURE_STAGES, ms.tolist()))
