@@ -1097,6 +1097,87 @@ int rs_surface_colorize(rs_ctx *ctx, const double *vertices, int64_t nv, const i
 int rs_surface_texture_timing(rs_ctx *ctx, int32_t enable, double *ms);
 
 /* ------------------------------------------------------------------------------------------
+ * The evaluation stage (eval.hip): the exact distance from many points to a triangle mesh, the
+ * operation under the accuracy and completeness measures of tsbb15_amd.evaluation.  The
+ * reference's evaluation.py loads the true cameras and stops; nothing here restates code of it.
+ * All fp64, one lane per query, integer atomics only.  The result of a query is a minimum over
+ * the pair (bits of d2, face index), which no visiting order can change: it depends neither on
+ * the grid, nor on `cell`, nor on the arrival order of an atomic, and two calls give the same
+ * bits.
+ * ------------------------------------------------------------------------------------------ */
+#define RS_EVAL_MAX_POINTS (1LL << 28)  /* queries of one call                               */
+#define RS_EVAL_MAX_CELLS (1LL << 24)   /* cells of the grid, all three axes multiplied       */
+#define RS_EVAL_MAX_ENTRIES (1LL << 27) /* face-cell registrations                            */
+
+typedef struct rs_eval_info {
+  int64_t cells[3];       /* grid dimensions along x, y, z                                  */
+  int64_t entries;        /* face-cell registrations                                        */
+  int64_t largest_cell;   /* registrations in the fullest cell                              */
+  int64_t tests;          /* point-triangle tests run                                       */
+  int64_t faces_skipped;  /* invalid faces                                                  */
+  int64_t beyond;         /* queries answered +inf                                          */
+} rs_eval_info;           /* 64 bytes */
+
+/* pts is (n, 3), vertices (nv, 3), faces (nf, 3) int32; max_dist > 0 (+inf allowed), cell > 0
+ * and finite.  d2 is (n), face (n) int32, closest (n, 3).
+ *   A face (a, b, c) is invalid, skipped and counted in info.faces_skipped, when one of its nine
+ *   coordinates is not finite or when, with ab = b - a and ac = c - a, the three components
+ *   ab1 ac2 - ab2 ac1, ab2 ac0 - ab0 ac2, ab0 ac1 - ab1 ac0 are all exactly zero (no area; a
+ *   repeated index).
+ *   The closest point of a valid face to p is Ericson's ClosestPtPointTriangle, by Voronoi region
+ *   of the triangle, the vertices first, then the edges, then the interior.  No product is fused
+ *   with a sum, every dot product is x x' + y y' + z z' summed left to right, and the first rule
+ *   that holds decides:
+ *     ab = b - a, ac = c - a, ap = p - a, d1 = ab.ap, d2 = ac.ap
+ *     bp = p - b, d3 = ab.bp, d4 = ac.bp;  cp = p - c, d5 = ab.cp, d6 = ac.cp
+ *     d1 <= 0 and d2 <= 0                       ->  q = a
+ *     d3 >= 0 and d4 <= d3                      ->  q = b
+ *     d6 >= 0 and d5 <= d6                      ->  q = c
+ *     vc = d1 d4 - d3 d2;  vc <= 0, d1 >= 0, d3 <= 0
+ *                                               ->  q = a + (d1 / (d1 - d3)) ab
+ *     vb = d5 d2 - d1 d6;  vb <= 0, d2 >= 0, d6 <= 0
+ *                                               ->  q = a + (d2 / (d2 - d6)) ac
+ *     va = d3 d6 - d5 d4;  va <= 0, d4 - d3 >= 0, d5 - d6 >= 0
+ *                                               ->  q = b + ((d4 - d3) / ((d4 - d3) + (d5 - d6))) (c - b)
+ *     otherwise, s = (va + vb) + vc             ->  q = (a + (vb / s) ab) + (vc / s) ac
+ *   q = x + t u stands for x_k + t u_k per coordinate.  The face's squared distance is
+ *   e.e with e = p - q.  A face whose squared distance is NaN (possible only where a sliver's
+ *   s rounds to zero, or on overflow) never wins.
+ *   d2[i] is the minimum over the valid faces, face[i] the lowest index among the faces whose
+ *   squared distance is bit-equal to it, closest[i] that face's q.  When no face wins, or when
+ *   d2[i] > max_dist max_dist (the fp64 product): d2 = +inf, face = -1, closest = NaN; such
+ *   queries are counted in info.beyond.  A query with a coordinate that is not finite gets
+ *   d2 = NaN, face = -1, closest = NaN.  nf = 0 or no valid face: every finite query gets +inf.
+ * The search is a dense uniform grid of side `cell` from the minimum corner `lo` of the box of
+ * the faces with finite coordinates: floor((hi - lo) / cell) + 1 cells per axis.  A valid face
+ * is registered in every cell its own box overlaps (count with an integer atomicAdd per cell,
+ * exclusive scan, scatter through an integer atomic cursor; the order inside a cell is the
+ * arrival order and cannot matter).  A query takes its integer cell coordinate
+ * floor((p - lo) / cell), which may lie outside the grid, and walks the Chebyshev rings r = r0,
+ * r0 + 1, ... around it, each clipped to the grid, r0 the first that meets the grid.  Before
+ * ring r >= 1 it stops when the best squared distance is <= B^2, B = (r - 1) cell (1 - 2^-20),
+ * or when B > max_dist: a face not yet seen is registered only in cells of ring >= r, so its box
+ * and the face lie at least (r - 1) cell away; the factor covers the rounding of the cell
+ * coordinates.  It also stops when the ring has left the grid on every side.  `tests` counts a
+ * face once per cell in which a query meets it.
+ * RS_EINVAL before any launch: n, nv or nf negative, n > RS_EVAL_MAX_POINTS, nv or 3 nf above
+ * 2^31 - 1, a face index outside 0..nv - 1, max_dist not > 0, cell not finite or not > 0, a box
+ * whose extent is not finite, cell < 2^-24 of the box's largest coordinate magnitude (the ring
+ * bound needs the squared distances accurate to 2^-20), more than RS_EVAL_MAX_CELLS cells or
+ * more than RS_EVAL_MAX_ENTRIES registrations (the message names the cap and says "choose a
+ * larger cell").  n = 0 returns at once. */
+int rs_eval_mesh_distance(rs_ctx *ctx, const double *pts, int64_t n, const double *vertices,
+                          int64_t nv, const int32_t *faces, int64_t nf, double max_dist,
+                          double cell, double *d2, int32_t *face, double *closest,
+                          rs_eval_info *info);
+
+/* HIP events between the stages of the next rs_eval_mesh_distance calls (enable != 0).  Returns
+ * the last timed call's device ms: slot 0 bin (validity, triangle packing, count per cell), 1
+ * scan, 2 scatter, 3 query; -1 where none (tools/bench_eval.py). */
+#define RS_EVAL_TIMING_SLOTS 4
+int rs_eval_timing(rs_ctx *ctx, int32_t enable, double *ms);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU (RCCL over xGMI).  One process per GPU; the unique id travels out of band.
  * ---------------------------------------------------------------------------------------- */
 #define RS_COMM_ID_BYTES 128

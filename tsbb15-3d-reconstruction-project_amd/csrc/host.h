@@ -125,6 +125,9 @@ struct rs_ctx {
   // rs_surface_texture_timing: around the kernels of the next mesh-colouring calls
   // (surface_texture.hip): raster_small, raster_large, gather
   rs::StageTimer<4, RS_SURFACE_TEXTURE_TIMING_SLOTS> texture{-1.0};
+  // rs_eval_timing: between the stages of the next mesh-distance calls (eval.hip): bin, scan,
+  // scatter, query
+  rs::StageTimer<5, RS_EVAL_TIMING_SLOTS> eval{-1.0};
 };
 
 namespace rs {

@@ -82,10 +82,16 @@ class CloudInfo(C.Structure):
                 ("rows_not_ok", C.c_int64)]
 
 
+class EvalInfo(C.Structure):
+    _fields_ = [("cells", C.c_int64 * 3), ("entries", C.c_int64), ("largest_cell", C.c_int64),
+                ("tests", C.c_int64), ("faces_skipped", C.c_int64), ("beyond", C.c_int64)]
+
+
 BA_MAX_CAMERAS = 128
 WASH_MAX_TRACK = 128
 CLOUD_MAX_CELLS = 1 << 21
 CLOUD_STAGES = ("grid", "scan", "sort", "normals", "attributes")
+EVAL_STAGES = ("bin", "scan", "scatter", "query")
 BA_LOSSES = ("linear", "soft_l1", "huber", "cauchy")   # RS_BA_LOSS_*: the index is the code
 BA_KERNELS = ("k_ba_linearize", "k_ba_camera", "k_ba_pointsum", "k_ba_point", "k_ba_schur",
               "k_ba_chol", "k_ba_step", "k_ba_cost+final")
@@ -237,6 +243,10 @@ _SIGS = {
                                       C.c_int32, _dp, C.c_int32, C.c_int64, C.c_int64, _dp,
                                       C.c_double, C.c_double, _dp, _i32p, _fp]),
     "rs_surface_texture_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "rs_eval_mesh_distance": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _i32p,
+                                        C.c_int64, C.c_double, C.c_double, _dp, _i32p, _dp,
+                                        C.POINTER(EvalInfo)]),
+    "rs_eval_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
     "rs_np_shard_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.POINTER(C.c_void_p)]),
     "rs_np_shard_destroy": (C.c_int, [C.c_void_p]),

@@ -1,0 +1,293 @@
+"""The evaluation stage: how good a mesh is, and how good the cameras are.
+
+The reference names this step (evaluation.py loads the true cameras of imgdata/dino_Ps.mat, prints
+them and stops; main.py:180-181 saves R_eval_clean / t_eval_clean for it).  The measures are those
+of the multi-view-stereo benchmark the Dino comes from (Seitz et al. 2006):
+
+  * accuracy      the distance d such that a given fraction of the reconstruction lies within d
+                  of the truth
+  * completeness  the fraction of the truth that lies within a given distance of the
+                  reconstruction
+
+Both rest on ``mesh_distance``, the exact distance from many points to a triangle mesh (HIP kernels
+of eval.hip; the contract stands in include/rsamd.h).  Everything about the cameras -- tens of
+them -- is host numpy: ``decompose_projection``, ``align_similarity``, ``camera_errors``.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _ffi
+
+_d = _ffi.C.c_double
+_i32 = _ffi.C.c_int32
+
+MAX_POINTS = 1 << 28    # RS_EVAL_MAX_POINTS
+MAX_CELLS = 1 << 24     # RS_EVAL_MAX_CELLS
+MAX_ENTRIES = 1 << 27   # RS_EVAL_MAX_ENTRIES
+STAGES = _ffi.EVAL_STAGES
+
+
+def _ctx(ctx):
+    return (ctx or _ffi.default_context()).handle
+
+
+def _points(a, name):
+    a = _ffi.f64c(a)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError(f'{name} must be (n, 3)')
+    return a
+
+
+def _faces(faces, nv):
+    f = np.asarray(faces)
+    if f.size and not np.issubdtype(f.dtype, np.integer):
+        raise ValueError('faces must hold integers')
+    f = f.reshape(-1, 3) if f.size == 0 else f
+    if f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError('faces must be (nf, 3)')
+    if f.size and (f.min() < 0 or f.max() >= nv):
+        raise ValueError('a face index is out of range')
+    return np.ascontiguousarray(f, dtype=np.int32)
+
+
+def default_cell(vertices, faces):
+    """max(2 x the median diagonal of the faces' boxes, the mesh box's largest extent / 512), over
+    the faces whose coordinates are finite; 1 for a mesh without one or without any extent.  Never
+    below 2^-23 of the largest coordinate magnitude (rs_eval_mesh_distance refuses 2^-24)."""
+    tri = vertices[faces]
+    tri = tri[np.isfinite(tri).all(axis=(1, 2))]
+    if len(tri) == 0:
+        return 1.0
+    lo, hi = tri.min(axis=1), tri.max(axis=1)
+    diag = np.sqrt(((hi - lo) ** 2).sum(axis=1))
+    cell = max(2.0 * float(np.median(diag)), float((hi.max(axis=0) - lo.min(axis=0)).max()) / 512.0,
+               float(np.abs(tri).max()) / (1 << 23))
+    return cell if np.isfinite(cell) and cell > 0.0 else 1.0
+
+
+def mesh_distance(points, vertices, faces, max_dist=np.inf, cell=None, ctx=None):
+    """The distance from every point to a triangle mesh (rs_eval_mesh_distance).
+
+    points (n, 3), vertices (nv, 3), faces (nf, 3) integers.  Returns (dist, face, closest, info):
+    dist (n) the distance to the closest point of the mesh, face (n) int32 the lowest-numbered
+    face that attains it, closest (n, 3) that point.  A point farther than ``max_dist`` (+inf
+    allowed) from every face, or a mesh without a valid face, gives dist = +inf, face = -1,
+    closest = NaN; a point with a coordinate that is not finite gives dist = NaN, face = -1.  A
+    face with a coordinate that is not finite or without area is skipped.
+
+    ``cell`` is the side of the search grid, ``default_cell`` when None; the result does not
+    depend on it, the time does.  info = dict(d2, cell, cells, entries, largest_cell, tests,
+    faces_skipped, beyond), d2 (n) the squared distances as the kernel made them.  n == 0 returns
+    empty arrays without a launch.  ValueError: bad shapes, an index out of range, max_dist not
+    > 0, cell not finite or not > 0, or a cell so small that the grid passes MAX_CELLS cells or
+    MAX_ENTRIES registrations."""
+    points, vertices = _points(points, 'points'), _points(vertices, 'vertices')
+    faces = _faces(faces, len(vertices))
+    max_dist = float(max_dist)
+    if not max_dist > 0.0:
+        raise ValueError('max_dist must be positive (+inf is allowed)')
+    cell = default_cell(vertices, faces) if cell is None else float(cell)
+    if not np.isfinite(cell) or not cell > 0.0:
+        raise ValueError('cell must be finite and positive')
+    n = len(points)
+    d2, face, closest = np.empty(n), np.full(n, -1, dtype=np.int32), np.empty((n, 3))
+    info = _ffi.EvalInfo()
+    if n > 0:
+        _ffi.check(_ffi.lib().rs_eval_mesh_distance(
+            _ctx(ctx), _ffi.ptr(points, _d), n, _ffi.ptr(vertices, _d), len(vertices),
+            _ffi.ptr(faces, _i32), len(faces), max_dist, cell, _ffi.ptr(d2, _d),
+            _ffi.ptr(face, _i32), _ffi.ptr(closest, _d), _ffi.C.byref(info)))
+    return np.sqrt(d2), face, closest, {
+        "d2": d2, "cell": cell, "cells": tuple(info.cells), "entries": info.entries,
+        "largest_cell": info.largest_cell, "tests": info.tests,
+        "faces_skipped": info.faces_skipped, "beyond": info.beyond}
+
+
+def timing(enable, ctx=None):
+    """Enable / disable HIP events between the stages of the next mesh_distance calls
+    (rs_eval_timing); returns the last timed call's {stage: device ms}, -1 where none."""
+    ctx = ctx or _ffi.default_context()
+    ms = np.zeros(len(STAGES))
+    _ffi.check(_ffi.lib().rs_eval_timing(ctx.handle, int(enable), _ffi.ptr(ms, _d)))
+    return dict(zip(STAGES, ms.tolist()))
+
+
+def sample_surface(vertices, faces, n, seed=0):
+    """n points on the mesh, drawn uniformly by area with np.random.RandomState(seed) (host only).
+
+    Returns (points (n, 3), face (n) int64).  One draw of n uniforms picks the faces by the
+    running sum of the areas, a second and third give the place inside: with s = sqrt(r1) the
+    point is (1 - s) a + s (1 - r2) b + s r2 c.  A face without area or with a coordinate that is
+    not finite is never drawn.  ValueError for a mesh without area when n > 0."""
+    vertices = _points(vertices, 'vertices')
+    faces = _faces(faces, len(vertices))
+    n = int(n)
+    if n < 0:
+        raise ValueError('n must not be negative')
+    rs = np.random.RandomState(seed)
+    tri = vertices[faces]
+    with np.errstate(invalid='ignore', over='ignore'):
+        cr = np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
+        area = 0.5 * np.sqrt((cr * cr).sum(axis=1))
+    area[~np.isfinite(area)] = 0.0
+    if n == 0:
+        return np.empty((0, 3)), np.empty(0, dtype=np.int64)
+    if not area.sum() > 0.0:
+        raise ValueError('the mesh has no area to sample')
+    cum = np.cumsum(area)
+    u, r1, r2 = rs.uniform(size=n), rs.uniform(size=n), rs.uniform(size=n)
+    # the first face whose running sum passes the draw: a face without area never is
+    f = np.searchsorted(cum, u * cum[-1], side='right')
+    f = np.minimum(f, int(np.flatnonzero(area > 0.0)[-1]))
+    s = np.sqrt(r1)
+    w = np.stack([1.0 - s, s * (1.0 - r2), s * r2], axis=1)
+    return (w[:, :, None] * tri[f]).sum(axis=1), f.astype(np.int64)
+
+
+def _distances(dist):
+    dist = np.asarray(dist, dtype=np.float64).reshape(-1)
+    if len(dist) == 0:
+        raise ValueError('no distances')
+    return dist
+
+
+def accuracy(dist, fraction=0.9):
+    """The distance within which ``fraction`` of the points lie: the ceil(fraction n)-th smallest
+    value (fraction n is rounded to 9 decimals first, so that 0.7 x 10 counts as 7).  +inf counts
+    as +inf.  ValueError for a NaN, an empty array or a fraction outside (0, 1]."""
+    dist = _distances(dist)
+    if np.isnan(dist).any():
+        raise ValueError('a distance is NaN (a point with a coordinate that is not finite)')
+    if not 0.0 < fraction <= 1.0:
+        raise ValueError('fraction must be in (0, 1]')
+    k = max(int(np.ceil(np.round(fraction * len(dist), 9))), 1)
+    return float(np.partition(dist, k - 1)[k - 1])
+
+
+def completeness(dist, threshold):
+    """The share of the points within ``threshold``: mean(dist <= threshold)."""
+    return float((_distances(dist) <= threshold).mean())
+
+
+def compare_meshes(rec_v, rec_f, gt_v, gt_f, fraction=0.9, threshold=None, max_dist=np.inf,
+                   samples=None, seed=0, ctx=None):
+    """Accuracy and completeness of a reconstruction against the truth, both through
+    mesh_distance: the reconstruction's points against the true mesh, and the truth's points
+    against the reconstructed one.  The points are the meshes' vertices, or with ``samples`` that
+    many surface samples of each (sample_surface, seeds ``seed`` and ``seed + 1``).  ``threshold``
+    is completeness' distance, by default 1 % of the diagonal of the truth's box.
+
+    Returns dict(accuracy, completeness, fraction, threshold, dist_rec, dist_gt, info_rec,
+    info_gt)."""
+    rec_v, gt_v = _points(rec_v, 'rec_v'), _points(gt_v, 'gt_v')
+    rec_f, gt_f = _faces(rec_f, len(rec_v)), _faces(gt_f, len(gt_v))
+    if threshold is None:
+        finite = gt_v[np.isfinite(gt_v).all(axis=1)]
+        if len(finite) == 0:
+            raise ValueError('the truth has no finite vertex to take a threshold from')
+        threshold = 0.01 * float(np.sqrt(((finite.max(axis=0) - finite.min(axis=0)) ** 2).sum()))
+    if samples is None:
+        rec_p, gt_p = rec_v, gt_v
+    else:
+        rec_p = sample_surface(rec_v, rec_f, samples, seed)[0]
+        gt_p = sample_surface(gt_v, gt_f, samples, seed + 1)[0]
+    dist_rec, _, _, info_rec = mesh_distance(rec_p, gt_v, gt_f, max_dist=max_dist, ctx=ctx)
+    dist_gt, _, _, info_gt = mesh_distance(gt_p, rec_v, rec_f, max_dist=max_dist, ctx=ctx)
+    return {"accuracy": accuracy(dist_rec, fraction),
+            "completeness": completeness(dist_gt, threshold), "fraction": fraction,
+            "threshold": threshold, "dist_rec": dist_rec, "dist_gt": dist_gt,
+            "info_rec": info_rec, "info_gt": info_gt}
+
+
+# ---- cameras (host only) ---------------------------------------------------------------------
+
+def nearest_rotation(M):
+    """The rotation closest to M (..., 3, 3) in the Frobenius norm: U diag(1, 1, det(U V^T)) V^T."""
+    U, _, Vt = np.linalg.svd(np.asarray(M, dtype=np.float64))
+    D = np.ones(U.shape[:-2] + (3,))
+    D[..., 2] = np.sign(np.linalg.det(U @ Vt))
+    return (U * D[..., None, :]) @ Vt
+
+
+def decompose_projection(P):
+    """K, R, t of P ~ K [R | t] by an RQ decomposition of P[:, :3]: K upper triangular with a
+    positive diagonal and K[2, 2] = 1, det R = +1.  P is (3, 4) or (n, 3, 4); the overall scale
+    and sign of P do not matter.  ValueError for another shape or a singular P[:, :3]."""
+    P = np.asarray(P, dtype=np.float64)
+    if P.shape[-2:] != (3, 4) or P.ndim not in (2, 3):
+        raise ValueError('P must be (3, 4) or (n, 3, 4)')
+    if P.ndim == 3:
+        parts = [decompose_projection(p) for p in P]
+        return tuple(np.array([q[k] for q in parts]).reshape((len(P),) + s)
+                     for k, s in enumerate(((3, 3), (3, 3), (3,))))
+    det = np.linalg.det(P[:, :3])
+    if not np.isfinite(det) or det == 0.0:
+        raise ValueError('P[:, :3] is singular or not finite')
+    P = P if det > 0.0 else -P
+    # M = K R from the QR of the reversed matrix: (J M)^T = Q U  =>  M = (J U^T J)(J Q^T)
+    Q, U = np.linalg.qr(P[::-1, :3].T)
+    K, R = U.T[::-1, ::-1], Q.T[::-1]
+    sign = np.where(np.diag(K) < 0.0, -1.0, 1.0)
+    K, R = K * sign, sign[:, None] * R     # det R = +1: det K > 0 and det M > 0
+    t = np.linalg.solve(K, P[:, 3])
+    return K / K[2, 2], R, t
+
+
+def align_similarity(src, dst, with_scale=True):
+    """Umeyama's alignment: (s, R, t) minimising sum |dst_i - (s R src_i + t)|^2 with R a rotation
+    (det +1 also where the best orthogonal map is a reflection) and s = 1 without ``with_scale``.
+    src and dst are (n, 3)."""
+    src, dst = _points(src, 'src'), _points(dst, 'dst')
+    if src.shape != dst.shape or len(src) == 0:
+        raise ValueError('src and dst must be (n, 3) with the same n > 0')
+    ms, md = src.mean(axis=0), dst.mean(axis=0)
+    xs, xd = src - ms, dst - md
+    U, D, Vt = np.linalg.svd(xd.T @ xs / len(src))
+    S = np.array([1.0, 1.0, 1.0 if np.linalg.det(U) * np.linalg.det(Vt) >= 0.0 else -1.0])
+    R = (U * S) @ Vt
+    var = (xs * xs).sum() / len(src)
+    s = float((D * S).sum() / var) if with_scale and var > 0.0 else 1.0
+    return s, R, md - s * R @ ms
+
+
+def apply_similarity(points, s, R, t):
+    """s R p + t for every row p of points."""
+    return s * np.asarray(points, dtype=np.float64) @ np.asarray(R).T + np.asarray(t)
+
+
+def camera_errors(R_est, t_est, R_gt, t_gt, frame=True):
+    """Estimated cameras against true ones, x_cam = R X + t each, in the arrays of
+    tables.getCamerasForEvaluation: R (n, 3, 3), t (n, 3) or (n, 3, 1).
+
+      1. every estimated R is replaced by its nearest rotation; the largest |R R^T - I| before
+         that is ``orthogonality_defect`` (a 12-parameter adjustment leaves R not orthogonal).
+         The centres are -R^T t with R as given: the centre the pipeline itself works with
+         (tables.py:189-214, rs_cloud_attributes), which is what it is to be charged for.
+      2. the estimated centres are aligned to the true ones by align_similarity: (s, R, t).
+      3. with ``frame``, one constant rotation of the camera frame F is estimated, the nearest
+         rotation to sum_i R_gt,i (R_est,i R^T)^T, and divided out: a resectioning that fixes the
+         cameras only up to such a gauge is not charged for it.  Without it F is the identity.
+
+    Returns dict(s, R, t, frame, centre_error (n), rotation_error_deg (n), orthogonality_defect):
+    centre_error_i = |s R c_est,i + t - c_gt,i|, rotation_error_deg_i the angle of
+    R_gt,i (F R_est,i R^T)^T."""
+    R_est, R_gt = (np.asarray(a, dtype=np.float64).reshape(-1, 3, 3) for a in (R_est, R_gt))
+    t_est, t_gt = (np.asarray(a, dtype=np.float64).reshape(-1, 3) for a in (t_est, t_gt))
+    n = len(R_est)
+    if n == 0 or not (len(t_est) == len(R_gt) == len(t_gt) == n):
+        raise ValueError('one R and one t per camera, the same number estimated and true, n > 0')
+    eye = np.eye(3)
+    defect = float(np.abs(R_est @ R_est.transpose(0, 2, 1) - eye).max())
+    c_est = -np.einsum('nji,nj->ni', R_est, t_est)
+    R_est = nearest_rotation(R_est)
+    c_gt = -np.einsum('nji,nj->ni', R_gt, t_gt)
+    s, Ra, ta = align_similarity(c_est, c_gt)
+    moved = R_est @ Ra.T
+    F = nearest_rotation((R_gt @ moved.transpose(0, 2, 1)).sum(axis=0)) if frame else eye
+    E = R_gt @ (F @ moved).transpose(0, 2, 1)
+    cos = np.clip((np.trace(E, axis1=1, axis2=2) - 1.0) / 2.0, -1.0, 1.0)
+    return {"s": s, "R": Ra, "t": ta, "frame": F,
+            "centre_error": np.linalg.norm(apply_similarity(c_est, s, Ra, ta) - c_gt, axis=1),
+            "rotation_error_deg": np.degrees(np.arccos(cos)),
+            "orthogonality_defect": defect}
