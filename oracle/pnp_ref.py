@@ -114,6 +114,41 @@ def ransac_pnp(y_med, X_med, y_high, X_high, r, thresh, n=6, rng=None, trace=Fal
     return R_best, t_best, inl_med, inl_high, best, counts
 
 
+class _PrefixRng:
+    """An ``rng`` whose ``shuffle`` writes the next given tuple as the list's prefix (the rest
+    stays a permutation), so the loops of ransac_pnp / ransac_pnp_p3p run on chosen samples."""
+
+    def __init__(self, tuples):
+        self._it = iter(tuples)
+
+    def shuffle(self, idx):
+        T = [int(v) for v in next(self._it)]
+        rest = sorted(set(idx) - set(T))
+        idx[:] = T + rest
+
+
+def ransac_pnp_tuples(y_med, X_med, y_high, X_high, tuples, thresh):
+    """The loop of ``ransac_pnp`` with the samples given: ``tuples`` (H, n) indices into D_high.
+    Equal tuples are solved and scored once (a planted-winner test repeats one contaminated
+    tuple tens of thousands of times).  Returns ``(R, t, inl_med, inl_high, best_index, counts)``
+    with the per-trial D_med counts always."""
+    tuples = np.asarray(tuples)
+    uniq, inverse = np.unique(tuples, axis=0, return_inverse=True)
+    poses, c_u = [], np.zeros(len(uniq), dtype=np.int64)
+    for j, T in enumerate(uniq):
+        R, t = pnp_dlt(X_high[T], y_high[T])
+        poses.append((R, t))
+        c_u[j] = int(np.count_nonzero(thresh >= pose_errors(R, t, X_med, y_med)))
+    counts = c_u[np.ravel(inverse)]
+    best = int(np.argmax(counts))               # first occurrence of the largest count
+    if counts[best] <= 0:                       # strict ">" against the initial best size 0
+        return None, None, None, None, -1, counts
+    R_best, t_best = poses[int(np.ravel(inverse)[best])]
+    inl_med = np.flatnonzero(thresh >= pose_errors(R_best, t_best, X_med, y_med))
+    inl_high = np.flatnonzero(thresh >= pose_errors(R_best, t_best, X_high, y_high))
+    return R_best, t_best, inl_med, inl_high, best, counts
+
+
 # ------------------------------------------------------------------------------------------
 # n = 3: the p3p branch of ransac_robust (ransac.py:81-82, 91-111)
 # ------------------------------------------------------------------------------------------
@@ -123,17 +158,34 @@ def ransac_pnp(y_med, X_med, y_high, X_high, r, thresh, n=6, rng=None, trace=Fal
 # pnp_minimal.h p3p_lambda_twist computes it, so the GPU kernel is checked against an
 # independent CPU evaluation of the same algorithm, solution order included.
 
-def _cubic_roots(c3, c2, c1, c0):
+class NumpyOps:
+    """The arithmetic p3p_lambda_twist and p3p_pose4 run on: numpy's float64 here; the golden
+    generator (tests/golden/make_golden_pnp_minimal.py) passes the same operations in mpmath
+    to measure this restatement's own rounding error."""
+    pi = np.pi
+    sqrt = staticmethod(np.sqrt)
+    arccos = staticmethod(np.arccos)
+    cos = staticmethod(np.cos)
+    cbrt = staticmethod(np.cbrt)
+    copysign = staticmethod(np.copysign)
+    det = staticmethod(np.linalg.det)
+    solve = staticmethod(np.linalg.solve)
+    inv = staticmethod(np.linalg.inv)
+    zeros = staticmethod(np.zeros)
+    eye = staticmethod(np.eye)
+
+
+def _cubic_roots(c3, c2, c1, c0, ops=NumpyOps):
     a, b, c = c2 / c3, c1 / c3, c0 / c3
     q = (a * a - 3.0 * b) / 9.0
     r = (2.0 * a * a * a - 9.0 * a * b + 27.0 * c) / 54.0
     if r * r < q * q * q:
-        th = np.arccos(min(1.0, max(-1.0, r / np.sqrt(q * q * q))))
-        sq = -2.0 * np.sqrt(q)
-        x = [sq * np.cos(th / 3.0) - a / 3.0, sq * np.cos((th + 2.0 * np.pi) / 3.0) - a / 3.0,
-             sq * np.cos((th - 2.0 * np.pi) / 3.0) - a / 3.0]
+        th = ops.arccos(min(1.0, max(-1.0, r / ops.sqrt(q * q * q))))
+        sq = -2.0 * ops.sqrt(q)
+        x = [sq * ops.cos(th / 3.0) - a / 3.0, sq * ops.cos((th + 2.0 * ops.pi) / 3.0) - a / 3.0,
+             sq * ops.cos((th - 2.0 * ops.pi) / 3.0) - a / 3.0]
     else:
-        A = -np.copysign(np.cbrt(abs(r) + np.sqrt(r * r - q * q * q)), r)
+        A = -ops.copysign(ops.cbrt(abs(r) + ops.sqrt(r * r - q * q * q)), r)
         B = q / A if A != 0.0 else 0.0
         x = [(A + B) - a / 3.0]
     for i in range(len(x)):
@@ -145,21 +197,24 @@ def _cubic_roots(c3, c2, c1, c0):
     return x
 
 
-def _null3(A):
+def _null3(A, ops=NumpyOps):
     A = A.reshape(3, 3)
     c = [np.cross(A[0], A[1]), np.cross(A[0], A[2]), np.cross(A[1], A[2])]
-    d = [float(v @ v) for v in c]
-    k = int(np.argmax(d))   # first of equal maxima, as the kernel's strict ">"
-    return c[k] / np.sqrt(d[k]) if d[k] > 0.0 else c[k] * 0.0
+    d = [v @ v for v in c]
+    k = 0                   # first of equal maxima, as the kernel's strict ">"
+    for i in (1, 2):
+        if d[i] > d[k]:
+            k = i
+    return c[k] / ops.sqrt(d[k]) if d[k] > 0.0 else c[k] * 0.0
 
 
-def p3p_lambda_twist(X, y):
+def p3p_lambda_twist(X, y, ops=NumpyOps):
     """Poses (R, t, mirrored) from three world points X (3,3) and unit bearings y (3,3): up to
     four front-facing solutions, each followed by its mirrored-depth twin."""
     b01, b02, b12 = y[0] @ y[1], y[0] @ y[2], y[1] @ y[2]
-    a01 = float((X[0] - X[1]) @ (X[0] - X[1]))
-    a02 = float((X[0] - X[2]) @ (X[0] - X[2]))
-    a12 = float((X[1] - X[2]) @ (X[1] - X[2]))
+    a01 = (X[0] - X[1]) @ (X[0] - X[1])
+    a02 = (X[0] - X[2]) @ (X[0] - X[2])
+    a12 = (X[1] - X[2]) @ (X[1] - X[2])
     D1 = np.array([[a12, -a12 * b01, 0.0], [-a12 * b01, a12 - a01, a01 * b12], [0.0, a01 * b12, -a01]])
     D2 = np.array([[a12, 0.0, -a12 * b02], [0.0, -a02, a02 * b12], [-a12 * b02, a02 * b12, a12 - a02]])
     A0, A1, A2 = D1[:, 0], D1[:, 1], D1[:, 2]
@@ -173,20 +228,20 @@ def p3p_lambda_twist(X, y):
     a = np.array([[0.0, a01, a02], [a01, 0.0, a12], [a02, a12, 0.0]])
     bb = np.array([[1.0, b01, b02], [b01, 1.0, b12], [b02, b12, 1.0]])
     out = []
-    for g in _cubic_roots(c3, c2, c1, c0):
+    for g in _cubic_roots(c3, c2, c1, c0, ops):
         D0 = D1 + g * D2
         T = D0[0, 0] + D0[1, 1] + D0[2, 2]
         P = ((D0[0, 0] * D0[1, 1] - D0[0, 1] ** 2) + (D0[0, 0] * D0[2, 2] - D0[0, 2] ** 2)
              + (D0[1, 1] * D0[2, 2] - D0[1, 2] ** 2))
         if not P < 0.0:
             continue
-        sq = np.sqrt(T * T - 4.0 * P)
+        sq = ops.sqrt(T * T - 4.0 * P)
         s0 = 0.5 * (T + sq) if T >= 0.0 else 0.5 * (T - sq)
         s1 = P / s0
-        e0 = _null3(D0 - s0 * np.eye(3))
-        e1 = _null3(D0 - s1 * np.eye(3))
+        e0 = _null3(D0 - s0 * ops.eye(3), ops)
+        e1 = _null3(D0 - s1 * ops.eye(3), ops)
         for sg in range(2):
-            tt = (-1.0 if sg else 1.0) * np.sqrt(-s0 / s1)
+            tt = (-1.0 if sg else 1.0) * ops.sqrt(-s0 / s1)
             nv = e1 - tt * e0
             k = 0
             if abs(nv[1]) > abs(nv[k]):
@@ -202,7 +257,7 @@ def p3p_lambda_twist(X, y):
             disc = q1 * q1 - 4.0 * q2 * q0
             if not disc >= 0.0 or q2 == 0.0:
                 continue
-            sd = np.sqrt(disc)
+            sd = ops.sqrt(disc)
             for rt in range(2):
                 if len(out) >= 8:
                     break
@@ -212,8 +267,8 @@ def p3p_lambda_twist(X, y):
                 den = tau * tau - 2.0 * bq * tau + 1.0
                 if not den > 0.0:
                     continue
-                lam = np.zeros(3)
-                lam[o2] = np.sqrt(aq / den)
+                lam = ops.zeros(3)
+                lam[o2] = ops.sqrt(aq / den)
                 lam[o1] = tau * lam[o2]
                 lam[k] = w1 * lam[o1] + w2 * lam[o2]
                 if not (lam[0] > 0.0 and lam[1] > 0.0 and lam[2] > 0.0):
@@ -225,18 +280,18 @@ def p3p_lambda_twist(X, y):
                     J = np.array([[2.0 * (lam[0] - b01 * lam[1]), 2.0 * (lam[1] - b01 * lam[0]), 0.0],
                                   [2.0 * (lam[0] - b02 * lam[2]), 0.0, 2.0 * (lam[2] - b02 * lam[0])],
                                   [0.0, 2.0 * (lam[1] - b12 * lam[2]), 2.0 * (lam[2] - b12 * lam[1])]])
-                    if not abs(np.linalg.det(J)) > 0.0:
+                    if not abs(ops.det(J)) > 0.0:
                         break
-                    lam = lam - np.linalg.solve(J, r)
+                    lam = lam - ops.solve(J, r)
                 xa, xb = X[1] - X[0], X[2] - X[0]
                 Xm = np.column_stack([xa, xb, np.cross(xa, xb)])
-                if not abs(np.linalg.det(Xm)) > 0.0:
+                if not abs(ops.det(Xm)) > 0.0:
                     continue
                 for mirror in range(2):
                     Pt = (-1.0 if mirror else 1.0) * lam[:, None] * y
                     pa, pb = Pt[1] - Pt[0], Pt[2] - Pt[0]
                     Pm = np.column_stack([pa, pb, np.cross(pa, pb)])
-                    R = Pm @ np.linalg.inv(Xm)
+                    R = Pm @ ops.inv(Xm)
                     out.append((R, Pt[0] - R @ X[0], bool(mirror)))
         break   # one real root that gives a line pair carries every solution
     return out[:8]
@@ -250,19 +305,60 @@ def bearings(y):
     return b / np.linalg.norm(b, axis=1, keepdims=True)
 
 
-def ransac_pnp_p3p(y_med, X_med, y_high, X_high, r, thresh, rng=None, trace=False):
+def mirror_wins(e_mirror, e_front):
+    """pnp_minimal.h mirror_wins: a mirrored-depth pose replaces the best front-facing one only
+    below 1e-2 of its error, or when the front-facing error is NaN and its own is not."""
+    return bool(e_mirror < 1e-2 * e_front or (e_front != e_front and e_mirror == e_mirror))
+
+
+def p3p_pose4(X, y, ops=NumpyOps):
+    """P3P on four correspondences as pnp_minimal.h p3p_pose: Lambda Twist on points 0..2, the
+    reprojection error of point 3 per solution (strict "<", first of equals), front-facing and
+    mirrored-depth candidates kept apart, the mirrored one winning only by ``mirror_wins``.
+    X (4,3), y (4,3) C-normalised homogeneous.  Returns (R, t, err) or None."""
+    u, v = y[:, 0] / y[:, 2], y[:, 1] / y[:, 2]
+    nrm = [ops.sqrt(u[i] * u[i] + v[i] * v[i] + 1.0) for i in range(3)]
+    b = np.array([[u[i] / nrm[i], v[i] / nrm[i], 1.0 / nrm[i]] for i in range(3)])
+    inf = float("inf")
+    best, arg = [inf, inf], [None, None]
+    for R, t, mirrored in p3p_lambda_twist(X[:3], b, ops):
+        q = R @ X[3] + t
+        du, dv = u[3] - q[0] / q[2], v[3] - q[1] / q[2]
+        e = ops.sqrt(du * du + dv * dv)
+        k = 1 if mirrored else 0
+        if e < best[k]:
+            best[k], arg[k] = e, (R, t)
+    k = 1 if mirror_wins(best[1], best[0]) else 0
+    if arg[k] is None:
+        return None
+    return arg[k][0], arg[k][1], best[k]
+
+
+def ransac_pnp_p3p(y_med, X_med, y_high, X_high, r, thresh, rng=None, trace=False, tuples=None):
     """ransac_robust with n = 3 (ransac.py:72-111): per trial the P3P poses in order, each
     scored on D_med; strict ">" over (trial, pose) within the front-facing and within the
     mirrored-depth poses, a mirrored winner only at more than twice the front-facing count.  Returns (R, t, inl_med, inl_high,
-    best_trial, best_pose, counts (r, 8) or None)."""
+    best_trial, best_pose, counts (r, 8) or None).  With ``tuples`` (r, 3) the samples are given
+    (``rng`` is not consumed) and equal triples are solved and scored once."""
+    memo = {}
     # per class (front-facing, mirrored-depth): the first pose of largest count, strict ">"
     cls = [[-1, -1, 0, None, None], [-1, -1, 0, None, None]]
     counts = np.zeros((r, 8), np.int64) if trace else None
     for i in range(r):
-        T = gen_rnd_indices(len(X_high), 3, rng)
-        sols = p3p_lambda_twist(X_high[T], bearings(y_high[T]))
-        for j, (R, t, mirrored) in enumerate(sols):
-            c_med = int(np.count_nonzero(thresh >= pose_errors(R, t, X_med, y_med)))
+        if tuples is None:
+            T = gen_rnd_indices(len(X_high), 3, rng)
+            scored = None
+        else:
+            T = [int(v) for v in tuples[i]]
+            scored = memo.get(tuple(T))
+        if scored is None:
+            sols = p3p_lambda_twist(X_high[T], bearings(y_high[T]))
+            scored = [(R, t, mirrored,
+                       int(np.count_nonzero(thresh >= pose_errors(R, t, X_med, y_med))))
+                      for R, t, mirrored in sols]
+            if tuples is not None:
+                memo[tuple(T)] = scored
+        for j, (R, t, mirrored, c_med) in enumerate(scored):
             if trace:
                 counts[i, j] = c_med
             b = cls[1 if mirrored else 0]

@@ -1,6 +1,8 @@
 """GPU parity of the PnP path (DLT pnp.py:132-160, consensus ransac.py:37-113) against the
 oracle restatement and the reference's noise-free BAdino2 scene (R, t from the reference's
-fun.camera_resectioning).  Parity with OpenCV solvePnPRansac is unpinned (absent)."""
+fun.camera_resectioning).  Parity with OpenCV solvePnPRansac is unpinned (absent); the minimal
+kernels behind it (EPnP, P3P) are checked here on known answers and in test_gpu_pnp_edges.py
+against CPU restatements on noisy data, with the size boundaries of the whole path."""
 import random
 
 import numpy as np

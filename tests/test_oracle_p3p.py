@@ -4,6 +4,7 @@ put the three points behind the camera, and the RANSAC restatement finds the pos
 import random
 
 import numpy as np
+import pytest
 
 from oracle import pnp_ref
 
@@ -66,3 +67,79 @@ def test_consensus_arithmetic_emulation_equals_the_oracle():
         Rp, tp = R + rs.normal(0, 1e-3, (3, 3)), t + rs.normal(0, 1e-3, 3)
         e = pnp_exact.errors_exact(np.concatenate([Rp.ravel(), tp]), X, y)
         assert np.array_equal(e, pnp_ref.pose_errors(Rp, tp, X, y))
+
+
+def _dist(R, t, Rr, tr):
+    return max(np.abs(R - Rr).max(), np.abs(t - tr).max() / np.abs(tr).max())
+
+
+def test_p3p_pose4_recovers_the_pose():
+    """Three points solve, the fourth chooses: the exact pose on noise-free data, in front of
+    the camera and (a negative-scale camera, every depth negated) behind it."""
+    rs = np.random.RandomState(3)
+    found = 0
+    for trial in range(100):
+        R = _rot(rs.normal(0, 0.5, 3))
+        t = np.array([rs.uniform(-1, 1), rs.uniform(-1, 1), rs.uniform(4, 9)])
+        X = rs.uniform(-1.5, 1.5, (4, 3))
+        for tz in (t, t * np.array([1.0, 1.0, -1.0])):
+            Y = X @ R.T + tz
+            out = pnp_ref.p3p_pose4(X, Y / Y[:, 2:])
+            found += out is not None and _dist(out[0], out[1], R, tz) < 1e-7 and out[2] < 1e-8
+    assert found >= 196, found
+
+
+def test_mirror_wins_rule():
+    inf, nan = float("inf"), float("nan")
+    assert pnp_ref.mirror_wins(0.9e-2, 1.0) and not pnp_ref.mirror_wins(1.1e-2, 1.0)
+    assert pnp_ref.mirror_wins(5.0, inf) and not pnp_ref.mirror_wins(inf, inf)
+    assert pnp_ref.mirror_wins(1.0, nan) and not pnp_ref.mirror_wins(nan, nan)
+    assert not pnp_ref.mirror_wins(nan, 1.0)
+
+
+def test_ransac_pnp_tuples_is_the_loop_with_given_samples():
+    """ransac_pnp_tuples = ransac_pnp fed the same samples; ransac_pnp_p3p(tuples=) likewise."""
+    from tsbb15_amd import synth
+    X, _, y, _, _, _ = synth.pnp_scene(80, 0.2, seed=3, sigma=0.05)
+    thr = (1.5 / 800.0) ** 2
+    rng = random.Random(4)
+    tup = np.array([pnp_ref.gen_rnd_indices(80, 6, rng) for _ in range(60)])
+    tup[40] = tup[3]                        # a repeated tuple: scored once, counted twice
+    a = pnp_ref.ransac_pnp(y[:50], X[:50], y, X, 60, thr, 6, rng=pnp_ref._PrefixRng(tup),
+                           trace=True)
+    b = pnp_ref.ransac_pnp_tuples(y[:50], X[:50], y, X, tup, thr)
+    assert a[4] == b[4] >= 0 and np.array_equal(a[5], b[5])
+    for u, v in zip(a[:4], b[:4]):
+        assert np.array_equal(u, v)
+    c = pnp_ref.ransac_pnp_p3p(y, X, y, X, 60, thr, rng=pnp_ref._PrefixRng(tup[:, :3]),
+                               trace=True)
+    d = pnp_ref.ransac_pnp_p3p(y, X, y, X, 60, thr, trace=True, tuples=tup[:, :3])
+    assert c[4:6] == d[4:6] and np.array_equal(c[6], d[6])
+    for u, v in zip(c[:4], d[:4]):
+        assert np.array_equal(u, v)
+    # nothing reaches the threshold: no winner
+    e = pnp_ref.ransac_pnp_tuples(y, X, y, X, tup, 1e-30)
+    assert e[4] == -1 and e[0] is None and not e[5].any()
+
+
+@pytest.mark.parametrize("key", ["p3p_front", "p3p_dino", "p3p_dino_fine"])
+def test_p3p_pose4_float64_run_reproduces_the_golden_floors(key):
+    """The float64 restatement against the 50-digit poses recorded in
+    tests/golden/pnp_minimal.npz (make_golden_pnp_minimal.py): at most 5 % of the samples are
+    left out as ill-conditioned (floor above 1e-9) and the float64 run stays within the bar the
+    recorded floors set for tests/test_gpu_pnp_edges.py.  (BAdino2's true poses are the
+    mirrored-depth ones, but under 0.8 px of noise the mirrored candidate's fourth-point error
+    is never below 1e-2 of its front-facing twin's: all 50 samples exercise the rule's "no"
+    side; p3p_dino_fine, the same views under 0.01 px, has the mirrored pose win in 32 of 50.)"""
+    from conftest import golden
+    z = golden("pnp_minimal.npz")
+    X, y, Rg, tg, floor = (z[f"{key}_{s}"] for s in ("X", "y", "R", "t", "floor"))
+    keep = floor <= 1e-9
+    assert 1.0 - keep.mean() <= 0.05
+    bar = max(4.0 * floor[keep].max(), 16.0 * np.finfo(np.float64).eps)
+    mirrored = 0
+    for i in np.flatnonzero(keep):
+        R, t, _ = pnp_ref.p3p_pose4(X[i], y[i])
+        assert _dist(R, t, Rg[i], tg[i]) <= bar, (key, i)
+        mirrored += bool(((X[i] @ R.T + t)[:3, 2] < 0).all())
+    assert mirrored == (32 if key == "p3p_dino_fine" else 0)

@@ -29,7 +29,9 @@ solvePnPRansac structure:
 Limits: zero lens distortion only (tables.py:140 passes zeros); other ``flags`` raise
 ValueError.  OpenCV itself is absent and unversioned here, so parity with
 its exact samples is unpinned; the tests check known answers (BAdino2 views, including 4- and
-5-point subsets) and the documented semantics (pixel threshold, adaptive budget, determinism).
+5-point subsets), the documented semantics (pixel threshold, adaptive budget, determinism), the
+minimal solvers on noisy data against CPU restatements (oracle/epnp_ref.py, pnp_ref.p3p_pose4)
+and the winner's sample against a CPU replay of the Philox stream (tests/test_gpu_pnp_edges.py).
 """
 from __future__ import annotations
 
