@@ -4,7 +4,10 @@
 Bars: matching -- the same D / A partition, exactly; epipolar gate -- the same mask; new
 points -- 1e-6 relative (optimal triangulation); BA residuals -- 1e-12 (same expression; the
 reference's np.dot may sum in another order); BA Jacobian -- equal to the oracle's analytic
-blocks to 1e-12 and consistent with finite differences of the GPU residuals."""
+blocks to 1e-12 and consistent with finite differences of the GPU residuals (against the same
+differences of the longdouble restatement of tests/tables_edges_fixture.py; measured on the
+MI355X: 0.012 of the derived bar).  Sizes at tile and block edges, ties and the gate:
+tests/test_gpu_tables_edges.py."""
 import numpy as np
 import pytest
 
@@ -67,3 +70,31 @@ def test_ba_residuals_and_jacobian(ctx, tag):
     np.testing.assert_allclose(Jp, Jp0, rtol=1e-12, atol=1e-15)
     with pytest.raises(ValueError):
         gt.ba_residuals(cams, pts, view, point + nP, y[:, :2])
+
+
+def test_ba_finite_differences_of_the_gpu_residuals(ctx):
+    """Central differences of gt.ba_residuals in the 12 entries of one camera and the 3
+    coordinates of one point against the same differences of the longdouble restatement, at the
+    same float64 arguments: only the rounding of the two residuals separates them, so the bar is
+    (bar_r(+h) + bar_r(-h)) / (2 h) with the residual's derived bar.  Whether such differences
+    agree with the analytic blocks is tests/test_oracle_tables.py's affair."""
+    import tables_edges_fixture as fx
+    if not fx.LD_OK:
+        pytest.skip(fx.LD_REASON)
+    case = fx.ba_case(fx.FD_N, "nC3")
+    worst = 0.0
+    for name, h, plus, minus in fx.fd_steps(case):
+        fd, ref_fd, bar = 0, 0, 0
+        for sgn, c in ((1, plus), (-1, minus)):
+            args = (c["cams"], c["pts"], c["ov"], c["op"], c["uv"])
+            ref, b, _ = fx.ba_ref(*args)
+            fd = fd + sgn * np.asarray(gt.ba_residuals(*args, ctx=ctx), dtype=fx.LD)
+            ref_fd = ref_fd + sgn * ref["r"]
+            bar = bar + b["r"]
+        touched = ref_fd != 0
+        assert touched.any(), name
+        ratio = float((np.abs(fd - ref_fd) / bar).max())      # both over 2 h
+        assert np.all(fd[~touched] == 0), name
+        worst = max(worst, ratio)
+        assert ratio <= 1.0, (name, ratio)
+    print(f"finite differences: worst error / bar {worst:.3f}")

@@ -14,10 +14,12 @@ starts 1e-4 away, 2.7e-10 with every track reversed (the LM stops where a step g
 relative + 1e-8 t^2 absolute where finite, NaN in the same places.
 
 Measured on the MI355X, GPU against the reference: kept points differ by 3.7e-11 (6x40),
-2.7e-10 (12x120), 6.0e-11 (16x60), 6.3e-12 (the three 128-view tracks); triangulate_nview on
-the clean 12x120 by 6.0e-10; err2 at most 0.69 of its bar (12x120).  Kept points of tracks
->= 4 lie within 6.7e-4 / 1.0e-3 / 5.8e-4 of truth.  End to end on 6x40: 27 observations and 3
-points removed, then BundleAdjustment2 from 6.1e-9 to 4.3e-9 per kept observation.
+2.7e-10 (12x120), 6.0e-11 (16x60), 6.3e-12 (the three 128-view tracks), 1.7e-11 / 1.9e-11 /
+2.1e-11 / 1.2e-15 (the tracks of 63 / 64 / 65 / 127 views, err2 at most 0.059 of its bar);
+triangulate_nview on the clean 12x120 by 6.0e-10; err2 at most 0.69 of its bar (12x120).  Kept
+points of tracks >= 4 lie within 6.7e-4 / 1.0e-3 / 5.8e-4 of truth.  End to end on 6x40: 27
+observations and 3 points removed, then BundleAdjustment2 from 6.1e-9 to 4.3e-9 per kept
+observation.
 """
 import numpy as np
 import pytest
@@ -146,37 +148,9 @@ def test_triangulate_nview_leaves_a_single_observation_alone(ctx):
 # ------------------------------------------------------------------------------------------
 # 4. the longest track
 # ------------------------------------------------------------------------------------------
-def _ring(nC=128):
-    """nC cameras on a wavy circle of radius 4 looking at the origin, 3 points near it seen by
-    all of them, noise 1e-4, 5 observations of each point displaced by 0.02."""
-    th = 2.0 * np.pi * np.arange(nC) / nC
-    C = 4.0 * np.stack([np.cos(th), 0.3 * np.sin(3.0 * th), np.sin(th)], axis=1)
-    z = -C / np.linalg.norm(C, axis=1, keepdims=True)
-    x = np.cross([0.0, 1.0, 0.0], z)
-    x /= np.linalg.norm(x, axis=1, keepdims=True)
-    y = np.cross(z, x)
-    R = np.stack([x, y, z], axis=1)
-    cams = np.concatenate([R, -np.einsum("kij,kj->ki", R, C)[:, :, None]], axis=2)
-    pts = np.array([[0.3, 0.1, -0.2], [-0.25, 0.3, 0.15], [0.05, -0.35, 0.3]])
-    rng = np.random.RandomState(77)
-    perm = rng.permutation(3 * nC)
-    ov = np.tile(np.arange(nC), 3)[perm].astype(np.int32)
-    op = np.repeat(np.arange(3), nC)[perm].astype(np.int32)
-    yh = np.einsum("nij,nj->ni", cams[ov], np.hstack([pts[op], np.ones((len(op), 1))]))
-    uv = yh[:, :2] / yh[:, 2:3] + 1e-4 * rng.standard_normal((len(op), 2))
-    bad = np.zeros(len(op), bool)
-    for j in range(3):
-        pick = rng.choice(np.flatnonzero(op == j), 5, replace=False)
-        ang = rng.uniform(0.0, 2.0 * np.pi, 5)
-        uv[pick] += 0.02 * np.stack([np.cos(ang), np.sin(ang)], axis=1)
-        bad[pick] = True
-    pts0 = pts + 0.05 * rng.standard_normal(pts.shape)
-    return cams, pts, pts0, ov, op, uv, bad
-
-
 def test_longest_track(ctx):
     assert _ffi.WASH_MAX_TRACK == 128
-    cams, truth, pts0, ov, op, uv, bad = _ring()
+    cams, truth, pts0, ov, op, uv, bad = wf.ring(128)
     pts, ok, pk, e2, info = gt.wash_points(cams, pts0, ov, op, uv, 1e-3, ctx=ctx)
     assert np.array_equal(ok, ~bad) and pk.all()
     assert info["hypotheses"] == 3 * 8128 and info["obs_removed"] == 15
@@ -190,6 +164,20 @@ def test_longest_track(ctx):
         gt.triangulate_nview(cams, pts0, np.r_[ov, 0].astype(np.int32),
                              np.r_[op, 1].astype(np.int32), np.vstack([uv, [[0.0, 0.0]]]),
                              ctx=ctx)
+
+
+@pytest.mark.parametrize("nC", wf.RING_EDGES)
+def test_track_lengths_around_the_wave_width(ctx, nC):
+    """The pair walk of the 64-lane class (ordinal p on lane p % 64, `while (b >= m)`) with a
+    track one short of the wave, equal to it, one past it and one short of two waves: a lane
+    then crosses no row, one row or several rows of the pair triangle in one stride."""
+    cams, truth, pts0, ov, op, uv, bad = wf.ring(nC)
+    gpu = gt.wash_points(cams, pts0, ov, op, uv, wf.THRESH, ctx=ctx)
+    ref = _ref(("ring", nC), wr.wash_points, cams, pts0, ov, op, uv, wf.THRESH)
+    _compare(gpu, ref, wf.THRESH ** 2, f"ring {nC}")
+    pts, ok, pk, e2, info = gpu
+    assert np.array_equal(ok, ~bad) and pk.all()
+    assert info["hypotheses"] == 3 * nC * (nC - 1) // 2
 
 
 # ------------------------------------------------------------------------------------------

@@ -75,6 +75,25 @@ def test_masks_are_stable_around_the_threshold(case):
         assert np.array_equal(ok, ok0) and np.array_equal(pk, pk0)
 
 
+@pytest.mark.parametrize("nC", wf.RING_EDGES)
+def test_ring_masks_are_stable_around_the_threshold(nC):
+    """The same condition for the rings of tests/test_gpu_wash.py whose tracks lie around the
+    wave width, and what that test asserts of the GPU, here of the reference alone: exactly the
+    15 displaced observations removed, every point kept, every pair a hypothesis."""
+    cams, truth, pts0, ov, op, uv, bad = wf.ring(nC)
+    res = {s: wr.wash_points(cams, pts0, ov, op, uv, wf.THRESH * s)
+           for s in (1.0, 1.0 - 1e-6, 1.0 + 1e-6)}
+    pts, ok0, pk0, err2, info = res[1.0]
+    for s in (1.0 - 1e-6, 1.0 + 1e-6):
+        assert np.array_equal(res[s][1], ok0) and np.array_equal(res[s][2], pk0)
+    assert np.array_equal(ok0, ~bad) and bad.sum() == 15 and pk0.all()
+    assert info["hypotheses"] == 3 * nC * (nC - 1) // 2 and info["obs_removed"] == 15
+    ratio = err2 / wf.THRESH ** 2
+    print(f"ring {nC}: {info['hypotheses']} hypotheses, final errors nearest to t^2 at factors "
+          f"{ratio[ratio < 1].max():.3f} and {ratio[ratio >= 1].min():.1f}")
+    assert ratio[ratio < 1].max() < 1 / 6 and ratio[ratio >= 1].min() > 6
+
+
 def test_wash_pays_off_in_bundle_adjustment():
     W, (pts, obs_keep, point_keep, _, _) = _ref(CASES[0])
     ov, op, uv = W["ov"], W["op"], W["uv"]

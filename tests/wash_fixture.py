@@ -5,6 +5,9 @@ Test infrastructure.
 For j % 3 == 0 one randomly chosen observation of point j is displaced by 0.02 in a random
 direction; for j % 3 == 1 with a track of >= 5 observations, two are.  The points start at
 truth + 0.05 N(0, 1); the cameras are the true ones.  thresh = 1e-3 is 10 sigma.
+
+``ring(nC)`` is the other extreme: three points seen by every one of nC cameras, for the longest
+track (128) and the track lengths around the 64-lane wave (RING_EDGES).
 """
 from __future__ import annotations
 
@@ -14,6 +17,7 @@ import ba_fixture as bf
 
 THRESH = 1e-3
 DISPLACEMENT = 0.02
+RING_EDGES = (63, 64, 65, 127)   # ring(nC): tracks on either side of the 64-lane wave, and 2 x 64 - 1
 
 
 def table(nC, nP, seed, displaced=True):
@@ -35,6 +39,34 @@ def table(nC, nP, seed, displaced=True):
     pts0 = P["pts"] + 0.05 * rng.standard_normal(P["pts"].shape)
     return dict(cams=P["cams"], pts=P["pts"], pts0=pts0, ov=ov, op=op, uv=uv, bad=bad,
                 track_len=count[op], thresh=THRESH)
+
+
+def ring(nC):
+    """nC cameras on a wavy circle of radius 4 looking at the origin, 3 points near it seen by
+    all of them, noise 1e-4, 5 observations of each point displaced by 0.02."""
+    th = 2.0 * np.pi * np.arange(nC) / nC
+    C = 4.0 * np.stack([np.cos(th), 0.3 * np.sin(3.0 * th), np.sin(th)], axis=1)
+    z = -C / np.linalg.norm(C, axis=1, keepdims=True)
+    x = np.cross([0.0, 1.0, 0.0], z)
+    x /= np.linalg.norm(x, axis=1, keepdims=True)
+    y = np.cross(z, x)
+    R = np.stack([x, y, z], axis=1)
+    cams = np.concatenate([R, -np.einsum("kij,kj->ki", R, C)[:, :, None]], axis=2)
+    pts = np.array([[0.3, 0.1, -0.2], [-0.25, 0.3, 0.15], [0.05, -0.35, 0.3]])
+    rng = np.random.RandomState(77)
+    perm = rng.permutation(3 * nC)
+    ov = np.tile(np.arange(nC), 3)[perm].astype(np.int32)
+    op = np.repeat(np.arange(3), nC)[perm].astype(np.int32)
+    yh = np.einsum("nij,nj->ni", cams[ov], np.hstack([pts[op], np.ones((len(op), 1))]))
+    uv = yh[:, :2] / yh[:, 2:3] + 1e-4 * rng.standard_normal((len(op), 2))
+    bad = np.zeros(len(op), bool)
+    for j in range(3):
+        pick = rng.choice(np.flatnonzero(op == j), 5, replace=False)
+        ang = rng.uniform(0.0, 2.0 * np.pi, 5)
+        uv[pick] += 0.02 * np.stack([np.cos(ang), np.sin(ang)], axis=1)
+        bad[pick] = True
+    pts0 = pts + 0.05 * rng.standard_normal(pts.shape)
+    return cams, pts, pts0, ov, op, uv, bad
 
 
 def mini_tables(W):

@@ -316,6 +316,31 @@ def f64c(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def i32c(a, what):
+    """Indices -> contiguous int32, never wrapped or truncated (numpy's own conversion does both
+    silently: 2**32 + 1 becomes 1, 1.7 becomes 1).  ValueError naming ``what`` for a value
+    outside int32, a value that is not integral or not finite, or a dtype that is not a number.
+    Integer-valued floats pass (tables hand them over); int32 input passes without a copy."""
+    a = np.asarray(a)
+    if a.dtype == np.int32:
+        return np.ascontiguousarray(a)
+    if a.size == 0:
+        return np.zeros(a.shape, dtype=np.int32)
+    if np.issubdtype(a.dtype, np.floating):
+        if not np.all(np.isfinite(a)):
+            raise ValueError(f'{what} holds a value that is not finite')
+        if np.any(a != np.trunc(a)):
+            raise ValueError(f'{what} holds a value that is not an integer')
+        lo, hi = float(a.min()), float(a.max())
+    elif np.issubdtype(a.dtype, np.integer):
+        lo, hi = int(a.min()), int(a.max())
+    else:
+        raise ValueError(f'{what} must hold integers, not {a.dtype}')
+    if lo < -2 ** 31 or hi > 2 ** 31 - 1:
+        raise ValueError(f'{what} holds a value outside int32')
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
 def rccl_library():
     """(version, path) of the RCCL shared object this process runs (rs_comm_library)."""
     v = C.c_int32(0)

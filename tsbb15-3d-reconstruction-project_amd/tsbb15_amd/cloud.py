@@ -31,7 +31,7 @@ def _index(a, name):
     a = np.asarray(a)
     if a.size and not np.issubdtype(a.dtype, np.integer):
         raise ValueError(f'{name} must hold integers')
-    return np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+    return _ffi.i32c(a, name).reshape(-1)
 
 
 def point_attributes(cams, pts, entry_point, entry_obs, obs_view, obs_color, ctx=None):

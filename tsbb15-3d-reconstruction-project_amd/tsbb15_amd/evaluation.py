@@ -48,7 +48,7 @@ def _faces(faces, nv):
         raise ValueError('faces must be (nf, 3)')
     if f.size and (f.min() < 0 or f.max() >= nv):
         raise ValueError('a face index is out of range')
-    return np.ascontiguousarray(f, dtype=np.int32)
+    return _ffi.i32c(f, 'faces')
 
 
 def default_cell(vertices, faces):

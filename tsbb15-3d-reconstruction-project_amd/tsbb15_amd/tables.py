@@ -111,8 +111,8 @@ def add_new_points(y1_hom, y2_hom, C1, C2, gate=EPIPOLAR_GATE, ctx=None):
 def _ba_args(cams, pts, obs_view, obs_point):
     cams = _ffi.f64c(cams).reshape(-1, 3, 4)
     pts = _ffi.f64c(pts).reshape(-1, 3)
-    ov = np.ascontiguousarray(obs_view, dtype=np.int32).ravel()
-    op = np.ascontiguousarray(obs_point, dtype=np.int32).ravel()
+    ov = _ffi.i32c(obs_view, 'obs_view').ravel()
+    op = _ffi.i32c(obs_point, 'obs_point').ravel()
     if len(ov) != len(op):
         raise ValueError('obs_view and obs_point differ in length')
     return cams, pts, ov, op

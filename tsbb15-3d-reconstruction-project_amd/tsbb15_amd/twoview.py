@@ -79,7 +79,7 @@ def triangulate_optimal_batch(C1, C2, x1, x2, cam=None, ctx=None):
     n = x1.shape[1]
     cp = None
     if cam is not None:
-        cam = np.ascontiguousarray(cam, dtype=np.int32)
+        cam = _ffi.i32c(cam, 'cam')
         if cam.shape != (n,):
             raise ValueError('cam must be (n,)')
         cp = _ffi.ptr(cam, _ffi.C.c_int32)
