@@ -758,6 +758,96 @@ int rs_match_rois_f64(rs_ctx *ctx, const double *img1, int64_t h1, int64_t w1,
 int rs_features_timing(rs_ctx *ctx, int32_t enable, double *ms);
 
 /* ------------------------------------------------------------------------------------------
+ * The tracking stage (tracking.hip): a pyramidal Lucas-Kanade (KLT) tracker that follows
+ * sub-pixel positions from one uint8 grey image into the next, the step that turns images into
+ * the track array of imgdata/README images.txt (x1 y1 ... x36 y36 per scene point, -1 where
+ * unseen) that correspondences.py serves from.  Every sum over a window is an exact integer, so
+ * no result depends on how lanes split the window; every fp64 step below is evaluated in the
+ * order written, each operation rounded once (no fused multiply-add).  The same inputs give
+ * bitwise the same outputs, and a restatement of this text gives the same bits.
+ *
+ * Pyramid.  Level 0 is the image.  Level l + 1 has size ((h + 1) / 2, (w + 1) / 2) and at (y, x)
+ *   the value (S + 128) >> 8, S the separable [1 4 6 4 1] x [1 4 6 4 1] integer sum of level l
+ *   around (2 y, 2 x) over the reflect-101 continuation (gfedcb|abcdefgh|gfedcba).  Both sides
+ *   of a level that is reduced must be at least 3.
+ * Gradients.  (Gx, Gy) of a level is its aperture-3 integer Sobel pair, [1 2 1] x [-1 0 1] and
+ *   its transpose, over the reflect-101 continuation: |G| <= 1020.
+ * Sampling.  A position (qx, qy) in fp64 is inside a level of width w and height h for the
+ *   half-window r when qx >= r && qx < w - 1 - r && qy >= r && qy < h - 1 - r; NaN and infinity
+ *   are outside, and the test is made in fp64 before any conversion to an integer.  With
+ *   ix = floor(qx), a = qx - ix, iy = floor(qy), b = qy - iy the weights are
+ *     w00 = floor(((1 - a) (1 - b)) 16384 + 0.5),  w01 = floor((a (1 - b)) 16384 + 0.5),
+ *     w10 = floor(((1 - a) b) 16384 + 0.5),        w11 = 16384 - w00 - w01 - w10
+ *   and the sample of an integer image v at window offset (i, j), -r <= i, j <= r, is
+ *     (w00 v[iy+i][ix+j] + w01 v[iy+i][ix+j+1] + w10 v[iy+i+1][ix+j] + w11 v[iy+i+1][ix+j+1]
+ *      + 256) >> 9
+ *   with an arithmetic shift (floor for negatives): five fractional bits.  A grey sample is at
+ *   most 8160, a gradient sample at most 32640 in magnitude, and every window sum below stays
+ *   under 2^41 for window <= 31: exact in int64 and exact when converted to fp64.
+ * One feature.  Given p (fp64, level 0), a guess g (0 when none), window = 2 r + 1 with
+ *   n = window^2 pixels, levels L, max_iter, eps, min_eig, from image A into image B:
+ *     tau = (min_eig n) 65536          (65536 = (8 32)^2: the squared gain of a stored gradient
+ *                                       sample over a unit grey slope)
+ *     for l = L - 1 down to 0:
+ *       p_l = p 2^-l
+ *       p_l outside level l             ->  l = 0: LOST;  l > 0: g <- 2 g, next level
+ *       T, Gx, Gy = samples of A's level l, and of its gradients, at p_l
+ *       A = sum Gx Gx, B = sum Gx Gy, C = sum Gy Gy   (integers, then converted to fp64)
+ *       det = A C - B B
+ *       textured = A + C >= 2 tau  &&  (A - tau) (C - tau) - B B >= 0  &&  det > 0
+ *       not textured                    ->  l = 0: FLAT;  l > 0: g <- 2 g, next level
+ *       d = g;  at most max_iter times:
+ *         q = p_l + d
+ *         q outside level l             ->  l = 0: LOST;  l > 0: leave the loop, keeping d
+ *         Jv = samples of B's level l at q
+ *         bx = sum (T - Jv) Gx,  by = sum (T - Jv) Gy   (integers, then fp64)
+ *         dx = (8 (C bx - B by)) / det,  dy = (8 (A by - B bx)) / det
+ *         d <- d + (dx, dy);  at l = 0 one more is counted in iters
+ *         leave the loop when dx dx + dy dy <= eps eps
+ *       g <- 2 d for l > 0, g <- d for l = 0
+ *     q = p + g;  q outside level 0     ->  LOST
+ *     residual = (sum |T - Jv|) / (32 n), Jv sampled at q from B's level 0;  the result is q, OK
+ *   iters is what the forward pass counted, whatever the status.
+ * Forward-backward.  With fb_tol >= 0 every feature that reached OK is tracked back from its
+ *   result, from image 1 into image 0, with the same parameters and no guess, on the pyramids
+ *   already built.  fb is max(|xb - px|, |yb - py|) of the backward result when the backward
+ *   pass is OK and -1 otherwise (also where it did not run).  A backward pass that is not OK, or
+ *   fb > fb_tol, makes the status FB.
+ * A status other than OK gives the position (-1, -1) and the residual -1.
+ * ------------------------------------------------------------------------------------------ */
+#define RS_KLT_OK 0
+#define RS_KLT_LOST 1           /* left the image (or was never inside it) at level 0        */
+#define RS_KLT_FLAT 2           /* the level-0 window failed the texture test                */
+#define RS_KLT_FB 3             /* failed the forward-backward test                          */
+#define RS_KLT_MAX_WINDOW 31    /* at most 16 window pixels per lane                         */
+#define RS_KLT_MAX_LEVELS 8
+#define RS_KLT_MAX_ITER 1024
+#define RS_KLT_MAX_N (1LL << 22) /* features of one call                                     */
+
+/* One pyramid step: out is ((h + 1) / 2, (w + 1) / 2) uint8.  RS_EINVAL: a side below 3 or above
+ * RS_IMAGE_MAX_SIDE. */
+int rs_pyr_down(rs_ctx *ctx, const uint8_t *image, int64_t h, int64_t w, uint8_t *out);
+
+/* img0 and img1 are (h, w) uint8; pts is (2, n) -- x row, y row; guess is (2, n) or null.
+ * Outputs: pos (2, n), status (n) RS_KLT_*, residual (n), iters (n), fb (n).  fb_tol < 0 switches
+ * the forward-backward test off.  One launch follows every feature through all its levels.
+ * RS_EINVAL before any launch: a null pointer, a side outside 1..RS_IMAGE_MAX_SIDE, window even
+ * or outside 3..RS_KLT_MAX_WINDOW, levels outside 1..RS_KLT_MAX_LEVELS, a reduced level with a
+ * side below 3, max_iter outside 1..RS_KLT_MAX_ITER, eps NaN or negative, min_eig not finite or
+ * negative, fb_tol NaN, n negative or above RS_KLT_MAX_N.  n = 0 returns at once, without a
+ * launch.  Points and guesses that are not finite are legal: such a feature is LOST. */
+int rs_klt_track(rs_ctx *ctx, const uint8_t *img0, const uint8_t *img1, int64_t h, int64_t w,
+                 const double *pts, const double *guess, int64_t n, int32_t window,
+                 int32_t levels, int32_t max_iter, double eps, double min_eig, double fb_tol,
+                 double *pos, int32_t *status, double *residual, int32_t *iters, double *fb);
+
+/* HIP events between the stages of the next rs_klt_track calls (enable != 0).  Returns the last
+ * timed call's device ms: slot 0 both pyramids, 1 the forward launch, 2 the backward launch (-1
+ * when fb_tol < 0: there is no such launch); -1 where none (tools/bench_tracking.py). */
+#define RS_TRACKING_TIMING_SLOTS 3
+int rs_tracking_timing(rs_ctx *ctx, int32_t enable, double *ms);
+
+/* ------------------------------------------------------------------------------------------
  * The point-cloud stage (cloud.hip): what main.py does last (main.py:175-176,
  * Tables.get3DPointsColorsAndNormals) and the surface normals 3Dvisualization.py attempts.
  * All fp64, one lane per point, no floating-point atomics: the same inputs give bitwise the

@@ -123,6 +123,7 @@ extern "C" int rs_ctx_destroy(rs_ctx *c) {
   c->pnp.destroy();
   c->ba.destroy();
   c->feat.destroy();
+  c->track.destroy();
   c->cloud.destroy();
   c->dense.destroy();
   c->dense_sgm.destroy();

@@ -111,6 +111,9 @@ struct rs_ctx {
   // rs_features_timing: around the kernels of the next front-end calls (features.hip), the last
   // timed call's device ms between its upload and its download
   rs::StageTimer<2, 1> feat{-1.0};
+  // rs_tracking_timing: between the stages of the next rs_klt_track calls (tracking.hip):
+  // pyramid, forward, backward
+  rs::StageTimer<4, RS_TRACKING_TIMING_SLOTS> track{-1.0};
   // rs_cloud_timing: between the stages of the next point-cloud calls (cloud.hip), per stage
   rs::StageTimer<5, RS_CLOUD_TIMING_SLOTS> cloud{-1.0};
   // rs_dense_timing: around the kernel of the next dense calls (dense.hip): plane sweep,

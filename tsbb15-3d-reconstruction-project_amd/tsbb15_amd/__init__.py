@@ -9,6 +9,8 @@ Drop-in modules mirroring the reference surface:
   tsbb15_amd.cv      solvePnPRansac, Rodrigues (the tables.py:141-145 call site)
   tsbb15_amd.evaluation  mesh_distance, compare_meshes, camera_errors (the step evaluation.py
                      names: accuracy and completeness of a mesh, errors of the cameras)
+  tsbb15_amd.tracking  track, track_sequence, Correspondences (the track array of
+                     imgdata/points.txt from images: a pyramidal Lucas-Kanade tracker)
 Compute runs in lib/librsamd.so (HIP, gfx950) through ctypes; there is no CPU fallback.
 """
 __version__ = "0.1.0"

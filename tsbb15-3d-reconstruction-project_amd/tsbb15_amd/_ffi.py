@@ -92,6 +92,7 @@ WASH_MAX_TRACK = 128
 CLOUD_MAX_CELLS = 1 << 21
 CLOUD_STAGES = ("grid", "scan", "sort", "normals", "attributes")
 EVAL_STAGES = ("bin", "scan", "scatter", "query")
+TRACKING_STAGES = ("pyramid", "forward", "backward")
 BA_LOSSES = ("linear", "soft_l1", "huber", "cauchy")   # RS_BA_LOSS_*: the index is the code
 BA_KERNELS = ("k_ba_linearize", "k_ba_camera", "k_ba_pointsum", "k_ba_point", "k_ba_schur",
               "k_ba_chol", "k_ba_step", "k_ba_cost+final")
@@ -212,6 +213,11 @@ _SIGS = {
                                     C.c_int64, C.c_int64, _i32p, C.c_int64, C.c_int32, _i32p,
                                     _i32p, _dp, _dp]),
     "rs_features_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "rs_pyr_down": (C.c_int, [C.c_void_p, _u8p, C.c_int64, C.c_int64, _u8p]),
+    "rs_klt_track": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int64, C.c_int64, _dp, _dp, C.c_int64,
+                               C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                               C.c_double, _dp, _i32p, _dp, _i32p, _dp]),
+    "rs_tracking_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
     "rs_cloud_attributes": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _i32p, _i32p,
                                       C.c_int64, _i32p, _dp, C.c_int64, _dp, _dp]),
     "rs_cloud_normals": (C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_double, _dp, _dp, _i32p, _dp,
