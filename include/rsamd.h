@@ -1268,6 +1268,85 @@ int rs_eval_mesh_distance(rs_ctx *ctx, const double *pts, int64_t n, const doubl
 int rs_eval_timing(rs_ctx *ctx, int32_t enable, double *ms);
 
 /* ------------------------------------------------------------------------------------------
+ * Mesh clean-up (mesh.hip): connected components, compaction and Taubin smoothing of the welded
+ * index mesh rs_surface_extract returns.  The reference project has no such code; nothing here
+ * restates code of it.  vertices is (nv, 3) fp64, faces (nf, 3) int32 with indices in 0..nv - 1.
+ * Every result below is unique: integer atomics (a minimum, a sum, a cursor whose order a sort
+ * removes) and fp64 sums in a stated order, so two calls give the same bits and
+ * tests/mesh_ref.py restates them to the bit.
+ *   RS_EINVAL before any launch, for all three calls: nv or nf negative or above the limits, a
+ * face index outside 0..nv - 1, a null pointer with a non-zero size.  nv = 0 and nf = 0 are valid.
+ * ------------------------------------------------------------------------------------------ */
+#define RS_MESH_MAX_VERTICES (1LL << 27)
+#define RS_MESH_MAX_FACES (1LL << 27)   /* so that the 6 nf adjacency entries fit an int32 */
+#define RS_MESH_MAX_ROUNDS 64           /* hook rounds of rs_mesh_components                */
+#define RS_MESH_MAX_ITERATIONS 65536    /* of rs_mesh_smooth                                */
+#define RS_MESH_SCAN_CHUNK 2048 /* items one workgroup scans, the chunk of the surface stage's
+                                   scans (the size boundaries of a test) */
+
+/* Connected components over shared vertex indices: two vertices are connected when a face names
+ * both.  A face may repeat an index.
+ *   label (nv) int32: the smallest vertex index of the vertex's component; a vertex in no face
+ *   labels itself.  size (nv) int32: the number of faces of the vertex's component, 0 for a
+ *   vertex in no face.  *count: the number of components, the vertices in no face included (the
+ *   v with label[v] == v).  *rounds: the hook rounds the call ran, the last, which found nothing
+ *   to do, included; 0 when nf == 0.
+ * Method: union-find.  parent[v] <= v holds at every moment, so a walk to a root strictly
+ * decreases and ends.  A round hooks, per face and for two of its edges, the larger of the two
+ * ends' roots under the smaller with an atomic minimum, and the next round first shortens every
+ * path to its root by pointer jumping.  No kernel waits for another lane or workgroup; the host
+ * launches rounds until one hooks nothing.  Every root that has a neighbour of a smaller root is
+ * hooked in a round, whatever the diameter: a strip of 100 000 triangles takes 2 rounds numbered
+ * along the strip and 11 numbered at random.  RS_EDEVICE, with a message,
+ * when RS_MESH_MAX_ROUNDS rounds did not suffice. */
+int rs_mesh_components(rs_ctx *ctx, const int32_t *faces, int64_t nf, int64_t nv, int32_t *label,
+                       int32_t *size, int64_t *count, int32_t *rounds);
+
+/* Drop vertices and renumber.  keep is (nv) uint8, non-zero: keep.  The kept vertices follow in
+ * their original order, their bits copied (they are not examined: a non-finite vertex passes);
+ * the faces all three of whose vertices are kept follow in their original order with the new
+ * indices; vmap (nv) int32, or null, receives the new index of a vertex or -1.
+ *   vertices_out is (vcap, 3) and faces_out (fcap, 3), provided by the caller (either may be null
+ * with capacity 0).  *nv_out and *nf_out are always set, to 0 on an argument error and otherwise
+ * to the sizes of the result.  RS_EINVAL, and nothing written, vmap included, when a capacity is
+ * too small: a call with zero capacities learns the sizes, a second with exact arrays fetches the
+ * result (the ABI of rs_surface_extract).  Also RS_EINVAL: a negative capacity.  The offsets are
+ * exclusive scans over chunks of RS_MESH_SCAN_CHUNK. */
+int rs_mesh_compact(rs_ctx *ctx, const double *vertices, int64_t nv, const int32_t *faces,
+                    int64_t nf, const uint8_t *keep, double *vertices_out, int64_t vcap,
+                    int32_t *faces_out, int64_t fcap, int32_t *vmap, int64_t *nv_out,
+                    int64_t *nf_out);
+
+/* Taubin's lambda|mu smoothing with uniform weights.  out is (nv, 3) fp64.
+ *   Row.  The row of v holds, for every face corner that names v, the face's other two indices;
+ *   entries equal to v itself (a face that repeats an index) are dropped.  N(v) is the set of the
+ *   row's distinct entries: the vertices other than v that share a face with v.
+ *   Boundary.  v is a boundary vertex when some u occurs exactly once in its row.  For faces
+ *   without repeated indices that is: v shares exactly one face with u, (u, v) is a boundary edge.
+ *   Fixed.  v is fixed when fixed (nv, uint8, or null) is non-zero at v, or when pin_boundary != 0
+ *   and v is a boundary vertex.
+ *   Pass with factor f, all fp64, no product fused with a sum, per coordinate:
+ *     s = the sum of x_u over N(v) in ascending order of u, from the first term, left to right;
+ *     x'_v = x_v + f (s / |N(v)| - x_v).
+ *   A fixed vertex and a vertex with empty N(v) keep their bits.
+ *   One iteration is a pass with lambda, then a pass with mu, each reading the positions the
+ *   pass before it wrote.  iterations == 0 returns the input bits.
+ * The rows are built once per call: count, exclusive scan, scatter through an integer cursor,
+ * then each row is sorted and its duplicates removed in place, which removes the cursor's order.
+ * Any degree works.  Also RS_EINVAL: a vertex coordinate, lambda or mu not finite, iterations
+ * outside 0..RS_MESH_MAX_ITERATIONS. */
+int rs_mesh_smooth(rs_ctx *ctx, const double *vertices, int64_t nv, const int32_t *faces,
+                   int64_t nf, int32_t iterations, double lambda, double mu, const uint8_t *fixed,
+                   int32_t pin_boundary, double *out);
+
+/* HIP events around the kernels of the next three calls above (enable != 0).  Returns the last
+ * timed calls' device ms: slot 0 components (all rounds and the sizes), 1 compact (flags, scans
+ * and emit), 2 adjacency (rs_mesh_smooth's rows), 3 smooth (its passes); -1 where none
+ * (tools/bench_mesh.py). */
+#define RS_MESH_TIMING_SLOTS 4
+int rs_mesh_timing(rs_ctx *ctx, int32_t enable, double *ms);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU (RCCL over xGMI).  One process per GPU; the unique id travels out of band.
  * ---------------------------------------------------------------------------------------- */
 #define RS_COMM_ID_BYTES 128

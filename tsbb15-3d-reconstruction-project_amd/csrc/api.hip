@@ -130,6 +130,7 @@ extern "C" int rs_ctx_destroy(rs_ctx *c) {
   c->surface.destroy();
   c->texture.destroy();
   c->eval.destroy();
+  c->mesh.destroy();
   if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;

@@ -131,6 +131,9 @@ struct rs_ctx {
   // rs_eval_timing: between the stages of the next mesh-distance calls (eval.hip): bin, scan,
   // scatter, query
   rs::StageTimer<5, RS_EVAL_TIMING_SLOTS> eval{-1.0};
+  // rs_mesh_timing: around the kernels of the next mesh clean-up calls (mesh.hip): components,
+  // compact, adjacency, smooth
+  rs::StageTimer<3, RS_MESH_TIMING_SLOTS> mesh{-1.0};
 };
 
 namespace rs {

@@ -253,6 +253,13 @@ _SIGS = {
                                         C.c_int64, C.c_double, C.c_double, _dp, _i32p, _dp,
                                         C.POINTER(EvalInfo)]),
     "rs_eval_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "rs_mesh_components": (C.c_int, [C.c_void_p, _i32p, C.c_int64, C.c_int64, _i32p, _i32p,
+                                     _i64p, _i32p]),
+    "rs_mesh_compact": (C.c_int, [C.c_void_p, _dp, C.c_int64, _i32p, C.c_int64, _u8p, _dp,
+                                  C.c_int64, _i32p, C.c_int64, _i32p, _i64p, _i64p]),
+    "rs_mesh_smooth": (C.c_int, [C.c_void_p, _dp, C.c_int64, _i32p, C.c_int64, C.c_int32,
+                                 C.c_double, C.c_double, _u8p, C.c_int32, _dp]),
+    "rs_mesh_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
     "rs_np_shard_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.POINTER(C.c_void_p)]),
     "rs_np_shard_destroy": (C.c_int, [C.c_void_p]),

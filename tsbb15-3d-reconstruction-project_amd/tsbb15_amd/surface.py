@@ -13,6 +13,11 @@ has no such stage and nothing here restates code of it.
   * ``render_depth``    the mesh rendered into a z-buffer per view (rs_surface_render_depth,
                         surface_texture.hip)
   * ``vertex_colors``   a colour per vertex from the views that see it (rs_surface_colorize)
+  * ``components``      connected components of an index mesh (rs_mesh_components, mesh.hip)
+  * ``compact``         drop vertices and renumber (rs_mesh_compact)
+  * ``remove_small``    ``components``, a policy on the host, ``compact``: floaters go
+  * ``smooth``          Taubin's lambda|mu smoothing (rs_mesh_smooth)
+  * ``clean``           ``remove_small`` -> ``smooth``
 
 Conventions are those of ``dense``: cameras are the project's normalised (3, 4) ``C``,
 ``P = K @ C``, pixel centres at integers, the depth of X in a view is ``C[2] @ [X; 1]`` and may
@@ -36,6 +41,12 @@ STAGES = ("integrate", "classify", "scan", "emit")
 TEXTURE_STAGES = ("raster_small", "raster_large", "gather")
 RASTER_SMALL = 32            # RS_SURFACE_RASTER_SMALL
 TEXTURE_LIST_CAP = 1 << 20   # RS_SURFACE_TEXTURE_LIST_CAP
+MESH_STAGES = ("components", "compact", "adjacency", "smooth")
+MESH_MAX_VERTICES = 1 << 27  # RS_MESH_MAX_VERTICES
+MESH_MAX_FACES = 1 << 27     # RS_MESH_MAX_FACES
+MESH_MAX_ROUNDS = 64         # RS_MESH_MAX_ROUNDS
+MESH_MAX_ITERATIONS = 65536  # RS_MESH_MAX_ITERATIONS
+MESH_SCAN_CHUNK = 2048       # RS_MESH_SCAN_CHUNK
 
 
 def _ctx(ctx):
@@ -399,12 +410,200 @@ def vertex_colors(vertices, faces, images, cams, K, normals=None, rel_tol=0.01, 
     return (colors, count, depth) if return_depth else (colors, count)
 
 
+def _index_mesh(faces, n_vertices):
+    """faces as contiguous (Nf, 3) int32 after the ABI's size and range rules."""
+    faces = np.asarray(faces)
+    if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype.kind not in 'iu':
+        raise ValueError('faces must be (Nf, 3) integers')
+    if n_vertices > MESH_MAX_VERTICES or len(faces) > MESH_MAX_FACES:
+        raise ValueError('more than 2^27 vertices or faces')
+    if len(faces) and (faces.min() < 0 or faces.max() >= n_vertices):
+        raise ValueError('a face index is out of range')
+    return np.ascontiguousarray(faces, dtype=np.int32)
+
+
+def _mask(a, name, n):
+    a = np.asarray(a)
+    if a.dtype not in (np.bool_, np.uint8) or a.shape != (n,):
+        raise ValueError(f'{name} must be bool or uint8 of shape (Nv,)')
+    return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def components(faces, n_vertices, return_rounds=False, ctx=None):
+    """Connected components over shared vertex indices (rs_mesh_components).  faces is (Nf, 3)
+    integers in 0..n_vertices - 1; a face may repeat an index.
+
+    Returns (label (Nv,) int32: the smallest vertex index of the vertex's component, a vertex in
+    no face labels itself; size (Nv,) int32: the faces of the vertex's component, 0 for a vertex
+    in no face; count: the number of components, the vertices in no face included), and as a
+    fourth item, when ``return_rounds`` is set, the hook rounds the device ran.
+
+    ValueError before any launch: faces not (Nf, 3) integers, more than 2^27 vertices or faces,
+    a face index out of range."""
+    try:
+        n = int(n_vertices)
+    except (TypeError, ValueError):
+        raise ValueError('n_vertices must be an integer') from None
+    if n < 0:
+        raise ValueError('n_vertices must not be negative')
+    faces = _index_mesh(faces, n)
+    label, size = np.empty(n, np.int32), np.empty(n, np.int32)
+    count, rounds = _ffi.C.c_int64(0), _ffi.C.c_int32(0)
+    _ffi.check(_ffi.lib().rs_mesh_components(
+        _ctx(ctx), _ffi.ptr(faces, _i32) if len(faces) else None, len(faces), n,
+        _ffi.ptr(label, _i32) if n else None, _ffi.ptr(size, _i32) if n else None,
+        _ffi.C.byref(count), _ffi.C.byref(rounds)))
+    if return_rounds:
+        return label, size, count.value, rounds.value
+    return label, size, count.value
+
+
+def compact(vertices, faces, keep, ctx=None):
+    """Drop the vertices where ``keep`` (Nv, bool or uint8) is false and renumber
+    (rs_mesh_compact).  Returns (vertices: the kept ones in their order, bit for bit; faces: those
+    all three of whose vertices are kept, in their order, with the new indices; vmap (Nv,) int32:
+    the new index of a vertex or -1).  The ABI is called twice, as in ``extract``.
+
+    ValueError before any launch: vertices not (Nv, 3), what ``components`` lists, keep not a
+    bool or uint8 mask of length Nv."""
+    vertices = _ffi.f64c(vertices)
+    if vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError('vertices must be (Nv, 3)')
+    n = len(vertices)
+    faces = _index_mesh(faces, n)
+    keep = _mask(keep, 'keep', n)
+    lib, h = _ffi.lib(), _ctx(ctx)
+    nv, nf = _ffi.C.c_int64(-1), _ffi.C.c_int64(-1)
+    vmap = np.empty(n, np.int32)
+
+    def call(vout, fout):
+        return lib.rs_mesh_compact(
+            h, _ffi.ptr(vertices, _d) if n else None, n,
+            _ffi.ptr(faces, _i32) if len(faces) else None, len(faces),
+            _ffi.ptr(keep, _ffi.C.c_uint8) if n else None,
+            _ffi.ptr(vout, _d) if len(vout) else None, len(vout),
+            _ffi.ptr(fout, _i32) if len(fout) else None, len(fout),
+            _ffi.ptr(vmap, _i32) if n else None, _ffi.C.byref(nv), _ffi.C.byref(nf))
+
+    vout, fout = np.empty((0, 3)), np.empty((0, 3), np.int32)
+    st = call(vout, fout)
+    if st != 0 and nv.value <= 0 and nf.value <= 0:
+        _ffi.check(st)                     # an error, not "the result does not fit"
+    if nv.value > 0 or nf.value > 0:
+        vout = np.empty((nv.value, 3))
+        fout = np.empty((nf.value, 3), np.int32)
+        _ffi.check(call(vout, fout))
+    return vout, fout, vmap
+
+
+def _keep_components(label, size, n_faces, min_faces, keep_largest, min_fraction):
+    """The vertex mask of ``remove_small`` from ``components``' label and size: host numpy."""
+    if min_faces is None and keep_largest is None and min_fraction is None:
+        raise ValueError('give at least one of min_faces, keep_largest, min_fraction')
+    keep = size > 0                                   # a vertex in no face is dropped
+    if min_faces is not None:
+        keep &= size >= int(min_faces)
+    if min_fraction is not None:
+        min_fraction = float(min_fraction)
+        if not 0.0 <= min_fraction <= 1.0:
+            raise ValueError('min_fraction must be in [0, 1]')
+        keep &= size >= min_fraction * n_faces
+    if keep_largest is not None:
+        k = int(keep_largest)
+        if k < 0:
+            raise ValueError('keep_largest must not be negative')
+        roots = np.flatnonzero((label == np.arange(len(label))) & (size > 0))
+        # the largest first, ties to the smaller label: roots ascends and the sort is stable
+        best = roots[np.argsort(-size[roots].astype(np.int64), kind='stable')[:k]]
+        keep &= np.isin(label, best)
+    return keep
+
+
+def remove_small(vertices, faces, min_faces=None, keep_largest=None, min_fraction=None,
+                 ctx=None):
+    """Drop the small components of a mesh: ``components``, a policy in host numpy, ``compact``.
+    A component stays when it meets every criterion given: at least ``min_faces`` faces, among
+    the ``keep_largest`` components of most faces (ties go to the smaller label), at least
+    ``min_fraction`` of all faces.  Vertices in no face are dropped.  Returns (vertices, faces,
+    vmap) as ``compact``.
+
+    ValueError before any launch: what ``compact`` lists, no criterion given."""
+    if min_faces is None and keep_largest is None and min_fraction is None:
+        raise ValueError('give at least one of min_faces, keep_largest, min_fraction')
+    vertices = _ffi.f64c(vertices)
+    if vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError('vertices must be (Nv, 3)')
+    faces = _index_mesh(faces, len(vertices))
+    label, size, _ = components(faces, len(vertices), ctx=ctx)
+    keep = _keep_components(label, size, len(faces), min_faces, keep_largest, min_fraction)
+    return compact(vertices, faces, keep, ctx=ctx)
+
+
+def smooth(vertices, faces, iterations=10, lam=0.5, mu=-0.53, fixed=None, pin_boundary=True,
+           ctx=None):
+    """Taubin's lambda|mu smoothing with uniform weights (rs_mesh_smooth).
+
+    N(v) is the set of vertices other than v that share a face with v.  A pass with factor f, in
+    fp64 without fused products: s = the sum of x_u over N(v) in ascending order of u,
+    x'_v = x_v + f (s / |N(v)| - x_v).  One iteration is a pass with ``lam``, then one with
+    ``mu``.  A vertex is fixed where ``fixed`` (Nv, bool or uint8) is set and, with
+    ``pin_boundary``, where it ends a boundary edge (an edge of exactly one face); a fixed
+    vertex, and one without a neighbour, keeps its bits.  Returns the new (Nv, 3) float64
+    vertices, the input's bits for ``iterations=0``.  Bitwise reproducible.
+
+    ValueError before any launch: vertices not (Nv, 3) or not finite, what ``components``
+    lists, iterations outside 0..65536, lam or mu not finite, fixed not a mask of length Nv."""
+    vertices = _ffi.f64c(vertices)
+    if vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError('vertices must be (Nv, 3)')
+    n = len(vertices)
+    faces = _index_mesh(faces, n)
+    if not np.all(np.isfinite(vertices)):
+        raise ValueError('the vertices must be finite')
+    iterations, lam, mu = int(iterations), float(lam), float(mu)
+    if not 0 <= iterations <= MESH_MAX_ITERATIONS:
+        raise ValueError('iterations must be in 0..65536')
+    if not np.isfinite(lam) or not np.isfinite(mu):
+        raise ValueError('lam and mu must be finite')
+    if fixed is not None:
+        fixed = _mask(fixed, 'fixed', n)
+    out = np.empty_like(vertices)
+    _ffi.check(_ffi.lib().rs_mesh_smooth(
+        _ctx(ctx), _ffi.ptr(vertices, _d) if n else None, n,
+        _ffi.ptr(faces, _i32) if len(faces) else None, len(faces), iterations, lam, mu,
+        _ffi.ptr(fixed, _ffi.C.c_uint8) if fixed is not None and n else None,
+        int(bool(pin_boundary)), _ffi.ptr(out, _d) if n else None))
+    return out
+
+
+def clean(vertices, faces, min_faces=None, keep_largest=None, min_fraction=None, iterations=10,
+          lam=0.5, mu=-0.53, pin_boundary=True, ctx=None):
+    """``remove_small`` with the criteria given (skipped when there is none), then ``smooth``
+    (skipped for ``iterations=0``).  Returns (vertices, faces, vmap); vmap is the identity when
+    no component was looked at."""
+    if min_faces is None and keep_largest is None and min_fraction is None:
+        vertices, faces = _ffi.f64c(vertices), _index_mesh(faces, len(vertices))
+        vmap = np.arange(len(vertices), dtype=np.int32)
+    else:
+        vertices, faces, vmap = remove_small(vertices, faces, min_faces, keep_largest,
+                                             min_fraction, ctx=ctx)
+    if iterations:
+        vertices = smooth(vertices, faces, iterations, lam, mu, pin_boundary=pin_boundary,
+                          ctx=ctx)
+    return vertices, faces, vmap
+
+
+_clean = clean    # ``reconstruct`` has a keyword of that name
+
+
 def reconstruct(images, cams, K, depths, origin, voxel, dims, trunc, min_weight=2, ctx=None,
-                colors=False, **fuse_kw):
+                colors=False, clean=None, **fuse_kw):
     """Posed images to a mesh: ``dense.fuse(..., return_maps=True)``, the depth set to NaN where
     ``keep`` is false, ``integrate`` with ``count`` as the weight, ``extract``.  ``fuse_kw`` goes
     to ``dense.fuse``: ``smooth=(p1, p2)`` there picks the depth maps' winners after semi-global
-    aggregation.  Returns (vertices, faces, tsdf, weight), and with ``colors=True``
+    aggregation.  ``clean``, a dict of the keywords of ``clean``, applies that function to the
+    extracted mesh before anything else uses it; with None the mesh is ``extract``'s.  Returns
+    (vertices, faces, tsdf, weight), and with ``colors=True``
     (vertices, faces, tsdf, weight, colors): the first item of ``vertex_colors`` on the same
     images, with the mesh's ``vertex_normals``."""
     fuse_kw.pop('return_maps', None)
@@ -413,6 +612,8 @@ def reconstruct(images, cams, K, depths, origin, voxel, dims, trunc, min_weight=
     tsdf, weight = integrate(depth, cams, K, origin, voxel, dims, trunc,
                              weights=maps["count"].astype(np.float32), ctx=ctx)
     vertices, faces = extract(tsdf, weight, origin, voxel, min_weight=min_weight, ctx=ctx)
+    if clean is not None:
+        vertices, faces, _ = _clean(vertices, faces, ctx=ctx, **dict(clean))
     if not colors:
         return vertices, faces, tsdf, weight
     col = vertex_colors(vertices, faces, images, cams, K,
@@ -428,6 +629,15 @@ def timing(enable, ctx=None):
     ms = np.zeros(len(STAGES))
     _ffi.check(_ffi.lib().rs_surface_timing(ctx.handle, int(enable), _ffi.ptr(ms, _d)))
     return dict(zip(STAGES, ms.tolist()))
+
+
+def mesh_timing(enable, ctx=None):
+    """The same for the next ``components``, ``compact`` and ``smooth`` calls (rs_mesh_timing):
+    {components, compact, adjacency, smooth: device ms}, -1 where none."""
+    ctx = ctx or _ffi.default_context()
+    ms = np.zeros(len(MESH_STAGES))
+    _ffi.check(_ffi.lib().rs_mesh_timing(ctx.handle, int(enable), _ffi.ptr(ms, _d)))
+    return dict(zip(MESH_STAGES, ms.tolist()))
 
 
 def texture_timing(enable, ctx=None):
