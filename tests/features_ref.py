@@ -48,12 +48,13 @@ def harris_tensor(image, block_size, kernel_size):
 
 
 def harris64(image, block_size, kernel_size, k=0.04):
-    """The response in float64 and the magnitude s^4 (|ac| + b^2 + k (a + c)^2) its rounding
+    """The response in float64 and the magnitude s^4 (|ac| + b^2 + |k| (a + c)^2) its rounding
     error scales with (a, b, c the integer sums)."""
     sxx, sxy, syy = (t.astype(np.float64) for t in harris_tensor(image, block_size, kernel_size))
     s2 = harris_scale(block_size, kernel_size) ** 2
     a, b, c = sxx * s2, sxy * s2, syy * s2
-    return a * c - b * b - k * (a + c) * (a + c), np.abs(a * c) + b * b + k * (a + c) * (a + c)
+    return (a * c - b * b - k * (a + c) * (a + c),
+            np.abs(a * c) + b * b + abs(k) * (a + c) * (a + c))
 
 
 def harris(image, block_size, kernel_size, k=0.04, raw=False):
