@@ -947,13 +947,17 @@ int rs_cloud_timing(rs_ctx *ctx, int32_t enable, double *ms);
  *   the b-sums in fp32 in raster order.  The sums are accumulated on the values shifted by 128
  *   (one pass, no second centring pass).  The score is valid when the window lies inside the
  *   image, all n samples are valid, va >= min_var n^2 (on the integers) and vb >= min_var n^2.
+ *   The second test is made in fp32: vb as the fp32 expression above against
+ *   (float)(min_var n^2).  Equality passes both tests.
  *   Cost.  cost(pixel, k) = the sum of the valid sources' scores in source order / their number
  *   nvalid; no valid source: the hypothesis is invalid (NaN in the volume).
  *   Winner.  index = the k of the largest cost, the smallest such k on ties; score its cost,
  *   nvalid its number of sources.  With c-, c0, c+ the costs at index - 1, index, index + 1:
  *   delta = clamp(0.5 (c- - c+) / (c- - 2 c0 + c+), -0.5, 0.5), and 0 when a neighbour is
- *   missing or invalid or the denominator is not negative.  A pixel without a valid hypothesis
- *   gets index -1, delta 0, score NaN, nvalid 0.
+ *   missing or invalid or the denominator is not negative.  The formula is evaluated in fp32 as
+ *   written, (c- - 2 c0) + c+ with a rounding after each step: where c+ == c0 (a repeated depth)
+ *   delta is 0.5 or, when c- - 2 c0 rounds, a few floats below it.  A pixel without a valid
+ *   hypothesis gets index -1, delta 0, score NaN, nvalid 0.
  * index (h, w) int32, delta and score (h, w) float, nvalid (h, w) uint8; volume (D, h, w) float
  * is written when not null, and the other outputs do not depend on that.
  * RS_EINVAL before any launch: patch even or outside 3..RS_DENSE_MAX_PATCH, S outside
