@@ -263,12 +263,21 @@ int rs_f8_plan_prune_stats(rs_f8_plan *plan, int64_t out[4]);
  * previous run had the same H and threshold over the same points has no sample; its L (as
  * rs_f8_plan_prune_stats reports it) is that run's best count less a gap (RSAMD_CARRY_GAP).  Such
  * a run is exact when the best full count among its survivors reaches L, which is checked on the
- * device; otherwise every hypothesis is counted again without pruning (the run "fell back").
+ * device; otherwise the run "fell back": its last kernel selects nothing, and every hypothesis is
+ * counted again without pruning when the run is read, inside the first of rs_f8_plan_result and
+ * the accessors below called after it.  Only the last run issued can be read; a fallen-back run
+ * that is followed by another run, by rs_f8_plan_set_points, rs_f8_plan_set_count_precision or
+ * rs_f8_plan_destroy before it is read is never counted again and has no result (the accessors
+ * return RS_EINVAL for it until the next run is issued).
  * Results are those of the unpruned count either way.  out = {runs carried since the plan was
  * created, runs among them that fell back, whether the last run was carried, whether it fell
  * back}.  set_points, a retarget, rs_f8_plan_set_count_precision and a run with another H or
  * threshold end the carry: the next run on each lane takes a sample again. */
 int rs_f8_plan_carry_stats(rs_f8_plan *plan, int64_t out[4]);
+/* out = {fallen-back runs counted again when they were read, since the plan was created; the
+ * kernel launches the last run enqueued for its count: 3 with a sample (sample, prefix, rest), 2
+ * for a carried run, 1 unpruned, 2 for the float64 kernel and its maximum}.  Host state: no wait. */
+int rs_f8_plan_recount_stats(rs_f8_plan *plan, int64_t out[2]);
 /* The counting stages' own per-hypothesis counts of the last run, with no recount (test &
  * diagnostics).  After a pruned run: the full count of a sample hypothesis or a survivor, and
  * for a dropped hypothesis K minus its certified outliers among the first K points, an upper

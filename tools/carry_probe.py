@@ -1,7 +1,7 @@
 """bench.py's timed loop (C2, Philox, runs back to back, the counting kernel timed on every
-8th run) with what bench.py does not print: the plan's carry_stats() over all the runs, its
-lane_waits(), the prune_stats() of the last run and the count between the timing events.  One
-JSON line (tools/carry_ab.sh collects them).
+8th run) with what bench.py does not print: the plan's carry_stats() and recount_stats() over all
+the runs, its lane_waits(), the prune_stats() of the last run and the count between the timing
+events.  One JSON line (tools/carry_ab.sh and tools/nocheck_ab.sh collect them).
 
   python tools/carry_probe.py <label> [--steps 100 --warmup 200]
 """
@@ -48,6 +48,10 @@ def main():
         rec["carry_stats"] = plan.carry_stats()
     except AttributeError:      # a library from before the carried bound (RSAMD_LIB)
         rec["carry_stats"] = None
+    try:                        # [recounts at a flush, count launches of the last run]
+        rec["recount_stats"] = list(plan.recount_stats())
+    except AttributeError:      # a library from before the deferred recount
+        rec["recount_stats"] = None
     plan.close()
     print(json.dumps(rec))
 

@@ -30,9 +30,6 @@ struct SolveArgs {
   double gT, gDe, gDn;  // their inputs: (t/s)^2 and the fp32 error bounds of e and m
   int *pw;       // pruned count: the run's kPruneWords words zeroed, may be null
   int *gdone_b;  // ... and the rest stage's per-group finish counters
-  // carried run (above k_f8_count32q, "Carried bound"): the check stage's storage zeroed, its
-  // counts, per-group finish counters and c* word; all null otherwise
-  int *counts_fb, *gdone_fb, *fbw;
 };
 
 // One run's selection tail (candidates, reference statistics, replay, S_RANSAC).
@@ -52,11 +49,14 @@ struct TailArgs {
   F8DevResult *hres;  // pinned host header slot (device mapping)
   int *hinl;          // pinned host S_RANSAC (int32, device mapping)
   int *carry;         // the lane's carry word: the run's c* is left there, may be null
-  // carried run: the prune words, the check stage's counts and c* word, the plan's fallback
-  // counter; the tail takes c* and the counts from the check stage's storage when the run fell
-  // back (carry_fell_back); all null otherwise
+  // carried run: the prune words, the set's fallback storage (the whole count of every
+  // hypothesis and its c* word, filled by the plan's recount) and the plan's fallback counter; all
+  // null otherwise.  When the run fell back (carry_fell_back) the tail selects nothing: it marks
+  // hres, counts the fallback and leaves the run's c_f in the carry word.  recount: the second
+  // pass over such a run, after the recount: c* and the counts from the fallback storage
   const int *pw, *counts_fb, *fbw;
   int *n_fb;
+  int recount;
 };
 
 hipError_t launch_pack_points(const double *p1, const double *p2, int n, Pt *pts,
@@ -101,15 +101,14 @@ struct PruneArgs {
   int g_first;   // hypothesis groups counted in full by the sample stage
   int margin;    // m: K = roundup8(n - L + m)
   int min_skip;  // fewer points than this to skip: K = npad, nothing is pruned
-  // carried run: L = *carry - gap instead of status[0] (null: the sample's L); cf: the run's
-  // status word c_f, which the check stage reads and never writes
+  // carried run: L = *carry - gap instead of status[0] (null: the sample's L)
   const int *carry;
   int gap;
-  const int *cf;
 };
 // What one launch of k_f8_count32q reads and writes.  counts / gdone / status are the stage's
-// own: the check stage of a carried run takes the set's fallback storage (counts_fb, gdone_fb and
-// the word fbw) there.  gdone and status may be null (no fused c*), Hdev too (H hypotheses).
+// own: the recount of a carried run that fell back takes the set's fallback storage (counts_fb,
+// gdone_fb and the word fbw) there.  gdone and status may be null (no fused c*), Hdev too (H
+// hypotheses).
 struct CountArgs {
   const float4 *ptsq;
   const Pt *pts;
@@ -127,10 +126,7 @@ struct CountArgs {
 // cuts its slices from K on the device), H the run's hypothesis count.  kCountRest: the survivors
 // over the whole window; the grid is sized for `waves` resident waves (the survivor count is on
 // the device), at most the grid of sh, the shape of the H hypotheses the prefix stage screened.
-// kCountCheck, the last stage of a carried run: a whole-window count of all H hypotheses when the
-// run fell back (K < npad and c_f < L, read from pa.pw and pa.cf, which no wave of this launch
-// writes); otherwise every workgroup returns at once.
-constexpr int kCountWhole = 0, kCountPrefix = 1, kCountRest = 2, kCountCheck = 3;
+constexpr int kCountWhole = 0, kCountPrefix = 1, kCountRest = 2;
 hipError_t launch_f8_count32q(int mode, const CountArgs &a, const Count32qShape &sh, int waves,
                               const PruneArgs &pa, hipStream_t s);
 hipError_t launch_f8_count(const Pt *pts, int n, int H, const double *Fsoa, int64_t ld,

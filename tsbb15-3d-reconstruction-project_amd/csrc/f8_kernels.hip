@@ -73,11 +73,6 @@ __device__ __forceinline__ void solve_one(const SolveArgs &a, int h) {
     }
     if ((h & 63) == 0) a.gdone_b[h >> 6] = 0;
   }
-  if (a.counts_fb) {  // a carried run's check stage accumulates into storage of its own
-    a.counts_fb[h] = 0;
-    if ((h & 63) == 0) a.gdone_fb[h >> 6] = 0;
-    if (h == 0) a.fbw[0] = 0;
-  }
   int idx[8];
   if (mode == RSD_SAMPLER_PHILOX) {
     floyd_sample<8>(seed, hyp_offset + static_cast<uint64_t>(h), n, idx);
@@ -328,22 +323,41 @@ __global__ __launch_bounds__(256) void k_f8_count(const Pt *__restrict__ pts, in
 // c* >= c_f >= L_g.  So the run is exact if and only if c_f >= L_g, and then status[0] = c_f = c*
 // and the tail sees what it would have seen; otherwise nothing is known and the run is counted
 // again without pruning.  When K = npad (L_g <= 1 or too little to skip) nothing was dropped and
-// the run is exact whatever L_g.  Three launches in stream order, every decision on the device:
+// the run is exact whatever L_g.  Two launches in stream order, every decision on the device:
 //   prefix  (kCountPrefix, g_first = 0) L_g = *carry - gap, read from the lane's carry word, which
 //           the tail of the lane's previous run wrote in an earlier launch on the same stream
-//           (cand_stats_block: it holds that run's final c*); K, the screen and the survivor list
-//           as above
+//           (cand_stats_block); K, the screen and the survivor list as above
 //   rest    (kCountRest) unchanged: the survivors over the whole window, c_f into status[0]
-//   check   (kCountCheck) carry_fell_back, K < npad and status[0] < L_g, read from pw[] and
-//           status[0], which no wave of this launch writes: if false every workgroup returns at
-//           once (a grid of one slice per resident wave); if true a whole-window count of all H
-//           hypotheses into storage of its own (counts_fb, gdone_fb, c* in fbw[0], zeroed by the
-//           solve as counts is)
-// The tail makes the same test and takes c*, the counts and max_count_fast from the check stage's
-// storage when it holds, leaves c* in the lane's carry word for the lane's next run, and counts
-// the fallbacks.  rs_f8_plan_counts / stage_counts follow the same choice.  No cross-lane event,
-// no host read and no host wait: the word is per lane and stream order covers it.
-// Measured against the parent commit's library (profiles/carry/ab.txt, tools/carry_ab.sh; the
+// The tail makes the test carry_fell_back (K < npad and status[0] < L_g, from pw[] and status[0],
+// which no tail block writes).  When it fails the run is exact: the tail selects as ever and leaves
+// c* in the lane's carry word.  When it holds the tail selects nothing: it sets fell_back in the
+// run's pinned header, counts the fallback, and leaves c_f in the carry word -- a full count of
+// this run's own hypotheses (0 with no survivor), so a guess below the one that failed: the lane's
+// next run either is exact against it or falls back to a lower one still, and from 0 it gets
+// K = npad, the whole count, and the true c* again; the c* of an older run is never left there, or
+// a guess that was too high once would stay too high.  The status words 1..3 and the block
+// counts stay as the solve zeroed them, for the second pass.  The recount is deferred to the one
+// place the host waits (plan_flush in f8_plan.hip, f8::flush_recounts), and only for the run that
+// is read: the set's fallback storage (counts_fb, gdone_fb, the word fbw) zeroed, a whole-window
+// count (kCountWhole) of all H hypotheses into it, the tail again with TailArgs::recount, which
+// takes c*, the counts and max_count_fast from that storage, clears fell_back and leaves the true
+// c* in the carry word.  rs_f8_plan_counts / stage_counts return that storage.  A fallen-back run
+// that is never read is never recounted.  No cross-lane event and no host read on the hot path: the
+// word is per lane and stream order covers it.
+// Before this, every carried run ended with a third launch (the check stage: a grid of one slice per
+// resident wave that tested carry_fell_back and counted again on the spot), empty in all 298
+// carried runs of the bench yet 5.9 us on the lane's chain, and the solve zeroed the fallback
+// storage in every run.  Measured against that form (profiles/nocheck/ab.txt, tools/nocheck_ab.sh,
+// the parent commit's library, two sessions of five interleaved rounds): C2 bench value
+// 1.703-1.718e9 against 1.657-1.711e9 hypotheses/s (medians 1.02 x) and 1.705-1.782e9 against
+// 1.682-1.715e9 (1.03 x); the ranges overlap in both sessions (the lowest new line lies below the
+// highest parent line), so by the rule the earlier stages were held to this is no gain at C2.
+// The chain is shorter as predicted (kernel trace: check 5.8 us x 298 gone, prefix 45.8 -> 46.3,
+// rest 29.1 -> 29.0, tail + solve 19.7 -> 20.0 us), but at 1e5 hypotheses the two lanes' kernels
+// compete for the machine and the step is no longer set by the chain alone: the wall time per run
+// (tools/chain_probe.py) went 55.7-56.8 -> 54.1-55.3 us at H = 1e5, 47.5-48.1 -> 44.3-44.8 at 5e4,
+// 41.9-42.6 -> 39.7-40.2 at 2.5e4 and 29.1-29.6 -> 25.5-26.1 at 4096, where the chain is all.
+// The carried bound against the sample, parent commit's library (profiles/carry/ab.txt, tools/carry_ab.sh; the
 // CPU model is tools/carry_model.py): C2 bench value 1.676-1.727e9 against 1.520-1.557e9
 // hypotheses/s (1.10 x, five interleaved rounds, every line of one arm outside the other's range),
 // the count between the timing events 62.3-65.3 us against 70.4-71.9 us; kernel trace of the bench:
@@ -386,12 +400,11 @@ __device__ __forceinline__ void group_done_max(int *counts, int *gdone, int *sta
 
 // Stages of the pruned count (k_f8_count32q's MODE, f8_kernels.h): kCountWhole the whole window,
 // kCountPrefix the prefix [0, K) of the groups past the sample (screened), kCountRest the survivors
-// over the whole window again, and kCountCheck, the check stage of a carried run: the whole window
-// again, into storage of its own, only when the carried bound turned out to be above c*
+// over the whole window again
 
 // A carried run fell back: it pruned (K = pw[2] < npad) against a bound L = pw[3] that the best
 // full count among its survivors, c_f = cf[0], did not reach.  Written by the prefix and rest
-// stages; the check stage and the tail only read them.
+// stages; the tail only reads them.
 __device__ __forceinline__ bool carry_fell_back(const int *pw, const int *cf, int npad) {
   return pw[2] < npad && cf[0] < pw[3];
 }
@@ -561,11 +574,7 @@ __global__ __launch_bounds__(BT) void k_f8_count32q(const float4 *__restrict__ p
   // every stage with win for npad; rest / Lq: the prefix stage's points past the window (-1:
   // none skipped, the exact count; else the screening loop) and L
   int win = npad, hoff = 0, rest = -1, Lq = 0;
-  constexpr bool kWhole = MODE == kCountWhole || MODE == kCountCheck;
-  if constexpr (MODE == kCountCheck) {
-    // uniform over the grid, before any barrier: nothing to do unless the run fell back
-    if (!carry_fell_back(pa.pw, pa.cf, npad)) return;
-  }
+  constexpr bool kWhole = MODE == kCountWhole;
   if constexpr (MODE == kCountPrefix) {
     // K from L = status[0], the sample stage's best full count, which no wave of this launch
     // writes (the group maxima go to pw[0]): every wave computes the same K.  A carried run has
@@ -881,8 +890,21 @@ __device__ void cand_stats_block(const TailArgs &a, int bid, int nblocks) {
   const int64_t ld = a.ld;
   const int *__restrict__ status = a.status;
   int *__restrict__ status_rw = a.status;
-  // a carried run that fell back: c* and the counts are the check stage's
+  // a carried run that fell back (no tail block writes the words of this test, so every block of
+  // both passes decides alike).  First pass: nothing is selected; the header is marked, the
+  // fallback counted, and the lane's next run gets c_f, the best full count among this run's own
+  // survivors (0 without one), as its guess.  Status words 1..3 and the block counts stay as the
+  // solve left them, for the second pass (a.recount, after the plan's recount at the flush that
+  // reads the run): c* and the counts are the recount's
   const bool fb = a.pw && carry_fell_back(a.pw, status, (n + 7) / 8 * 8);
+  if (fb && !a.recount) {
+    if (bid == 0 && threadIdx.x == 0) {
+      a.hres->fell_back = 1;
+      atomicAdd(a.n_fb, 1);
+      if (a.carry) *a.carry = status[0];
+    }
+    return;
+  }
   const int *__restrict__ counts = fb ? a.counts_fb : a.counts;
   const double thresh = a.thresh;
   int *__restrict__ bc = a.status + 4;
@@ -903,7 +925,6 @@ __device__ void cand_stats_block(const TailArgs &a, int bid, int nblocks) {
   if (bid == 0 && tid == 0) {
     // the lane's next run reads the word in a later launch on the same stream
     if (a.carry) *a.carry = cmax;
-    if (fb) atomicAdd(a.n_fb, 1);
   }
   const int thr = max(cmax - slack, 1);
   const int b0 = bid * per_block, b1 = min(H, b0 + per_block);
@@ -1163,6 +1184,7 @@ __device__ void replay_inliers(const Pt *__restrict__ pts, int n, const int *cou
         for (int k = 0; k < 9; ++k) fw[k] = 0.0;
       }
       const bool spec_ok = best >= 0 && brow >= 0;
+      hres->fell_back = 0;
       hres->n_candidates = nc;
       hres->max_count_fast = cfast_max;
       hres->guard_mismatch = mismatch;
@@ -1429,7 +1451,6 @@ hipError_t launch_f8_count32q(int mode, const CountArgs &a, const Count32qShape 
   switch (mode) {
     case kCountWhole: return count32q<kCountWhole>(a, sh.blocks, sh.per_wave, pa, s);
     case kCountPrefix: return count32q<kCountPrefix>(a, sh.blocks, sh.per_wave, pa, s);
-    case kCountCheck: return count32q<kCountCheck>(a, sh.blocks, sh.per_wave, pa, s);
     case kCountRest: {
       const int64_t blocks = std::max<int64_t>(
           1, std::min<int64_t>(sh.blocks, (waves + kCountBT / 64 - 1) / (kCountBT / 64)));

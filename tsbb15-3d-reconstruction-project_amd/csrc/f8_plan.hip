@@ -10,14 +10,20 @@
 //                    (RSAMD_PRUNE=1, the fp32 path) three in a row on the same lane -- sample,
 //                    prefix, rest (f8_kernels.hip above k_f8_count32q) -- with no host decision
 //                    and no event between them; a run whose lane last ran the same H and
-//                    threshold over the same points (RSAMD_CARRY=1) has prefix, rest, check
-//                    instead, its bound from that run's c* in the lane's carry word
+//                    threshold over the same points (RSAMD_CARRY=1) has prefix and rest alone,
+//                    its bound from that run's c* in the lane's carry word
 //
 // and leaves run k's tail pending on that lane: it rides along with the lane's next solve, or
 // is flushed alone by rs_f8_plan_result / set_points / destroy (plan_flush, the only place the
-// host waits).  The tail (candidates, reference statistics, replay, S_RANSAC; latency bound, a
-// few busy workgroups) and the solve (latency bound, ~1.5 waves per SIMD) thus share the
-// machine instead of running back to back.
+// host waits).  A carried run whose bound turned out to be above c* ("fell back", f8_kernels.hip
+// above k_f8_count32q) is not counted again on the lane: its tail selects nothing and marks the
+// run's pinned header.  Only the last run before a flush can be read through the API, so
+// plan_flush, when it serves an accessor and finds that mark on the last run, counts the run again
+// in full and runs its tail a second time before it returns (plan_recount).  A fallen-back run
+// that is never read is never recounted: its pinned slot is marked, not filled.  The tail
+// (candidates, reference statistics, replay, S_RANSAC; latency bound, a few busy workgroups) and
+// the solve (latency bound, ~1.5 waves per SIMD) share the machine in their one launch instead of
+// running back to back.
 //
 // One lane (RSAMD_OVERLAP=0): every run on the context's stream, the tail of run k-1 with the
 // solve of run k.
@@ -94,6 +100,9 @@ struct rs_f8_plan : f8::PlanBufs {
   int tail_cus = 256;         // CUs shared by the tail + solve launch
   f8::PruneKnobs knobs;       // the pruned count and the carried bound (RSAMD_PRUNE*, RSAMD_CARRY*)
   int64_t n_carried = 0;      // runs carried since the plan was created
+  int64_t n_recounts = 0;     // fallen-back runs counted again at a flush (plan_recount)
+  int count_launches = 0;     // launches the last run enqueued between its timing events
+  bool unread_dropped = false;  // the last run fell back and a dropping flush left it unread
   int *d_full = nullptr;      // rs_f8_plan_counts after a pruned run: the full counts (ld ints)
   int nospec = 0;             // RSAMD_NOSPEC=1 (test hook): the replay extracts S_RANSAC itself
   uint64_t *d_ts = nullptr;   // RSAMD_TSTAMP=<file>: wave timeline of the counting kernel
@@ -199,7 +208,8 @@ extern "C" int rs_f8_plan_create(rs_ctx *c, int64_t n, int64_t max_hyp, rs_f8_pl
   return RS_OK;
 }
 
-static int plan_flush(rs_f8_plan *p);
+static int plan_flush(rs_f8_plan *p, f8::FlushFor why);
+static int plan_recount(rs_f8_plan *p);
 
 // A new population for an existing plan (the drop-in's calls, one pair after another): the
 // per-point arenas are reallocated only when n exceeds what they hold; the per-hypothesis
@@ -207,7 +217,7 @@ static int plan_flush(rs_f8_plan *p);
 static int plan_retarget(rs_f8_plan *p, int64_t n) {
   if (n < 8) return fail(RS_EINVAL, "Cannot take a larger sample than population when 'replace=False'");
   if (n > (1LL << 30)) return fail(RS_EINVAL, "plan dimensions out of range");
-  int st = plan_flush(p);  // runs in flight read the resident points and results
+  int st = plan_flush(p, f8::FlushFor::kDrop);  // runs in flight read the resident points and results
   if (st) return st;
   if (n > p->cap_n) {
     const int64_t cap = std::max<int64_t>(n, p->cap_n + p->cap_n / 4);
@@ -280,20 +290,28 @@ static hipError_t lane1_drain(rs_f8_plan *p) {
   return f8::lane_drained(p->s, 1) ? lane_wait(p, 1) : hipSuccess;
 }
 
-// Enqueue both lanes' pending tails alone, then wait for both streams.
-static int plan_flush(rs_f8_plan *p) {
+// Enqueue both lanes' pending tails alone, then wait for both streams.  The last run's header is
+// final then: if it says the run fell back, a flush that serves an accessor counts the run again
+// (f8::flush_recounts); one that drops the results does not, and the run stays without a result.
+static int plan_flush(rs_f8_plan *p, f8::FlushFor why) {
   HIP_TRY(hipSetDevice(p->ctx->device));
   for (int l = 0; l < rs_f8_plan::kLanes; ++l) HIP_TRY(lane_tail_alone(p, l));
   if (p->s.busy[1]) HIP_TRY(hipStreamSynchronize(p->lane1));
   HIP_TRY(hipStreamSynchronize(p->ctx->stream));
   for (auto &e : p->excl) e = nullptr;
+  const bool pending = p->s.pending && p->s.runs > 0;
+  const bool carried = pending && p->last().carried;
+  const bool marked =
+      carried && p->h_slot[(p->s.runs - 1) % rs_f8_plan::kSlots]->fell_back != 0;
   f8::flushed(p->s);
+  if (f8::flush_drops_unread(pending, carried, marked, why)) p->unread_dropped = true;
+  if (f8::flush_recounts(pending, carried, marked, why)) return plan_recount(p);
   return RS_OK;
 }
 
 extern "C" int rs_f8_plan_destroy(rs_f8_plan *p) {
   if (!p) return RS_OK;
-  (void)plan_flush(p);
+  (void)plan_flush(p, f8::FlushFor::kDrop);
   plan_free(p);
   delete p;
   return RS_OK;
@@ -301,7 +319,7 @@ extern "C" int rs_f8_plan_destroy(rs_f8_plan *p) {
 
 extern "C" int rs_f8_plan_set_points(rs_f8_plan *p, const double *p1, const double *p2) {
   if (!p || !p1 || !p2) return fail(RS_EINVAL, "null pointer");
-  int st = plan_flush(p);  // runs in flight read the resident points
+  int st = plan_flush(p, f8::FlushFor::kDrop);  // runs in flight read the resident points
   if (st) return st;
   f8::carry_drop(p->s);
   rs_ctx *c = p->ctx;
@@ -423,11 +441,6 @@ static rsd::SolveArgs solve_args(const rs_f8_plan *p, const RunBufs &b, const Ru
     sa.pw = b.d_pw;
     sa.gdone_b = b.d_gdone_b;
   }
-  if (r.cp.carried) {
-    sa.counts_fb = b.d_counts_fb;
-    sa.gdone_fb = b.d_gdone_fb;
-    sa.fbw = b.d_fbw;
-  }
   return sa;
 }
 
@@ -465,7 +478,6 @@ static rsd::PruneArgs prune_args(const rs_f8_plan *p, const RunBufs &b, int lane
   if (b.carried) {  // every group is screened against the lane's carried bound
     pa.carry = p->d_carry + lane;
     pa.gap = pn.gap;
-    pa.cf = b.d_status;
   }
   return pa;
 }
@@ -491,8 +503,8 @@ static int enqueue_count(rs_f8_plan *p, RunBufs &b, const Run &r) {
     // groups screened, K from L on the device, survivors listed -> the survivors over the whole
     // window; all in stream order on this lane, no host decision.  A carried run has no sample:
     // prefix of every group against L = the lane's carry word - gap -> the survivors (c_f in
-    // status[0]) -> check: everything again into the set's fallback storage if c_f < L, else an
-    // empty launch of one slice per resident wave; all on the device
+    // status[0]), and nothing else: whether c_f reached L is the tail's test, and a run that fell
+    // back is counted again when it is read (plan_recount)
     const rsd::PruneArgs pa = prune_args(p, b, r.lane);
     const int hr = r.cp.carried ? h : h - h0;  // the hypotheses the prefix stage screens
     const rsd::Count32qShape sh1 = shape(hr, p->q_slices);
@@ -504,21 +516,17 @@ static int enqueue_count(rs_f8_plan *p, RunBufs &b, const Run &r) {
     HIP_TRY(rsd::launch_f8_count32q(rsd::kCountPrefix, ca, sh1, 0, pa, ms));
     ca.H = hr;
     HIP_TRY(rsd::launch_f8_count32q(rsd::kCountRest, ca, sh1, p->q_waves, pa, ms));
-    if (r.cp.carried) {
-      ca.H = h;
-      ca.counts = b.d_counts_fb;
-      ca.gdone = b.d_gdone_fb;
-      ca.status = b.d_fbw;
-      HIP_TRY(rsd::launch_f8_count32q(rsd::kCountCheck, ca, shape(h, 1), 0, pa, ms));
-      ++p->n_carried;
-    }
+    p->count_launches = r.cp.carried ? 2 : 3;
+    if (r.cp.carried) ++p->n_carried;
   } else if (r.fp32) {
     // fused c*: the chunk that completes a hypothesis group folds its max into status[0]
     HIP_TRY(rsd::launch_f8_count32q(rsd::kCountWhole, ca, shape(h, p->q_slices), 0, {}, ms));
+    p->count_launches = 1;
   } else {
     HIP_TRY(rsd::launch_f8_count(p->d_pts, n, h, b.d_F, p->ld, f8::choose_chunk(p->n, h),
                                  r.thresh * r.thresh, b.d_counts, ms));
     HIP_TRY(rsd::launch_f8_max(b.d_counts, h, b.d_status, ms));
+    p->count_launches = 2;  // the float64 count and its c*
   }
   if (r.tl >= 1) HIP_TRY(hipEventRecord(r.ev[1], ms));
   if (r.tl >= 1 && p->s.overlap) p->excl[1 - r.lane] = r.ev[1];
@@ -557,6 +565,33 @@ static rsd::TailArgs tail_args(const rs_f8_plan *p, const RunBufs &b, const Run 
   return ta;
 }
 
+// The last run, complete on both lanes, fell back and is about to be read: every hypothesis over
+// the whole window into the set's fallback storage, then the run's tail a second time, which takes
+// c*, the counts and max_count_fast from there (TailArgs::recount), fills the pinned slot and
+// leaves the true c* in the lane's carry word.  Nothing else is in flight (plan_flush); the
+// storage is zeroed here and not per run, so a run that did not fall back never touches it.
+static int plan_recount(rs_f8_plan *p) {
+  const RunBufs &b = p->last();
+  const int lane = p->s.last_lane, h = static_cast<int>(p->last_H);
+  hipStream_t ms = lane_stream(p, lane);
+  HIP_TRY(hipMemsetAsync(b.d_counts_fb, 0, sizeof(int) * p->ld, ms));
+  HIP_TRY(hipMemsetAsync(b.d_gdone_fb, 0, sizeof(int) * (p->ld / 64), ms));
+  HIP_TRY(hipMemsetAsync(b.d_fbw, 0, sizeof(int), ms));
+  rsd::CountArgs ca = count_args(p, b, h);
+  ca.counts = b.d_counts_fb;
+  ca.gdone = b.d_gdone_fb;
+  ca.status = b.d_fbw;
+  const rsd::Count32qShape sh =
+      rsd::count32q_shape(static_cast<int>(p->n), h, p->q_waves, p->q_slices);
+  HIP_TRY(rsd::launch_f8_count32q(rsd::kCountWhole, ca, sh, 0, {}, ms));
+  rsd::TailArgs ta = p->tail[lane];  // the last run's (its lane has had no run since)
+  ta.recount = 1;
+  HIP_TRY(rsd::launch_f8_tail_solve(&ta, nullptr, ms));
+  HIP_TRY(hipStreamSynchronize(ms));
+  ++p->n_recounts;
+  return RS_OK;
+}
+
 // One run.  dev_tuples: tuple mode with the tuples already written (in range, by the GPU
 // parity stream) into the buffer set this run uses, so there is no host copy or check.
 static int plan_run(rs_f8_plan *p, int64_t H, int32_t mode, uint64_t seed, uint64_t hyp_offset,
@@ -580,6 +615,7 @@ static int plan_run(rs_f8_plan *p, int64_t H, int32_t mode, uint64_t seed, uint6
   f8::carry_left(p->s, r.lane, H, thresh, r.fp32);
   f8::committed(p->s, r.lane);
   p->last_H = H;
+  p->unread_dropped = false;
   return RS_OK;
 }
 
@@ -661,7 +697,10 @@ extern "C" int rs_f8_plan_run_np(rs_f8_plan *p, int64_t H, uint32_t *key, int32_
 // set synchronously.
 static int plan_wait(rs_f8_plan *p) {
   if (p->s.runs == 0) return fail(RS_EINVAL, "no run has been issued on this plan");
-  return p->s.pending ? plan_flush(p) : RS_OK;
+  if (p->s.pending) return plan_flush(p, f8::FlushFor::kRead);
+  if (p->unread_dropped)
+    return fail(RS_EINVAL, "the last run fell back and its results were dropped before they were read");
+  return RS_OK;
 }
 
 extern "C" int rs_f8_plan_result(rs_f8_plan *p, rs_f8_result *out, int64_t *inliers, int64_t cap,
@@ -747,8 +786,8 @@ extern "C" int rs_f8_plan_candidates(rs_f8_plan *p, rs_f8_candidate *out, int64_
   return RS_OK;
 }
 
-// Whether the last run (complete: after plan_wait) was carried and fell back, by the test the
-// check stage and the tail made on the device (carry_fell_back in f8_kernels.hip)
+// Whether the last run (complete and, if so, recounted: after plan_wait) was carried and fell
+// back, by the test the tail made on the device (carry_fell_back in f8_kernels.hip)
 static int last_fell_back(rs_f8_plan *p, bool *fb) {
   const RunBufs &b = p->last();
   *fb = false;
@@ -773,7 +812,7 @@ extern "C" int rs_f8_plan_counts(rs_f8_plan *p, int32_t *counts, int64_t H) {
   bool fb = false;
   if ((st = last_fell_back(p, &fb))) return st;
   if (fb) {
-    src = b.d_counts_fb;  // the check stage counted every hypothesis in full
+    src = b.d_counts_fb;  // the recount counted every hypothesis in full
   } else if (b.staged && pw[2] < (n + 7) / 8 * 8) {
     // a pruned run leaves prefix upper bounds for the hypotheses it dropped: the full counts come
     // from the whole-window kernel over the run's models, still in the buffer set (a
@@ -819,6 +858,13 @@ extern "C" int rs_f8_plan_carry_stats(rs_f8_plan *p, int64_t *out) {
   out[1] = nfb;
   out[2] = p->last().carried ? 1 : 0;
   out[3] = fb ? 1 : 0;
+  return RS_OK;
+}
+
+extern "C" int rs_f8_plan_recount_stats(rs_f8_plan *p, int64_t *out) {
+  if (!p || !out) return fail(RS_EINVAL, "null pointer");
+  out[0] = p->n_recounts;
+  out[1] = p->count_launches;
   return RS_OK;
 }
 
@@ -893,7 +939,7 @@ extern "C" int rs_f8_plan_kernel_avg(rs_f8_plan *p, int64_t last_n, double *scor
 
 extern "C" int rs_f8_plan_set_count_precision(rs_f8_plan *p, int32_t fp64) {
   if (!p) return fail(RS_EINVAL, "null plan");
-  int st = plan_flush(p);  // runs in flight use the current kernel's buffers
+  int st = plan_flush(p, f8::FlushFor::kDrop);  // runs in flight use the current kernel's buffers
   if (st) return st;
   p->use_fp32 = fp64 == 0;
   f8::carry_drop(p->s);

@@ -36,8 +36,9 @@ struct RunBufs {
   int *d_surv = nullptr;
   int *d_gdone_b = nullptr;
   bool staged = false;
-  // carried run (no sample; L from the lane's carry word): the check stage's counts, per-group
-  // finish counters and c* word; carried: the set's last run was such a run
+  // carried run (no sample; L from the lane's carry word): the fallback storage, which the recount
+  // of a run that fell back zeroes and fills (counts, per-group finish counters, c* word);
+  // carried: the set's last run was such a run
   int *d_counts_fb = nullptr;
   int *d_gdone_fb = nullptr;
   int *d_fbw = nullptr;
@@ -229,8 +230,8 @@ inline int env_int(const char *name, int dflt) {
 // for come from n unless given (profiles/prune/ab.txt; swept again for the screening prefix stage,
 // profiles/screen/ab.txt).  Carried bound (pruning on): a run on a lane whose previous run had the
 // same H and threshold over the same points takes L = (that run's c*, left in d_carry[lane] by its
-// tail) - g, g = max(kCarryGapMin, n / kCarryGapDiv), instead of a sample's; no sample stage, a
-// check stage that counts everything again only if the bound turned out to be above c* (above
+// tail) - g, g = max(kCarryGapMin, n / kCarryGapDiv), instead of a sample's; no sample stage; if
+// the bound turned out to be above c* the run is counted again when it is read (flush_recounts; above
 // k_f8_count32q, "Carried bound").  profiles/carry/ab.txt, C2, two rounds, bench value in 1e9
 // hypotheses/s: g = n/50 / n/25 / n/16 / n/10 gave 1.705-1.713 / 1.647-1.671 / 1.628-1.641 /
 // 1.558-1.575, no fallback in 298 carried runs at any of them, hence n / 50.  The floor is for small
@@ -284,6 +285,27 @@ inline void carry_left(Sched &s, int lane, int64_t H, double thresh, bool fp32) 
   s.carry_H = H;
   s.carry_thresh = thresh;
   s.carry_ok[lane] = true;
+}
+
+// Deferred recount (f8_kernels.hip above k_f8_count32q, "Carried bound").  The tail of a carried run
+// that fell back selects nothing and marks the run's pinned header; the run is counted again only
+// if it is read.  Only the last run before a flush can be read, so the decision is taken in
+// plan_flush, after both lanes are drained (the header is final then), from host state and that
+// flag alone.  pending: a run has been issued since the last flush (nothing pending: nothing new to
+// read, and a run recounted at an earlier flush is not recounted again); last_carried: the last
+// issued run was a carried one (no other tail sets the flag: a stale word in a slot is not
+// trusted); header_fell_back: the flag of that run's slot; why: what the flush serves.
+enum class FlushFor {
+  kRead,  // an accessor of the last run (plan_wait)
+  kDrop,  // set_points, a retarget, set_count_precision, destroy: the results are dropped
+};
+inline bool flush_recounts(bool pending, bool last_carried, bool header_fell_back, FlushFor why) {
+  return pending && last_carried && header_fell_back && why == FlushFor::kRead;
+}
+// ... and whether that flush leaves the last run without a result: it fell back and was dropped
+// unread.  The accessors refuse such a run until the next one is issued.
+inline bool flush_drops_unread(bool pending, bool last_carried, bool header_fell_back, FlushFor why) {
+  return pending && last_carried && header_fell_back && why == FlushFor::kDrop;
 }
 
 // The pruned count's numbers: the margin m = max(16, n / 30) and the least skip n / 8 (at least

@@ -31,7 +31,9 @@ constexpr int kStatusWords = 4 + kSelectBlocks;
 constexpr int kPruneWords = 4;  // [0] cA (max count when K = npad), [1] survivors, [2] K, [3] L
 
 // Result header of one F run, written by the tail into the run's pinned host slot (through the
-// host mapping); S_RANSAC, n_inliers ints, goes to the slot's pinned list beside it.
+// host mapping); S_RANSAC, n_inliers ints, goes to the slot's pinned list beside it.  The tail of a
+// carried run that fell back selects nothing: it sets fell_back and leaves the other fields as they
+// were (f8_plan.hip recounts such a run at the flush that reads it); every other tail clears it.
 struct F8DevResult {
   double F[9];
   int64_t best_index;
@@ -42,6 +44,7 @@ struct F8DevResult {
   int64_t n_candidates;
   int64_t guard_mismatch;
   int64_t n_inliers;
+  int64_t fell_back;
 };
 
 }  // namespace rsd

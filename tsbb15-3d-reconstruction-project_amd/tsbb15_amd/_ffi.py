@@ -141,6 +141,7 @@ _SIGS = {
     "rs_f8_plan_lane_waits": (C.c_int, [C.c_void_p, _i64p]),
     "rs_f8_plan_prune_stats": (C.c_int, [C.c_void_p, _i64p]),
     "rs_f8_plan_carry_stats": (C.c_int, [C.c_void_p, _i64p]),
+    "rs_f8_plan_recount_stats": (C.c_int, [C.c_void_p, _i64p]),
     "rs_f8_plan_stage_counts": (C.c_int, [C.c_void_p, _i32p, C.c_int64]),
     "rs_f8_plan_set_count_precision": (C.c_int, [C.c_void_p, C.c_int32]),
     "rs_f8_ransac_np": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64, _u32p, _i32p,
@@ -774,6 +775,13 @@ class F8Plan:
         check(lib().rs_f8_plan_carry_stats(self._h, out))
         return {"carried": out[0], "fallbacks": out[1], "last_carried": bool(out[2]),
                 "last_fell_back": bool(out[3])}
+
+    def recount_stats(self):
+        """(fallen-back runs counted again when they were read, since the plan was created; kernel
+        launches the last run enqueued for its count).  Host state: waits for nothing."""
+        out = (C.c_int64 * 2)()
+        check(lib().rs_f8_plan_recount_stats(self._h, out))
+        return out[0], out[1]
 
     def kernel_ms(self, last_n=1):
         """Device times of the last run, or averaged over the last ``last_n`` runs."""
