@@ -1360,6 +1360,79 @@ int rs_mesh_smooth(rs_ctx *ctx, const double *vertices, int64_t nv, const int32_
 int rs_mesh_timing(rs_ctx *ctx, int32_t enable, double *ms);
 
 /* ------------------------------------------------------------------------------------------
+ * Mesh simplification (simplify.hip): vertex clustering on a uniform grid, the representative of
+ * a cell placed by the cell's accumulated error quadric (Lindstrom 2000).  The reference project
+ * has no such code; nothing here restates code of it.  The mesh is the index mesh of the calls
+ * above, with their limits.  Everything is fp64 in plain IEEE operations, no product fused with
+ * a sum, and every sum has a stated order, so two calls give the same bits and
+ * tests/simplify_ref.py restates them to the bit; it is also where the order of the operations
+ * of step 5 is written out.
+ *   1 Cells.  i_a = floor((x_a - origin_a) / cell) per axis a, compared as a double; every i_a
+ *     must lie in 0..dims_a - 1.  key = (i_2 dims_1 + i_1) dims_0 + i_0.  A vertex on a cell face
+ *     belongs to the upper cell.
+ *   2 Clusters.  A cell that holds a vertex, named by a face or not, is a cluster; clusters are
+ *     numbered in ascending key order.  vmap[v] is the cluster of v.
+ *   3 Mean.  m = the sum of the cluster's vertices in ascending vertex index, from the first
+ *     term, left to right, divided by their number.
+ *   4 Quadric.  Face f = (a, b, c) has n = (x_b - x_a) x (x_c - x_a), not normalised, and
+ *     d = -(n . x_a).  It contributes once to every distinct cluster among its three corners,
+ *     whatever becomes of it in step 6.  A cluster's ten numbers, in this order, are
+ *     n0 n0, n0 n1, n0 n2, n1 n1, n1 n2, n2 n2 (A), n0 d, n1 d, n2 d (b) and d d, each summed
+ *     over its faces in ascending face index from the first term; all 0 without a face.
+ *   5 Position.  x = m for placement 0.  For placement 1 A is diagonalised by cyclic Jacobi
+ *     (at most 30 sweeps; eigenvalues l_i on the diagonal, eigenvectors v_i in columns 0, 1, 2
+ *     as the sweeps leave them), L = max l_i.  Unless L > 0, x = m.  Otherwise
+ *     r = (-b) - A m and x = m + sum g_i v_i over the i with l_i > rank_tol L, in the order
+ *     i = 0, 1, 2, g_i = (v_i . r) / l_i.  x is accepted when its coordinates are finite and
+ *     floor((x_a - origin_a) / cell) is the cell's i_a on every axis; otherwise x = m and the
+ *     cluster is a fall-back.
+ *   6 Faces.  The corners go through vmap.  A face with two equal clusters is degenerate and
+ *     dropped.  Of the remaining faces with the same set of three clusters, in any rotation and
+ *     either orientation, the one of lowest index stays.  The survivors keep their order and
+ *     their corner order.  fmap[f] is the output index, -1 (degenerate) or -2 (duplicate).
+ * Clusters that no surviving face names are kept.
+ *   vertices_out is (v_cap, 3) and faces_out (f_cap, 3), the capacity protocol of
+ * rs_mesh_compact: *nv_out and *nf_out are always set, to 0 on an argument error; RS_EINVAL and
+ * no output byte written (vmap, fmap, quadrics_out and info included) when a capacity is too
+ * small.  vmap is (nv) and fmap (nf) int32; quadrics_out (clusters, 10) fp64 within v_cap rows,
+ * or null.  nv = 0 and nf = 0 are valid.
+ *   RS_EINVAL before any launch, nothing written: what the mesh calls above list, a vertex
+ * coordinate or origin not finite, cell not finite or not positive, a dim below 1, more than
+ * RS_SIMPLIFY_MAX_CELLS cells, placement outside 0..1, rank_tol outside [0, 1) or NaN, a vertex
+ * outside the grid, a negative capacity or a null array of non-zero capacity.
+ *   Method: three times "items grouped by bucket, each bucket ascending" -- vertices by cluster,
+ * face corners by cluster, faces by their smallest cluster -- each as count, exclusive scan,
+ * scatter through an integer cursor and a sort of each row in place by one lane, which removes
+ * the cursor's order.  Atomics are integer only; no kernel waits for another lane. */
+#define RS_SIMPLIFY_MAX_CELLS (1LL << 27)
+#define RS_SIMPLIFY_MEAN 0
+#define RS_SIMPLIFY_QUADRIC 1
+
+typedef struct rs_simplify_info {
+  int64_t clusters;         /* = *nv_out                                                    */
+  int64_t fallbacks;        /* clusters whose quadric position was rejected in step 5       */
+  int64_t degenerate_faces; /* fmap == -1                                                   */
+  int64_t duplicate_faces;  /* fmap == -2                                                   */
+  int64_t longest_row;      /* the most items one lane sorted: vertices of a cluster, face
+                               corners of a cluster, or faces that share a smallest cluster */
+} rs_simplify_info;
+
+int rs_mesh_simplify(rs_ctx *ctx, const double *vertices, int64_t nv, const int32_t *faces,
+                     int64_t nf, const double *origin, double cell, const int64_t *dims,
+                     int32_t placement, double rank_tol, double *vertices_out, int64_t v_cap,
+                     int32_t *faces_out, int64_t f_cap, int32_t *vmap, int32_t *fmap,
+                     double *quadrics_out, int64_t *nv_out, int64_t *nf_out,
+                     rs_simplify_info *info);
+
+/* HIP events between the stages of the next rs_mesh_simplify calls (enable != 0).  Returns the
+ * last timed call's device ms: slot 0 cluster (keys, occupancy scan, vmap), 1 rows (the vertex
+ * and corner rows and the means), 2 quadric (sums and solve), 3 faces (classification, the
+ * duplicate rows, scan and emit); -1 where none (tools/bench_simplify.py).  rs_mesh_timing does
+ * not see these calls. */
+#define RS_SIMPLIFY_TIMING_SLOTS 4
+int rs_simplify_timing(rs_ctx *ctx, int32_t enable, double *ms);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU (RCCL over xGMI).  One process per GPU; the unique id travels out of band.
  * ---------------------------------------------------------------------------------------- */
 #define RS_COMM_ID_BYTES 128

@@ -131,6 +131,7 @@ extern "C" int rs_ctx_destroy(rs_ctx *c) {
   c->texture.destroy();
   c->eval.destroy();
   c->mesh.destroy();
+  c->simplify.destroy();
   if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;

@@ -37,6 +37,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "device_math.h"
 #include "host.h"
 
 namespace rsd {
@@ -71,46 +72,6 @@ __device__ __forceinline__ unsigned long long cloud_hash(unsigned long long k) {
   k *= 0xc4ceb9fe1a85ec53ULL;
   k ^= k >> 33;
   return k;
-}
-
-// Cyclic Jacobi on a symmetric 3 x 3 matrix (row-major; destroyed): eigenvalues on the diagonal
-// of A, eigenvectors in the columns of V.  Stops when the off-diagonal mass is below 1e-30 of
-// the diagonal's (squared), after at most 30 sweeps.
-__device__ __forceinline__ void cloud_jacobi3(double (&A)[9], double (&V)[9]) {
-#pragma unroll
-  for (int i = 0; i < 9; ++i) V[i] = (i % 4 == 0) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    const double off = A[1] * A[1] + A[2] * A[2] + A[5] * A[5];
-    const double dia = A[0] * A[0] + A[4] * A[4] + A[8] * A[8];
-    if (!(off > 1e-30 * dia)) break;
-#pragma unroll
-    for (int pq = 0; pq < 3; ++pq) {
-      const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
-      const double apq = A[p * 3 + q];
-      if (apq == 0.0) continue;
-      const double th = (A[q * 3 + q] - A[p * 3 + p]) / (2.0 * apq);
-      const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
-      const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {  // columns p, q
-        const double akp = A[k * 3 + p], akq = A[k * 3 + q];
-        A[k * 3 + p] = c * akp - s * akq;
-        A[k * 3 + q] = s * akp + c * akq;
-      }
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {  // rows p, q
-        const double apk = A[p * 3 + k], aqk = A[q * 3 + k];
-        A[p * 3 + k] = c * apk - s * aqk;
-        A[q * 3 + k] = s * apk + c * aqk;
-      }
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const double vkp = V[k * 3 + p], vkq = V[k * 3 + q];
-        V[k * 3 + p] = c * vkp - s * vkq;
-        V[k * 3 + q] = s * vkp + c * vkq;
-      }
-    }
-  }
 }
 
 // Per-axis minimum over the points whose three coordinates are finite; +inf where a workgroup
@@ -400,7 +361,7 @@ __global__ __launch_bounds__(kCloudWave) void k_cloud_normals(const double *pts,
     A[4] = S[3] * ik - m1 * m1;
     A[5] = A[7] = S[4] * ik - m1 * m2;
     A[8] = S[5] * ik - m2 * m2;
-    cloud_jacobi3(A, V);
+    jacobi3(A, V);
     // ascending eigenvalues; equal ones keep their column order
     int o0 = 0, o1 = 1, o2 = 2;
     if (A[4 * o1] < A[4 * o0]) { const int w = o0; o0 = o1; o1 = w; }

@@ -408,4 +408,19 @@ __device__ __forceinline__ void residuals_ref(const double (&f)[9], const Pt &p,
   r2 = ((l20 * p.x2 + l21 * p.y2) + l22) / sqrt(l20 * l20 + l21 * l21);
 }
 
+// Cyclic Jacobi on a symmetric 3 x 3 matrix (row-major; destroyed): eigenvalues on the diagonal
+// of A, eigenvectors in the columns of V.  Stops when the off-diagonal mass is below 1e-30 of
+// the diagonal's (squared), after at most 30 sweeps.  jacobi3 is compiled with the translation
+// unit's contraction (the point-cloud normals, whose bits predate the second user);
+// jacobi3_exact fuses no product with a sum, so that a restatement in plain IEEE operations
+// (tests/simplify_ref.py) gives the same bits.  Both are the statements of jacobi3_body.h.
+__device__ __forceinline__ void jacobi3(double (&A)[9], double (&V)[9]) {
+#include "jacobi3_body.h"
+}
+
+__device__ __forceinline__ void jacobi3_exact(double (&A)[9], double (&V)[9]) {
+#pragma clang fp contract(off)
+#include "jacobi3_body.h"
+}
+
 }  // namespace rsd

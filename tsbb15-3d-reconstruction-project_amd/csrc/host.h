@@ -134,6 +134,9 @@ struct rs_ctx {
   // rs_mesh_timing: around the kernels of the next mesh clean-up calls (mesh.hip): components,
   // compact, adjacency, smooth
   rs::StageTimer<3, RS_MESH_TIMING_SLOTS> mesh{-1.0};
+  // rs_simplify_timing: between the stages of the next rs_mesh_simplify calls (simplify.hip):
+  // cluster, rows, quadric, faces
+  rs::StageTimer<5, RS_SIMPLIFY_TIMING_SLOTS> simplify{-1.0};
 };
 
 namespace rs {
@@ -247,5 +250,10 @@ void dense_sweep_launch(hipStream_t s, const uint8_t *ref, const uint8_t *src, i
                         const double *depths, int64_t D, int32_t patch, double min_var,
                         int32_t *index, float *delta, float *score, uint8_t *nvalid,
                         float *volume);
+// The argument rules the mesh calls share (RS_EINVAL with a message, else RS_OK) and the exclusive
+// scan of the int32 v[0 .. n) in place on stream s, n >= 1, the total in v[n]; sums is scratch of
+// blocks(n, RS_MESH_SCAN_CHUNK) + 1 items (mesh.hip).
+int mesh_check(const rs_ctx *c, const int32_t *faces, int64_t nf, int64_t nv);
+void mesh_scan(hipStream_t s, int32_t *v, int64_t n, int32_t *sums);
 int fmatrix_stls_lsq(rs_ctx *c, const double *pl, const double *pr, int64_t n, double *F_out);
 }  // namespace rs

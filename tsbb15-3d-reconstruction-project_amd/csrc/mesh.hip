@@ -388,12 +388,12 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_smooth_pass(
 
 }  // namespace rsd
 
-namespace {
-
 static_assert(RS_MESH_TIMING_SLOTS == 4, "components, compact, adjacency, smooth");
 static_assert(6 * RS_MESH_MAX_FACES <= INT32_MAX, "the adjacency offsets are int32");
 
-// the argument rules all three calls share
+namespace rs {
+
+// the argument rules every mesh call shares (rs_mesh_simplify of simplify.hip too)
 int mesh_check(const rs_ctx *c, const int32_t *faces, int64_t nf, int64_t nv) {
   if (!c) return fail(RS_EINVAL, "null pointer");
   if (nv < 0 || nf < 0) return fail(RS_EINVAL, "negative size");
@@ -415,7 +415,10 @@ void mesh_scan(hipStream_t s, int32_t *v, int64_t n, int32_t *sums) {
   hipLaunchKernelGGL(rsd::k_mesh_scan_add, grid, block, 0, s, v, n, sums, nchunks);
 }
 
-}  // namespace
+}  // namespace rs
+
+using rs::mesh_check;
+using rs::mesh_scan;
 
 extern "C" int rs_mesh_components(rs_ctx *c, const int32_t *faces, int64_t nf, int64_t nv,
                                   int32_t *label, int32_t *size, int64_t *count,

@@ -87,6 +87,12 @@ class EvalInfo(C.Structure):
                 ("tests", C.c_int64), ("faces_skipped", C.c_int64), ("beyond", C.c_int64)]
 
 
+class SimplifyInfo(C.Structure):
+    _fields_ = [("clusters", C.c_int64), ("fallbacks", C.c_int64),
+                ("degenerate_faces", C.c_int64), ("duplicate_faces", C.c_int64),
+                ("longest_row", C.c_int64)]
+
+
 BA_MAX_CAMERAS = 128
 WASH_MAX_TRACK = 128
 CLOUD_MAX_CELLS = 1 << 21
@@ -261,6 +267,11 @@ _SIGS = {
     "rs_mesh_smooth": (C.c_int, [C.c_void_p, _dp, C.c_int64, _i32p, C.c_int64, C.c_int32,
                                  C.c_double, C.c_double, _u8p, C.c_int32, _dp]),
     "rs_mesh_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "rs_mesh_simplify": (C.c_int, [C.c_void_p, _dp, C.c_int64, _i32p, C.c_int64, _dp, C.c_double,
+                                   _i64p, C.c_int32, C.c_double, _dp, C.c_int64, _i32p,
+                                   C.c_int64, _i32p, _i32p, _dp, _i64p, _i64p,
+                                   C.POINTER(SimplifyInfo)]),
+    "rs_simplify_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
     "rs_np_shard_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.POINTER(C.c_void_p)]),
     "rs_np_shard_destroy": (C.c_int, [C.c_void_p]),

@@ -9,7 +9,8 @@ has no such stage and nothing here restates code of it.
   * ``bounds``          origin and dims of a volume that encloses a cloud (host)
   * ``vertex_normals``  area-weighted normals (host)
   * ``save_ply`` / ``load_ply``   binary little-endian PLY (host)
-  * ``reconstruct``     ``dense.fuse`` -> ``integrate`` -> ``extract`` (-> ``vertex_colors``)
+  * ``reconstruct``     ``dense.fuse`` -> ``integrate`` -> ``extract`` (-> ``clean``
+                        -> ``simplify`` -> ``vertex_colors``)
   * ``render_depth``    the mesh rendered into a z-buffer per view (rs_surface_render_depth,
                         surface_texture.hip)
   * ``vertex_colors``   a colour per vertex from the views that see it (rs_surface_colorize)
@@ -18,6 +19,8 @@ has no such stage and nothing here restates code of it.
   * ``remove_small``    ``components``, a policy on the host, ``compact``: floaters go
   * ``smooth``          Taubin's lambda|mu smoothing (rs_mesh_smooth)
   * ``clean``           ``remove_small`` -> ``smooth``
+  * ``simplify``        vertex clustering on a grid, quadric placement (rs_mesh_simplify,
+                        simplify.hip)
 
 Conventions are those of ``dense``: cameras are the project's normalised (3, 4) ``C``,
 ``P = K @ C``, pixel centres at integers, the depth of X in a view is ``C[2] @ [X; 1]`` and may
@@ -47,6 +50,9 @@ MESH_MAX_FACES = 1 << 27     # RS_MESH_MAX_FACES
 MESH_MAX_ROUNDS = 64         # RS_MESH_MAX_ROUNDS
 MESH_MAX_ITERATIONS = 65536  # RS_MESH_MAX_ITERATIONS
 MESH_SCAN_CHUNK = 2048       # RS_MESH_SCAN_CHUNK
+SIMPLIFY_STAGES = ("cluster", "rows", "quadric", "faces")
+SIMPLIFY_PLACEMENTS = ("mean", "quadric")   # RS_SIMPLIFY_MEAN, RS_SIMPLIFY_QUADRIC
+SIMPLIFY_MAX_CELLS = 1 << 27                # RS_SIMPLIFY_MAX_CELLS
 
 
 def _ctx(ctx):
@@ -596,13 +602,115 @@ def clean(vertices, faces, min_faces=None, keep_largest=None, min_fraction=None,
 _clean = clean    # ``reconstruct`` has a keyword of that name
 
 
+def simplify_grid(vertices, cell, origin=None):
+    """The grid ``simplify`` clusters on: (origin (3,) float64, dims (d0, d1, d2) along x, y, z).
+    With ``origin=None`` the origin is the per-axis minimum of the vertices;
+    ``dims = floor((max - origin) / cell) + 1``, so the largest coordinate lies in the last cell.
+    An empty mesh gets the origin 0 and one cell.  ValueError: vertices not (Nv, 3) or not finite,
+    cell not finite or not positive, origin not three finite numbers, more than 2^27 cells."""
+    vertices = _ffi.f64c(vertices)
+    if vertices.ndim != 2 or vertices.shape[1] != 3:
+        raise ValueError('vertices must be (Nv, 3)')
+    if not np.all(np.isfinite(vertices)):
+        raise ValueError('the vertices must be finite')
+    cell = float(cell)
+    if not np.isfinite(cell) or not cell > 0.0:
+        raise ValueError('cell must be finite and positive')
+    if origin is None:
+        origin = vertices.min(axis=0) if len(vertices) else np.zeros(3)
+    origin = _ffi.f64c(origin).reshape(-1)
+    if origin.shape != (3,) or not np.all(np.isfinite(origin)):
+        raise ValueError('origin must be three finite numbers')
+    if not len(vertices):
+        return origin, (1, 1, 1)
+    top = np.floor((vertices.max(axis=0) - origin) / cell)
+    if np.any(top < 0.0):
+        raise ValueError('a vertex lies outside the grid')
+    if np.any(top >= SIMPLIFY_MAX_CELLS) or np.prod(top + 1.0) > SIMPLIFY_MAX_CELLS:
+        raise ValueError('a grid of more than 2^27 cells')
+    return origin, tuple(int(t) + 1 for t in top)
+
+
+def simplify(vertices, faces, cell, origin=None, placement="quadric", rank_tol=1e-3,
+             drop_unreferenced=True, return_info=False, ctx=None):
+    """Vertex clustering on a uniform grid of spacing ``cell`` (rs_mesh_simplify): all vertices
+    of a cell become one vertex, placed by the cell's error quadric (Lindstrom 2000).
+
+    The grid is ``simplify_grid``'s.  A vertex belongs to cell ``floor((x - origin) / cell)``
+    per axis, a vertex on a cell face to the upper cell; occupied cells are numbered in ascending
+    order of ``(i2 * d1 + i1) * d0 + i0``.  ``placement="mean"`` puts the new vertex at the mean
+    of the cell's vertices.  ``"quadric"`` accumulates, over the faces with a corner in the cell,
+    the squared distance to their planes weighted by squared area and moves the mean to its
+    minimum within the eigenvectors whose eigenvalue exceeds ``rank_tol`` times the largest; a
+    position that is not finite or leaves the cell falls back to the mean.  A face two of whose
+    corners share a cell is dropped, and of the faces with the same three cells the first stays;
+    the others keep their order and orientation.  Every new vertex lies in the cell of the
+    vertices it replaces, so no vertex moves further than ``cell`` along an axis.  All fp64 with
+    every sum in a stated order (include/rsamd.h): bitwise reproducible.
+
+    Returns (vertices (Nc, 3) float64, faces (Nk, 3) int32, vmap (Nv,) int32: the new index of
+    an input vertex).  With ``drop_unreferenced`` the new vertices that no remaining face names
+    are removed with ``compact`` and vmap is -1 for the input vertices they stood for.  With
+    ``return_info`` a fourth item: a dict of ``clusters`` (occupied cells), ``fallbacks``,
+    ``degenerate_faces``, ``duplicate_faces``, ``longest_row`` (the most items one lane sorted),
+    ``unreferenced`` (occupied cells no remaining face names), ``fmap`` ((Nf,) int32: the new
+    index of an input face, -1 for a degenerate face, -2 for a duplicate) and ``quadrics``
+    ((Nc, 10) float64 of the returned vertices).
+
+    ValueError before any launch: what ``simplify_grid`` and ``components`` list, a vertex
+    outside the grid of a given ``origin``, placement not "mean" or "quadric", rank_tol outside
+    [0, 1)."""
+    vertices = _ffi.f64c(vertices)
+    origin, dims = simplify_grid(vertices, cell, origin)
+    n = len(vertices)
+    faces = _index_mesh(faces, n)
+    if placement not in SIMPLIFY_PLACEMENTS:
+        raise ValueError('placement must be "mean" or "quadric"')
+    cell, rank_tol = float(cell), float(rank_tol)
+    if not 0.0 <= rank_tol < 1.0:
+        raise ValueError('rank_tol must be in [0, 1)')
+    m = len(faces)
+    # the result is never larger than the input: one call with the input's sizes as capacities
+    vout, fout = np.empty((n, 3)), np.empty((m, 3), np.int32)
+    vmap, fmap = np.empty(n, np.int32), np.empty(m, np.int32)
+    quad = np.empty((n, 10))
+    nv, nf = _ffi.C.c_int64(0), _ffi.C.c_int64(0)
+    rec = _ffi.SimplifyInfo()
+    d = np.array(dims, dtype=np.int64)
+    _ffi.check(_ffi.lib().rs_mesh_simplify(
+        _ctx(ctx), _ffi.ptr(vertices, _d) if n else None, n,
+        _ffi.ptr(faces, _i32) if m else None, m, _ffi.ptr(origin, _d), cell,
+        _ffi.ptr(d, _ffi.C.c_int64), SIMPLIFY_PLACEMENTS.index(placement), rank_tol,
+        _ffi.ptr(vout, _d) if n else None, n, _ffi.ptr(fout, _i32) if m else None, m,
+        _ffi.ptr(vmap, _i32) if n else None, _ffi.ptr(fmap, _i32) if m else None,
+        _ffi.ptr(quad, _d) if n else None, _ffi.C.byref(nv), _ffi.C.byref(nf),
+        _ffi.C.byref(rec)))
+    vout, fout, quad = vout[:nv.value].copy(), fout[:nf.value].copy(), quad[:nv.value].copy()
+    keep = np.zeros(len(vout), np.uint8)
+    keep[fout.reshape(-1)] = 1
+    unreferenced = int(len(keep) - keep.sum())
+    if drop_unreferenced and unreferenced:
+        vout, fout, cmap = compact(vout, fout, keep, ctx=ctx)
+        vmap, quad = cmap[vmap], quad[keep != 0]
+    if not return_info:
+        return vout, fout, vmap
+    info = {k: int(getattr(rec, k)) for k, _ in _ffi.SimplifyInfo._fields_}
+    info.update(unreferenced=unreferenced, fmap=fmap, quadrics=quad)
+    return vout, fout, vmap, info
+
+
+_simplify = simplify    # ``reconstruct`` has a keyword of that name
+
+
 def reconstruct(images, cams, K, depths, origin, voxel, dims, trunc, min_weight=2, ctx=None,
-                colors=False, clean=None, **fuse_kw):
+                colors=False, clean=None, simplify=None, **fuse_kw):
     """Posed images to a mesh: ``dense.fuse(..., return_maps=True)``, the depth set to NaN where
     ``keep`` is false, ``integrate`` with ``count`` as the weight, ``extract``.  ``fuse_kw`` goes
     to ``dense.fuse``: ``smooth=(p1, p2)`` there picks the depth maps' winners after semi-global
     aggregation.  ``clean``, a dict of the keywords of ``clean``, applies that function to the
-    extracted mesh before anything else uses it; with None the mesh is ``extract``'s.  Returns
+    extracted mesh before anything else uses it; with None the mesh is ``extract``'s.
+    ``simplify``, a dict of the keywords of ``simplify`` (``cell`` at least), applies that
+    function after ``clean`` and before the colours; with None nothing changes.  Returns
     (vertices, faces, tsdf, weight), and with ``colors=True``
     (vertices, faces, tsdf, weight, colors): the first item of ``vertex_colors`` on the same
     images, with the mesh's ``vertex_normals``."""
@@ -614,6 +722,9 @@ def reconstruct(images, cams, K, depths, origin, voxel, dims, trunc, min_weight=
     vertices, faces = extract(tsdf, weight, origin, voxel, min_weight=min_weight, ctx=ctx)
     if clean is not None:
         vertices, faces, _ = _clean(vertices, faces, ctx=ctx, **dict(clean))
+    if simplify is not None:
+        vertices, faces = _simplify(vertices, faces, ctx=ctx,
+                                    **dict(simplify, return_info=False))[:2]
     if not colors:
         return vertices, faces, tsdf, weight
     col = vertex_colors(vertices, faces, images, cams, K,
@@ -638,6 +749,16 @@ def mesh_timing(enable, ctx=None):
     ms = np.zeros(len(MESH_STAGES))
     _ffi.check(_ffi.lib().rs_mesh_timing(ctx.handle, int(enable), _ffi.ptr(ms, _d)))
     return dict(zip(MESH_STAGES, ms.tolist()))
+
+
+def simplify_timing(enable, ctx=None):
+    """The same for the next ``simplify`` calls (rs_simplify_timing): {cluster, rows, quadric,
+    faces: device ms}, -1 where none.  ``mesh_timing`` does not see these calls, nor this one the
+    ``compact`` that ``drop_unreferenced`` runs."""
+    ctx = ctx or _ffi.default_context()
+    ms = np.zeros(len(SIMPLIFY_STAGES))
+    _ffi.check(_ffi.lib().rs_simplify_timing(ctx.handle, int(enable), _ffi.ptr(ms, _d)))
+    return dict(zip(SIMPLIFY_STAGES, ms.tolist()))
 
 
 def texture_timing(enable, ctx=None):
