@@ -278,6 +278,19 @@ int rs_f8_plan_carry_stats(rs_f8_plan *plan, int64_t out[4]);
  * kernel launches the last run enqueued for its count: 3 with a sample (sample, prefix, rest), 2
  * for a carried run, 1 unpruned, 2 for the float64 kernel and its maximum}.  Host state: no wait. */
 int rs_f8_plan_recount_stats(rs_f8_plan *plan, int64_t out[2]);
+/* Point order of the pruned count (RSAMD_ORDER=0 turns it off).  A count is a sum over the points
+ * and the pruned count's drop rule holds for any fixed order of them, so the counting stages may
+ * read the points in an order of the plan's own: the points that a previous run's winner rejected
+ * first, where a hypothesis survives the screen only if it finds its inliers among them.  The
+ * order is installed once per rs_f8_plan_set_points, inside the first of rs_f8_plan_result and the
+ * accessors that completes a run after more than one run has been issued on the resident points
+ * (one small upload and one small kernel there; a plan with one run per rs_f8_plan_set_points never
+ * installs one); rs_f8_plan_set_points and a new population drop it.  Runs that read the ordered
+ * copy screen with the margin max(16, n / 60) unless RSAMD_PRUNE_MARGIN is set.  Results are those of the
+ * caller's order, bit for bit; only the stages' own counts of dropped hypotheses
+ * (rs_f8_plan_stage_counts) and the survivor count differ.  out = {whether an order is installed,
+ * the points placed first, installs since the plan was created}.  Host state: no wait, no install. */
+int rs_f8_plan_order_stats(rs_f8_plan *plan, int64_t out[3]);
 /* The counting stages' own per-hypothesis counts of the last run, with no recount (test &
  * diagnostics).  After a pruned run: the full count of a sample hypothesis or a survivor, and
  * for a dropped hypothesis K minus its certified outliers among the first K points, an upper

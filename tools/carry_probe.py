@@ -52,6 +52,10 @@ def main():
         rec["recount_stats"] = list(plan.recount_stats())
     except AttributeError:      # a library from before the deferred recount
         rec["recount_stats"] = None
+    try:                        # the point order: installed, points placed first, installs
+        rec["order_stats"] = plan.order_stats()
+    except AttributeError:      # a library from before the point order
+        rec["order_stats"] = None
     plan.close()
     print(json.dumps(rec))
 

@@ -73,6 +73,10 @@ hipError_t set_count_timeline(uint64_t *buf);  // RSAMD_TSTAMP diagnostics (null
 constexpr int kCountTsWords = 6;
 hipError_t launch_pack_points32q(const Pt *pts, int n, const Frame &fr, float4 *ptsq,
                                  hipStream_t s);
+// Both of the count kernel's point arrays gathered through perm, a permutation of [0, n):
+// pts_out[i] = pts[perm[i]] and ptsq the pair layout of pts_out (the plan's point order)
+hipError_t launch_pack_points32q_perm(const Pt *pts, const int *perm, int n, const Frame &fr,
+                                      Pt *pts_out, float4 *ptsq, hipStream_t s);
 struct Count32qShape {
   int64_t per_wave;  // points of the (group, point) plane per wave (a multiple of 8)
   int64_t blocks;    // 256-thread workgroups launched

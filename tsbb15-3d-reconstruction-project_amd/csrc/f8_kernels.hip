@@ -366,6 +366,46 @@ __global__ __launch_bounds__(256) void k_f8_count(const Pt *__restrict__ pts, in
 // sample's L at C2 is within 40 of c* already, so the gain is the launch, not the bound.  C5
 // 2.09-2.13 ms against 2.34-2.36 ms.  The gap g = max(16, n / 50) is from the sweep recorded
 // beside kCarryGapDiv (f8_plan.hip).
+//
+// Point order (RSAMD_ORDER; f8_order.h, f8_plan.hip order_install).  A count is a sum over the
+// points, and the drop rule c' + (n - K) < L - 1 is sound for any fixed order of them: c' bounds
+// the count over whichever K points stand first, n - K is the number of the others.  With the
+// points in the caller's order a hypothesis survives the screen when it finds about m inliers
+// among the first K, and the true inliers are spread evenly, so any half-good model gets through.
+// With the points a previous winner rejected first, it has to find them among points the best
+// model calls outliers.  So the plan keeps a second copy of both arrays the kernel reads (ptsq and
+// the Pt array of the float64 re-test), gathered through one permutation by
+// k_pack_points32q_perm: the indices outside the winner's S_RANSAC ascending, then those inside,
+// NaN padding still at the end ([0, K) holds no padding point).  The kernel is unchanged: it gets
+// other pointers.  Solve, tail, k_f8_count and the accessors keep the caller's order.  Installed
+// on the host at a read flush, both lanes drained, once per set_points and only after more than
+// one run on the points; no event and no host wait on the hot path.
+// Measured (profiles/order/ab.txt, tools/order_ab.sh, the parent commit's library and
+// RSAMD_ORDER=0, five interleaved rounds; tools/order_model.py is the CPU model): the survivors of
+// a C2 run fall from 11 132 to 3 551 of 1e5 (the model: 12.8 % -> 5.2 % of 6 144), and nothing
+// else moves.  Kernel trace of the bench (shortest launch in brackets): prefix 44.9 us (30.8) ->
+// 44.4 us (31.0), rest 28.2 us (21.0) -> 28.1 us (21.8), tail + solve 19.8 -> 19.7 us; bench value
+// at --steps 100 --warmup 200 1.742-1.773e9 -> 1.733-1.764e9 hypotheses/s (RSAMD_ORDER=0:
+// 1.742-1.792e9), at --steps 20 --warmup 5 1.550-1.566e9 -> 1.556-1.574e9: the ranges overlap,
+// the order alone is no gain at C2.  The rest stage cuts its plane into slices of at least 64
+// points, so with 174 survivor groups (5 437 waves) or 56 (1 750 waves) every wave runs one
+// 64-point slice: the launch is its floor of launch, model loads through surv[], ramp and the
+// group-completion atomics (~21 us alone) either way, and the 6 us of VALU issue it lost were not
+// what the other lane's kernels were waiting for.  What the order buys is room in the prefix: with
+// a third of the survivors the margin m can shrink.  Sweep with the order on (session B, bench
+// value in 1e9 hypotheses/s, two rounds): m = 16 / n/60 / n/30 / n/20 / n/15 gave 1.675-1.685 /
+// 1.778-1.812 / 1.728-1.745 / 1.694-1.703 / 1.684-1.701, both n/60 lines above every line of
+// every other arm; 1 / 2 / 3 / 4 slices per resident wave 1.746-1.812 / 1.709-1.714 / 1.667-1.697
+// / 1.513-1.542 (1 and 2 overlap the plain lines, the default stays 2).  So a run that reads the
+// ordered copy takes m = max(16, n / 60) (f8::order_margin; in the caller's order n/60 loses, see
+// the screening prefix's sweep above): K 784 -> 752, survivors 6 386 of 1e5.  Session C, this
+// form, five interleaved rounds: at --steps 100 --warmup 200 parent 1.701-1.753e9, new
+// 1.773-1.805e9 hypotheses/s (medians 1.731 -> 1.785, 1.031 x), RSAMD_ORDER=0 1.715-1.759e9; at
+// --steps 20 --warmup 5 parent 1.498-1.556e9, new 1.583-1.601e9 (1.029 x), RSAMD_ORDER=0
+// 1.525-1.566e9.  Every new line is above every parent line at both flag sets; RSAMD_ORDER=0
+// overlaps the parent's range (its best line 0.4 % above the parent's best).  C5 (lane_probe.py
+// c5, three rounds): 2.120-2.134 -> 2.034-2.057 ms, RSAMD_ORDER=0 2.107-2.122 ms.  Fallbacks,
+// recounts and lane_waits 0 over the 300 runs, two count launches, one install.
 // ----------------------------------------------------------------------------------------
 
 // The float64 test of k_f8_count (pixel units) for one (hypothesis, point).
@@ -794,6 +834,34 @@ __global__ __launch_bounds__(256) void k_pack_points32q(const Pt *__restrict__ p
     return;
   }
   const Pt p = pts[i];
+  const double is = 1.0 / fr.s;
+  o[0] = static_cast<float>((p.x2 - fr.cx2) * is);
+  o[8] = static_cast<float>((p.y2 - fr.cy2) * is);
+  o[16] = static_cast<float>((p.x1 - fr.cx1) * is);
+  o[24] = static_cast<float>((p.y1 - fr.cy1) * is);
+}
+
+// The same through a permutation (the plan's point order, "Point order" above k_f8_count32q):
+// position i of both ordered copies holds the caller's point perm[i] -- the AoS float64 point the
+// re-test reads and its pair-layout floats, by k_pack_points32q's expressions, so a point has the
+// bits it has there.  perm is a permutation of [0, n) (f8::order_outliers_first); an index outside
+// it is not followed.  NaN padding stays at the end.
+__global__ __launch_bounds__(256) void k_pack_points32q_perm(const Pt *__restrict__ pts,
+                                                             const int *__restrict__ perm, int n,
+                                                             Frame fr, Pt *__restrict__ pts_out,
+                                                             float *__restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ((n + 7) & ~7)) return;
+  float *o = out + 32 * (i >> 3) + (i & 7);
+  const int src = i < n ? perm[i] : -1;
+  if (src < 0 || src >= n) {
+    const float qn = __builtin_nanf("");
+    o[0] = o[8] = o[16] = o[24] = qn;
+    if (i < n) pts_out[i] = Pt{__builtin_nan(""), __builtin_nan(""), __builtin_nan(""), __builtin_nan("")};
+    return;
+  }
+  const Pt p = pts[src];
+  pts_out[i] = p;
   const double is = 1.0 / fr.s;
   o[0] = static_cast<float>((p.x2 - fr.cx2) * is);
   o[8] = static_cast<float>((p.y2 - fr.cy2) * is);
@@ -1366,6 +1434,13 @@ hipError_t launch_pack_points32q(const Pt *pts, int n, const Frame &fr, float4 *
                                  hipStream_t s) {
   hipLaunchKernelGGL(k_pack_points32q, dim3((n + 7 + 255) / 256), dim3(256), 0, s, pts, n, fr,
                      reinterpret_cast<float *>(ptsq));
+  return hipGetLastError();
+}
+
+hipError_t launch_pack_points32q_perm(const Pt *pts, const int *perm, int n, const Frame &fr,
+                                      Pt *pts_out, float4 *ptsq, hipStream_t s) {
+  hipLaunchKernelGGL(k_pack_points32q_perm, dim3((n + 7 + 255) / 256), dim3(256), 0, s, pts, perm,
+                     n, fr, pts_out, reinterpret_cast<float *>(ptsq));
   return hipGetLastError();
 }
 

@@ -55,6 +55,7 @@
 #include "host.h"
 #include "device_math.h"
 #include "f8_kernels.h"
+#include "f8_order.h"
 #include "f8_sched.h"
 
 namespace f8 = rs::f8;
@@ -101,6 +102,17 @@ struct rs_f8_plan : f8::PlanBufs {
   f8::PruneKnobs knobs;       // the pruned count and the carried bound (RSAMD_PRUNE*, RSAMD_CARRY*)
   int64_t n_carried = 0;      // runs carried since the plan was created
   int64_t n_recounts = 0;     // fallen-back runs counted again at a flush (plan_recount)
+  // Point order of the pruned count (f8_order.h): the ordered copies of d_pts / d_pts32q, which
+  // the fp32 count's stages read while ord_on; installed by plan_wait, dropped by set_points and
+  // a retarget
+  f8::OrderBufs ord;
+  int order = 1;              // RSAMD_ORDER
+  bool ord_on = false;
+  int64_t ord_first = 0;      // points placed first (the winner's outliers)
+  int64_t ord_installs = 0;   // installs since the plan was created
+  int64_t runs_since_points = 0;
+  std::vector<int32_t> ord_perm;        // host scratch of an install
+  std::vector<unsigned char> ord_mark;
   int count_launches = 0;     // launches the last run enqueued between its timing events
   bool unread_dropped = false;  // the last run fell back and a dropping flush left it unread
   int *d_full = nullptr;      // rs_f8_plan_counts after a pruned run: the full counts (ld ints)
@@ -119,10 +131,16 @@ static hipError_t alloc_point_arenas(rs_f8_plan *p, int64_t cap) {
   if (a.inl) (void)hipHostFree(a.inl);
   a.pts = a.inl = a.inl_dev = nullptr;
   f8::plan_layout(*p, p->max_hyp, cap);  // sizes; the per-point pointers go null
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&a.pts), a.pts_bytes);
+  p->ord_on = false;
+  f8::order_layout(p->ord, nullptr, cap);
+  // the ordered copies of the points lie behind plan_layout's buffers in the same allocation
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&a.pts), a.pts_bytes + p->ord.bytes);
   if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&a.inl), a.inl_bytes);
   if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void **>(&a.inl_dev), a.inl, 0);
-  if (e == hipSuccess) f8::plan_layout(*p, p->max_hyp, cap);
+  if (e == hipSuccess) {
+    f8::plan_layout(*p, p->max_hyp, cap);
+    f8::order_layout(p->ord, a.pts + a.pts_bytes, cap);
+  }
   return e;
 }
 
@@ -189,6 +207,7 @@ extern "C" int rs_f8_plan_create(rs_ctx *c, int64_t n, int64_t max_hyp, rs_f8_pl
   p->s.overlap = f8::env_int("RSAMD_OVERLAP", kOverlapDefault) != 0;
   p->nospec = f8::env_int("RSAMD_NOSPEC", 0) != 0;
   p->knobs = f8::prune_knobs_env();
+  p->order = f8::env_int("RSAMD_ORDER", 1) != 0;
   p->ts_path = std::getenv("RSAMD_TSTAMP");
   if (p->ts_path) {
     p->s.overlap = false;  // one device-global timeline buffer: one counting launch at a time
@@ -234,6 +253,8 @@ static int plan_retarget(rs_f8_plan *p, int64_t n) {
   p->n = n;
   p->fp32_ok = false;  // set_points decides it for the new points
   f8::carry_drop(p->s);
+  p->ord_on = false;
+  p->runs_since_points = 0;
   return RS_OK;
 }
 
@@ -322,6 +343,8 @@ extern "C" int rs_f8_plan_set_points(rs_f8_plan *p, const double *p1, const doub
   int st = plan_flush(p, f8::FlushFor::kDrop);  // runs in flight read the resident points
   if (st) return st;
   f8::carry_drop(p->s);
+  p->ord_on = false;
+  p->runs_since_points = 0;
   rs_ctx *c = p->ctx;
   const int64_t n = p->n;
   const size_t b = sizeof(double) * 2 * n;
@@ -473,7 +496,7 @@ static rsd::PruneArgs prune_args(const rs_f8_plan *p, const RunBufs &b, int lane
   pa.surv = b.d_surv;
   pa.gdone_b = b.d_gdone_b;
   pa.g_first = pn.g_first;
-  pa.margin = pn.margin;
+  pa.margin = f8::order_margin(pn.margin, p->knobs.margin >= 0, static_cast<int>(p->n), p->ord_on);
   pa.min_skip = pn.min_skip;
   if (b.carried) {  // every group is screened against the lane's carried bound
     pa.carry = p->d_carry + lane;
@@ -483,8 +506,13 @@ static rsd::PruneArgs prune_args(const rs_f8_plan *p, const RunBufs &b, int lane
 }
 
 // What the fp32 counting kernel reads and writes for h hypotheses of set b's last run
+// Both point arrays from one copy: the ordered one while an order is installed (a count is a sum
+// over the points and the drop rule holds for any fixed order, so every stage of a run, its
+// recount and rs_f8_plan_counts may read either; installs happen only with both lanes drained)
 static rsd::CountArgs count_args(const rs_f8_plan *p, const RunBufs &b, int h) {
-  return rsd::CountArgs{p->d_pts32q, p->d_pts, static_cast<int>(p->n), h, b.d_F32, b.d_F, p->ld,
+  const float4 *ptsq = p->ord_on ? p->ord.d_pts32q : p->d_pts32q;
+  const rsd::Pt *pts = p->ord_on ? p->ord.d_pts : p->d_pts;
+  return rsd::CountArgs{ptsq, pts, static_cast<int>(p->n), h, b.d_F32, b.d_F, p->ld,
                         rsd::GuardW{b.thresh * b.thresh}, b.d_counts, b.d_gdone, b.d_status, b.d_G4,
                         nullptr};
 }
@@ -616,6 +644,7 @@ static int plan_run(rs_f8_plan *p, int64_t H, int32_t mode, uint64_t seed, uint6
   f8::committed(p->s, r.lane);
   p->last_H = H;
   p->unread_dropped = false;
+  ++p->runs_since_points;
   return RS_OK;
 }
 
@@ -693,11 +722,47 @@ extern "C" int rs_f8_plan_run_np(rs_f8_plan *p, int64_t H, uint32_t *key, int32_
   return rs_f8_plan_run_np_slice(p, H, 0, H, key, pos, thresh);
 }
 
+// The point order (f8_order.h; derivation above k_f8_count32q, "Point order"), installed from the
+// winner a read flush just delivered: the run's pinned S_RANSAC list and best_count, final after
+// plan_flush (a fallen-back run has been recounted there).  Both lanes are drained and nothing
+// reads the ordered copies.  One small upload, one pack launch and one wait on the context
+// stream, after which either lane's launches see the copies.  A winner that orders nothing
+// (f8::order_outliers_first returns 0) installs nothing, and a later read may try again.
+static int order_install(rs_f8_plan *p) {
+  const int slot = static_cast<int>((p->s.runs - 1) % rs_f8_plan::kSlots);
+  const rsd::F8DevResult *r = p->h_slot[slot];
+  const int *inl = p->h_inl[slot];
+  if (!inl || r->fell_back != 0 || r->best_count <= f8::kOrderMinCount) return RS_OK;
+  const size_t n = static_cast<size_t>(p->n);
+  p->ord_perm.resize(n);
+  p->ord_mark.resize(n);
+  const int64_t first = f8::order_outliers_first(inl, r->n_inliers, r->best_count, p->n,
+                                                 p->ord_perm.data(), p->ord_mark.data());
+  if (first <= 0) return RS_OK;
+  hipStream_t s = p->ctx->stream;
+  HIP_TRY(hipMemcpyAsync(p->ord.d_perm, p->ord_perm.data(), sizeof(int32_t) * n,
+                         hipMemcpyHostToDevice, s));
+  HIP_TRY(rsd::launch_pack_points32q_perm(p->d_pts, p->ord.d_perm, static_cast<int>(p->n), p->frame,
+                                          p->ord.d_pts, p->ord.d_pts32q, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  p->ord_on = true;
+  p->ord_first = first;
+  ++p->ord_installs;
+  return RS_OK;
+}
+
 // Complete the last run (its pending tail) and wait.  Accessors below then read its buffer
-// set synchronously.
+// set synchronously.  The one place an order is installed: a read flush of a plan that has
+// issued more than one run on the resident points (f8::order_installs).
 static int plan_wait(rs_f8_plan *p) {
   if (p->s.runs == 0) return fail(RS_EINVAL, "no run has been issued on this plan");
-  if (p->s.pending) return plan_flush(p, f8::FlushFor::kRead);
+  if (p->s.pending) {
+    int st = plan_flush(p, f8::FlushFor::kRead);
+    if (st) return st;
+    const bool enabled = p->order && p->knobs.prune && p->use_fp32 && p->fp32_ok;
+    if (f8::order_installs(enabled, p->ord_on, p->runs_since_points)) return order_install(p);
+    return RS_OK;
+  }
   if (p->unread_dropped)
     return fail(RS_EINVAL, "the last run fell back and its results were dropped before they were read");
   return RS_OK;
@@ -865,6 +930,14 @@ extern "C" int rs_f8_plan_recount_stats(rs_f8_plan *p, int64_t *out) {
   if (!p || !out) return fail(RS_EINVAL, "null pointer");
   out[0] = p->n_recounts;
   out[1] = p->count_launches;
+  return RS_OK;
+}
+
+extern "C" int rs_f8_plan_order_stats(rs_f8_plan *p, int64_t *out) {
+  if (!p || !out) return fail(RS_EINVAL, "null pointer");
+  out[0] = p->ord_on ? 1 : 0;
+  out[1] = p->ord_on ? p->ord_first : 0;
+  out[2] = p->ord_installs;
   return RS_OK;
 }
 

@@ -148,6 +148,7 @@ _SIGS = {
     "rs_f8_plan_prune_stats": (C.c_int, [C.c_void_p, _i64p]),
     "rs_f8_plan_carry_stats": (C.c_int, [C.c_void_p, _i64p]),
     "rs_f8_plan_recount_stats": (C.c_int, [C.c_void_p, _i64p]),
+    "rs_f8_plan_order_stats": (C.c_int, [C.c_void_p, _i64p]),
     "rs_f8_plan_stage_counts": (C.c_int, [C.c_void_p, _i32p, C.c_int64]),
     "rs_f8_plan_set_count_precision": (C.c_int, [C.c_void_p, C.c_int32]),
     "rs_f8_ransac_np": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64, _u32p, _i32p,
@@ -793,6 +794,14 @@ class F8Plan:
         out = (C.c_int64 * 2)()
         check(lib().rs_f8_plan_recount_stats(self._h, out))
         return out[0], out[1]
+
+    def order_stats(self):
+        """The point order of the pruned count: whether one is installed, the points placed first
+        (the outliers of the winner it was built from), installs since the plan was created.
+        Host state: waits for nothing and installs nothing."""
+        out = (C.c_int64 * 3)()
+        check(lib().rs_f8_plan_order_stats(self._h, out))
+        return {"installed": bool(out[0]), "first": out[1], "installs": out[2]}
 
     def kernel_ms(self, last_n=1):
         """Device times of the last run, or averaged over the last ``last_n`` runs."""
