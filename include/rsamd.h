@@ -1294,6 +1294,95 @@ int rs_eval_mesh_distance(rs_ctx *ctx, const double *pts, int64_t n, const doubl
 int rs_eval_timing(rs_ctx *ctx, int32_t enable, double *ms);
 
 /* ------------------------------------------------------------------------------------------
+ * Registration (eval.hip): a target mesh and its grid kept on the device (rs_eval_index), queried
+ * many times, and one step of trimmed ICP of a source cloud against it, wholly on the device.
+ * tsbb15_amd.evaluation.register drives the steps; tests/register_ref.py restates a step in numpy.
+ * The index owns its device memory; it uses the stream of the context it was created with and
+ * must be destroyed before that context.  One index serves one caller at a time.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct rs_eval_index rs_eval_index;
+
+/* The grid of rs_eval_mesh_distance for (vertices, faces, cell), built once: the same checks, caps
+ * and messages (all but those about the queries), the same bin, scan and scatter kernels, the
+ * same cross-check of the host's and the device's entries and skipped faces.  info receives
+ * cells, entries, largest_cell and faces_skipped; tests and beyond are 0.  *out is null on an
+ * error. */
+int rs_eval_index_create(rs_ctx *ctx, const double *vertices, int64_t nv, const int32_t *faces,
+                         int64_t nf, double cell, rs_eval_index **out, rs_eval_info *info);
+int rs_eval_index_destroy(rs_eval_index *index);   /* null is allowed */
+
+/* rs_eval_mesh_distance's query (the same kernel) against the index: d2, face and closest are
+ * bit-equal to that call's on the same mesh, points, max_dist and cell, and so is info.  n = 0
+ * returns at once with info as create gave it.  RS_EINVAL: n < 0 or > RS_EVAL_MAX_POINTS,
+ * max_dist not > 0, a null pointer. */
+int rs_eval_index_query(rs_eval_index *index, const double *pts, int64_t n, double max_dist,
+                        double *d2, int32_t *face, double *closest, rs_eval_info *info);
+
+/* The source cloud of the steps that follow, pts (n, 3), uploaded once; 1 <= n <=
+ * RS_EVAL_MAX_POINTS.  It replaces an earlier cloud and forgets the last step. */
+int rs_eval_index_set_points(rs_eval_index *index, const double *pts, int64_t n);
+
+#define RS_EVAL_REG_POINT 0
+#define RS_EVAL_REG_PLANE 1
+#define RS_EVAL_REG_SLOTS 40
+#define RS_EVAL_REG_BLOCK 2048   /* source indices per block of the moments' sum */
+
+typedef struct rs_eval_step {
+  int64_t matched;   /* m: points with face >= 0                                             */
+  int64_t kept;      /* points with face >= 0 and d2 <= tau                                  */
+  int64_t k;         /* the rank tau was taken at; 0 when m = 0                              */
+  int64_t tests;     /* point-triangle tests of this step's query                            */
+  double tau;        /* the k-th smallest d2 among the matched; NaN when m = 0               */
+  double moments[RS_EVAL_REG_SLOTS];   /* see below; the slots a metric does not use are 0  */
+} rs_eval_step;      /* 360 bytes */
+
+/* One step under the similarity T = (s, R row-major, t), 13 doubles, about `origin`.  All fp64,
+ * no product fused with a sum, every sum left to right as written.
+ *   Transform.  p'_0 = s ((R00 x + R01 y) + R02 z) + t0, rows 1 and 2 likewise.  A point with a
+ *     coordinate that is not finite stays not finite.
+ *   Query.  rs_eval_mesh_distance's query of p' with max_dist: d2, face, closest.  A point is
+ *     matched when face >= 0; m is their number.  A matched d2 is finite and not negative.
+ *   Trim.  k = ceil(keep m - 1e-9) (one product, one difference, one ceil), clamped to 1..m.  tau
+ *     is the k-th smallest d2 among the matched points, found exactly: a finite double that is not
+ *     negative orders as its 64-bit pattern, and eight passes, from the highest byte down, each
+ *     count the matched points whose higher bytes equal the prefix found so far in 256 bins of
+ *     that byte (one table per workgroup in LDS, merged with integer atomics) and pick the bin
+ *     that holds rank k.  A point is kept when it is matched and d2 <= tau: ties at tau are all
+ *     kept, kept >= k.  m = 0: kept = k = 0, tau = NaN, every moment 0, RS_OK.
+ *   Moments.  x = p' - origin, y = closest - origin, e = p' - closest, per kept point.
+ *     RS_EVAL_REG_POINT, 17 slots: 0..2 sum x; 3..5 sum y; 6 + 3 i + j sum y_i x_j; 15 sum
+ *     (x0 x0 + x1 x1) + x2 x2; 16 sum d2.
+ *     RS_EVAL_REG_PLANE, 37 slots.  (a, b, c) is the matched face, u = b - a, v = c - a,
+ *     N = (u1 v2 - u2 v1, u2 v0 - u0 v2, u0 v1 - u1 v0), l = sqrt((N0 N0 + N1 N1) + N2 N2),
+ *     n = N / l per component, r = (n0 e0 + n1 e1) + n2 e2, and the row
+ *     J = (x1 n2 - x2 n1, x2 n0 - x0 n2, x0 n1 - x1 n0, n0, n1, n2, (x0 n0 + x1 n1) + x2 n2).
+ *     Slots 0..27 sum J_i J_j for i <= j, row after row (00, 01, .., 06, 11, 12, ..); 28..34 sum
+ *     J_i r; 35 sum r r; 36 sum d2.  Both signs of n give the same terms.
+ *   Order of a sum.  Source index i belongs to block i / RS_EVAL_REG_BLOCK and, inside it, to lane
+ *     (i mod RS_EVAL_REG_BLOCK) mod 256.  A lane starts at +0.0 and adds its terms in ascending
+ *     index; a point that is not kept, or an index >= n, adds +0.0.  The 256 lane sums fold by
+ *     halving: lane l takes l + (l + h) for h = 128, 64, .., 1; lane 0 holds the block's partial.
+ *     The total starts at +0.0 and adds the partials in ascending block order.  Nothing in it
+ *     depends on the grid, on cell, on an atomic's arrival or on scheduling; there is no
+ *     floating-point atomic anywhere.
+ * The 16 doubles travel as kernel arguments; the step downloads the record, once, after its one
+ * synchronisation.  RS_EINVAL: no source cloud, T or origin not finite, keep outside (0, 1],
+ * max_dist not > 0, an unknown metric, a null pointer. */
+int rs_eval_index_step(rs_eval_index *index, const double T[13], const double origin[3],
+                       double keep, double max_dist, int32_t metric, rs_eval_step *out);
+
+/* The last step's arrays: d2 (n), face (n) int32, closest (n, 3), kept (n) uint8, 1 where kept;
+ * a null pointer skips an array.  RS_EINVAL when no step has run since set_points. */
+int rs_eval_index_read(rs_eval_index *index, double *d2, int32_t *face, double *closest,
+                       uint8_t *kept);
+
+/* HIP events between the stages of the index's next steps (enable != 0).  Returns the last timed
+ * step's device ms: slot 0 transform, 1 query, 2 select (16 launches), 3 moments (the blocks'
+ * partials and their sum); -1 where none (tools/bench_register.py). */
+#define RS_EVAL_REG_TIMING_SLOTS 4
+int rs_eval_index_timing(rs_eval_index *index, int32_t enable, double *ms);
+
+/* ------------------------------------------------------------------------------------------
  * Mesh clean-up (mesh.hip): connected components, compaction and Taubin smoothing of the welded
  * index mesh rs_surface_extract returns.  The reference project has no such code; nothing here
  * restates code of it.  vertices is (nv, 3) fp64, faces (nf, 3) int32 with indices in 0..nv - 1.

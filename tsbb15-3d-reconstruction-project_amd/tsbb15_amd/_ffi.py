@@ -87,6 +87,11 @@ class EvalInfo(C.Structure):
                 ("tests", C.c_int64), ("faces_skipped", C.c_int64), ("beyond", C.c_int64)]
 
 
+class EvalStep(C.Structure):
+    _fields_ = [("matched", C.c_int64), ("kept", C.c_int64), ("k", C.c_int64),
+                ("tests", C.c_int64), ("tau", C.c_double), ("moments", C.c_double * 40)]
+
+
 class SimplifyInfo(C.Structure):
     _fields_ = [("clusters", C.c_int64), ("fallbacks", C.c_int64),
                 ("degenerate_faces", C.c_int64), ("duplicate_faces", C.c_int64),
@@ -98,6 +103,10 @@ WASH_MAX_TRACK = 128
 CLOUD_MAX_CELLS = 1 << 21
 CLOUD_STAGES = ("grid", "scan", "sort", "normals", "attributes")
 EVAL_STAGES = ("bin", "scan", "scatter", "query")
+EVAL_REG_STAGES = ("transform", "query", "select", "moments")
+EVAL_REG_METRICS = ("point", "plane")   # RS_EVAL_REG_*: the index is the code
+EVAL_REG_SLOTS = 40
+EVAL_REG_BLOCK = 2048
 TRACKING_STAGES = ("pyramid", "forward", "backward")
 BA_LOSSES = ("linear", "soft_l1", "huber", "cauchy")   # RS_BA_LOSS_*: the index is the code
 BA_KERNELS = ("k_ba_linearize", "k_ba_camera", "k_ba_pointsum", "k_ba_point", "k_ba_schur",
@@ -261,6 +270,16 @@ _SIGS = {
                                         C.c_int64, C.c_double, C.c_double, _dp, _i32p, _dp,
                                         C.POINTER(EvalInfo)]),
     "rs_eval_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "rs_eval_index_create": (C.c_int, [C.c_void_p, _dp, C.c_int64, _i32p, C.c_int64, C.c_double,
+                                       C.POINTER(C.c_void_p), C.POINTER(EvalInfo)]),
+    "rs_eval_index_destroy": (C.c_int, [C.c_void_p]),
+    "rs_eval_index_query": (C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_double, _dp, _i32p, _dp,
+                                      C.POINTER(EvalInfo)]),
+    "rs_eval_index_set_points": (C.c_int, [C.c_void_p, _dp, C.c_int64]),
+    "rs_eval_index_step": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double, C.c_double, C.c_int32,
+                                     C.POINTER(EvalStep)]),
+    "rs_eval_index_read": (C.c_int, [C.c_void_p, _dp, _i32p, _dp, _u8p]),
+    "rs_eval_index_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
     "rs_mesh_components": (C.c_int, [C.c_void_p, _i32p, C.c_int64, C.c_int64, _i32p, _i32p,
                                      _i64p, _i32p]),
     "rs_mesh_compact": (C.c_int, [C.c_void_p, _dp, C.c_int64, _i32p, C.c_int64, _u8p, _dp,

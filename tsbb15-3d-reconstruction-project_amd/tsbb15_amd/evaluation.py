@@ -12,6 +12,11 @@ of the multi-view-stereo benchmark the Dino comes from (Seitz et al. 2006):
 Both rest on ``mesh_distance``, the exact distance from many points to a triangle mesh (HIP kernels
 of eval.hip; the contract stands in include/rsamd.h).  Everything about the cameras -- tens of
 them -- is host numpy: ``decompose_projection``, ``align_similarity``, ``camera_errors``.
+
+Both measures assume the two meshes stand in one frame.  ``register`` brings them there: trimmed
+ICP of a point cloud to a mesh kept on the device (``MeshIndex``, the rs_eval_index_* entries),
+one device step and one small host solve per iteration; ``compare_meshes(register=...)`` runs it
+first.
 """
 from __future__ import annotations
 
@@ -171,12 +176,17 @@ def completeness(dist, threshold):
 
 
 def compare_meshes(rec_v, rec_f, gt_v, gt_f, fraction=0.9, threshold=None, max_dist=np.inf,
-                   samples=None, seed=0, ctx=None):
+                   samples=None, seed=0, ctx=None, register=None):
     """Accuracy and completeness of a reconstruction against the truth, both through
     mesh_distance: the reconstruction's points against the true mesh, and the truth's points
     against the reconstructed one.  The points are the meshes' vertices, or with ``samples`` that
     many surface samples of each (sample_surface, seeds ``seed`` and ``seed + 1``).  ``threshold``
     is completeness' distance, by default 1 % of the diagonal of the truth's box.
+
+    ``register``, a dict of keywords for ``register`` (an empty one for its defaults), first
+    registers the reconstruction's points to the true mesh and applies the similarity found to
+    ``rec_v`` before both distance calls; the result gains s, R, t and ``registration``, what
+    ``register`` returned.  With None nothing is aligned.
 
     Returns dict(accuracy, completeness, fraction, threshold, dist_rec, dist_gt, info_rec,
     info_gt)."""
@@ -187,6 +197,14 @@ def compare_meshes(rec_v, rec_f, gt_v, gt_f, fraction=0.9, threshold=None, max_d
         if len(finite) == 0:
             raise ValueError('the truth has no finite vertex to take a threshold from')
         threshold = 0.01 * float(np.sqrt(((finite.max(axis=0) - finite.min(axis=0)) ** 2).sum()))
+    if register is not None:
+        src = rec_v if samples is None else sample_surface(rec_v, rec_f, samples, seed)[0]
+        reg = _register(src, gt_v, gt_f, ctx=ctx, **dict(register))
+        moved = apply_similarity(rec_v, reg["s"], reg["R"], reg["t"])
+        out = compare_meshes(moved, rec_f, gt_v, gt_f, fraction=fraction, threshold=threshold,
+                             max_dist=max_dist, samples=samples, seed=seed, ctx=ctx)
+        out.update(s=reg["s"], R=reg["R"], t=reg["t"], registration=reg)
+        return out
     if samples is None:
         rec_p, gt_p = rec_v, gt_v
     else:
@@ -198,6 +216,272 @@ def compare_meshes(rec_v, rec_f, gt_v, gt_f, fraction=0.9, threshold=None, max_d
             "completeness": completeness(dist_gt, threshold), "fraction": fraction,
             "threshold": threshold, "dist_rec": dist_rec, "dist_gt": dist_gt,
             "info_rec": info_rec, "info_gt": info_gt}
+
+
+# ---- registration ------------------------------------------------------------------------------
+
+REG_STAGES = _ffi.EVAL_REG_STAGES
+REG_METRICS = _ffi.EVAL_REG_METRICS
+REG_BLOCK = _ffi.EVAL_REG_BLOCK   # RS_EVAL_REG_BLOCK
+
+
+def mesh_box(vertices, faces):
+    """(centre, diagonal) of the box of the faces with finite coordinates, the box the grid is
+    laid over; (0, 0) for a mesh without such a face."""
+    tri = np.asarray(vertices)[np.asarray(faces).reshape(-1, 3)]
+    tri = tri[np.isfinite(tri).all(axis=(1, 2))]
+    if len(tri) == 0:
+        return np.zeros(3), 0.0
+    lo, hi = tri.min(axis=(0, 1)), tri.max(axis=(0, 1))
+    return (lo + hi) / 2.0, float(np.sqrt(((hi - lo) ** 2).sum()))
+
+
+class MeshIndex:
+    """A target mesh and its search grid kept on the device (rs_eval_index): built once, queried
+    many times.  ``cell`` is the grid's side, ``default_cell`` when None.  Use it as a context
+    manager or call ``close``; the handle is also released when the object is collected.  The
+    index uses the stream of ``ctx`` and keeps it alive."""
+
+    def __init__(self, vertices, faces, cell=None, ctx=None):
+        self._h = None
+        vertices = _points(vertices, 'vertices')
+        faces = _faces(faces, len(vertices))
+        cell = default_cell(vertices, faces) if cell is None else float(cell)
+        if not np.isfinite(cell) or not cell > 0.0:
+            raise ValueError('cell must be finite and positive')
+        self.ctx = ctx or _ffi.default_context()
+        self.cell = cell
+        self.origin, self.diagonal = mesh_box(vertices, faces)
+        self.n_points = 0
+        h, info = _ffi.C.c_void_p(), _ffi.EvalInfo()
+        _ffi.check(_ffi.lib().rs_eval_index_create(
+            self.ctx.handle, _ffi.ptr(vertices, _d), len(vertices), _ffi.ptr(faces, _i32),
+            len(faces), cell, _ffi.C.byref(h), _ffi.C.byref(info)))
+        self._h = h
+        self.cells, self.entries = tuple(info.cells), info.entries
+        self.largest_cell, self.faces_skipped = info.largest_cell, info.faces_skipped
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise RuntimeError('the mesh index is closed')
+        return self._h
+
+    def close(self):
+        if getattr(self, '_h', None) is not None:
+            _ffi.lib().rs_eval_index_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def distance(self, points, max_dist=np.inf):
+        """What ``mesh_distance`` returns for these points against the index's mesh, bit for bit
+        (rs_eval_index_query)."""
+        h = self.handle
+        points = _points(points, 'points')
+        max_dist = float(max_dist)
+        if not max_dist > 0.0:
+            raise ValueError('max_dist must be positive (+inf is allowed)')
+        n = len(points)
+        d2, face, closest = np.empty(n), np.full(n, -1, dtype=np.int32), np.empty((n, 3))
+        info = _ffi.EvalInfo()
+        if n > 0:
+            _ffi.check(_ffi.lib().rs_eval_index_query(
+                h, _ffi.ptr(points, _d), n, max_dist, _ffi.ptr(d2, _d), _ffi.ptr(face, _i32),
+                _ffi.ptr(closest, _d), _ffi.C.byref(info)))
+        return np.sqrt(d2), face, closest, {
+            "d2": d2, "cell": self.cell, "cells": tuple(info.cells), "entries": info.entries,
+            "largest_cell": info.largest_cell, "tests": info.tests,
+            "faces_skipped": info.faces_skipped, "beyond": info.beyond}
+
+    def set_points(self, points):
+        """Upload the source cloud of the steps that follow (rs_eval_index_set_points)."""
+        h = self.handle
+        points = _points(points, 'points')
+        if len(points) == 0:
+            raise ValueError('the source cloud needs at least one point')
+        _ffi.check(_ffi.lib().rs_eval_index_set_points(h, _ffi.ptr(points, _d), len(points)))
+        self.n_points = len(points)
+
+    def step(self, s=1.0, R=None, t=None, keep=1.0, max_dist=np.inf, metric="plane",
+             origin=None):
+        """One registration step of the source cloud under p -> s R p + t (rs_eval_index_step,
+        where the step is defined).  Returns dict(matched, kept, k, tests, tau, moments (40))."""
+        h = self.handle
+        if metric not in REG_METRICS:
+            raise ValueError(f'metric must be one of {REG_METRICS}')
+        T = np.empty(13)
+        T[0] = s
+        T[1:10] = np.eye(3).ravel() if R is None else np.asarray(R, dtype=np.float64).reshape(9)
+        T[10:] = 0.0 if t is None else np.asarray(t, dtype=np.float64).reshape(3)
+        o = _ffi.f64c(self.origin if origin is None else origin).reshape(3)
+        rec = _ffi.EvalStep()
+        _ffi.check(_ffi.lib().rs_eval_index_step(
+            h, _ffi.ptr(T, _d), _ffi.ptr(o, _d), float(keep), float(max_dist),
+            REG_METRICS.index(metric), _ffi.C.byref(rec)))
+        return {"matched": rec.matched, "kept": rec.kept, "k": rec.k, "tests": rec.tests,
+                "tau": rec.tau, "moments": np.array(rec.moments[:])}
+
+    def read(self):
+        """(d2, face, closest, kept) of the last step, kept a bool mask (rs_eval_index_read)."""
+        h, n = self.handle, self.n_points
+        d2, face, closest = np.empty(n), np.empty(n, dtype=np.int32), np.empty((n, 3))
+        kept = np.empty(n, dtype=np.uint8)
+        _ffi.check(_ffi.lib().rs_eval_index_read(
+            h, _ffi.ptr(d2, _d), _ffi.ptr(face, _i32), _ffi.ptr(closest, _d),
+            _ffi.ptr(kept, _ffi.C.c_uint8)))
+        return d2, face, closest, kept.astype(bool)
+
+    def timing(self, enable):
+        """Enable / disable HIP events between the stages of this index's next steps
+        (rs_eval_index_timing); returns the last timed step's {stage: device ms}, -1 where
+        none."""
+        ms = np.zeros(len(REG_STAGES))
+        _ffi.check(_ffi.lib().rs_eval_index_timing(self.handle, int(enable), _ffi.ptr(ms, _d)))
+        return dict(zip(REG_STAGES, ms.tolist()))
+
+
+def rotation_exp(omega):
+    """Rodrigues' formula: the rotation by |omega| about omega."""
+    omega = np.asarray(omega, dtype=np.float64).reshape(3)
+    th = float(np.sqrt((omega * omega).sum()))
+    K = np.array([[0.0, -omega[2], omega[1]], [omega[2], 0.0, -omega[0]],
+                  [-omega[1], omega[0], 0.0]])
+    if th < 1e-8:
+        a, b = 1.0 - th * th / 6.0, 0.5 - th * th / 24.0
+    else:
+        a, b = np.sin(th) / th, (1.0 - np.cos(th)) / (th * th)
+    return np.eye(3) + a * K + b * (K @ K)
+
+
+def step_rms(metric, rec):
+    """The root mean square a step's record reports for its metric: of the distances (point) or
+    of the distances along the matched faces' normals (plane), over the kept points."""
+    total = rec["moments"][16 if metric == "point" else 35]
+    return float(np.sqrt(total / rec["kept"]))
+
+
+def step_update(metric, rec, origin, with_scale=True):
+    """(ds, dR, dt) from a step's moments: the increment p' -> ds dR p' + dt.
+
+    point: the moments centred (cov = sum y x^T / N - my mx^T, var = sum |x|^2 / N - |mx|^2),
+    then the SVD of ``align_similarity``.  plane: J^T J z = -J^T r for z = (omega, u, sigma) by
+    np.linalg.lstsq (the minimum-norm solution where the system is singular, as for a planar
+    target), sigma dropped without ``with_scale``; dR = Exp(omega), ds = 1 + sigma.  Both are
+    taken about ``origin``: dt = origin + u - ds dR origin."""
+    mom, origin = rec["moments"], np.asarray(origin, dtype=np.float64)
+    if metric == "point":
+        N = float(rec["kept"])
+        mx, my = mom[0:3] / N, mom[3:6] / N
+        cov = mom[6:15].reshape(3, 3) / N - np.outer(my, mx)
+        var = mom[15] / N - float((mx * mx).sum())
+        U, D, Vt = np.linalg.svd(cov)
+        S = np.array([1.0, 1.0, 1.0 if np.linalg.det(U) * np.linalg.det(Vt) >= 0.0 else -1.0])
+        dR = (U * S) @ Vt
+        ds = float((D * S).sum() / var) if with_scale and var > 0.0 else 1.0
+        u = my - ds * dR @ mx
+    else:
+        A = np.zeros((7, 7))
+        A[np.triu_indices(7)] = mom[0:28]
+        A = A + np.triu(A, 1).T
+        m = 7 if with_scale else 6
+        z = np.linalg.lstsq(A[:m, :m], -mom[28:28 + m], rcond=None)[0]
+        dR, u = rotation_exp(z[0:3]), z[3:6]
+        ds = 1.0 + float(z[6]) if with_scale else 1.0
+    return ds, dR, origin + u - ds * dR @ origin
+
+
+def register(points, vertices, faces, metric="plane", keep=1.0, with_scale=True, init=None,
+             max_dist=np.inf, max_iter=50, rtol=1e-6, atol=None, cell=None, index=None,
+             ctx=None):
+    """Trimmed ICP of a point cloud to a triangle mesh: the similarity (s, R, t) under which
+    s R p + t lies on the mesh, from ``init`` = (s, R, t) (the identity when None; the tested
+    basin is 20 degrees).
+
+    Every iteration is one rs_eval_index_step on the device -- transform, closest points, the
+    exact ``keep`` quantile tau of the matched squared distances (points farther than
+    ``max_dist`` are unmatched; ties at tau are kept), the moments over the kept points about the
+    centre of the mesh's box -- and ``step_update`` on the host.  ``metric`` "plane" minimises
+    the distances along the matched faces' normals and converges quadratically; "point" is the
+    closest-point / Umeyama update.  ``index`` reuses a MeshIndex of the mesh (vertices and faces
+    are then not looked at); otherwise one is built with ``cell`` and closed again.
+
+    Stops when rms_i <= atol (default 1e-12 of the mesh box's diagonal), when
+    |rms_(i-1) - rms_i| <= rtol rms_(i-1), or after ``max_iter`` steps.  The transform returned is
+    the one the last step was evaluated under: the last rms, dist and mask belong to it.
+
+    Returns dict(s, R, t, iterations, converged, rms, kept, matched, tau, dist, mask): rms, kept,
+    matched and tau hold one entry per step, dist (n) the distances (inf or NaN where unmatched)
+    and mask (n) the kept points of the last step.  ValueError before any launch: bad shapes, no
+    point, keep outside (0, 1], an unknown metric, an init that is not finite, max_dist not > 0,
+    max_iter < 1; and when a step matches no point."""
+    points = _points(points, 'points')
+    if len(points) == 0:
+        raise ValueError('points must hold at least one point')
+    if metric not in REG_METRICS:
+        raise ValueError(f'metric must be one of {REG_METRICS}')
+    keep, max_dist, max_iter = float(keep), float(max_dist), int(max_iter)
+    if not 0.0 < keep <= 1.0:
+        raise ValueError('keep must be in (0, 1]')
+    if not max_dist > 0.0:
+        raise ValueError('max_dist must be positive (+inf is allowed)')
+    if max_iter < 1:
+        raise ValueError('max_iter must be at least 1')
+    if init is None:
+        s, R, t = 1.0, np.eye(3), np.zeros(3)
+    else:
+        s, R, t = init
+        s, R, t = float(s), np.array(R, dtype=np.float64), np.array(t, dtype=np.float64)
+        if R.shape != (3, 3) or t.shape != (3,):
+            raise ValueError('init must be (s, R (3, 3), t (3))')
+        if not (np.isfinite(s) and np.isfinite(R).all() and np.isfinite(t).all()):
+            raise ValueError('init is not finite')
+    own = index is None
+    if own:
+        index = MeshIndex(vertices, faces, cell=cell, ctx=ctx)
+    try:
+        origin = index.origin
+        atol = 1e-12 * index.diagonal if atol is None else float(atol)
+        index.set_points(points)
+        hist = {"rms": [], "kept": [], "matched": [], "tau": []}
+        converged = False
+        for it in range(max_iter):
+            rec = index.step(s, R, t, keep=keep, max_dist=max_dist, metric=metric, origin=origin)
+            if rec["matched"] == 0:
+                raise ValueError(f'step {it} matched no point: under the current transform no '
+                                 'point lies within max_dist of the mesh')
+            rms = step_rms(metric, rec)
+            for key, val in (("rms", rms), ("kept", rec["kept"]), ("matched", rec["matched"]),
+                             ("tau", rec["tau"])):
+                hist[key].append(val)
+            if rms <= atol or (it > 0 and abs(hist["rms"][-2] - rms) <= rtol * hist["rms"][-2]):
+                converged = True
+                break
+            if it == max_iter - 1:
+                break
+            ds, dR, dt = step_update(metric, rec, origin, with_scale)
+            s, R, t = ds * s, dR @ R, ds * dR @ t + dt
+        d2, _, _, mask = index.read()
+    finally:
+        if own:
+            index.close()
+    return {"s": s, "R": R, "t": t, "iterations": len(hist["rms"]), "converged": converged,
+            "rms": np.array(hist["rms"]), "kept": np.array(hist["kept"], dtype=np.int64),
+            "matched": np.array(hist["matched"], dtype=np.int64), "tau": np.array(hist["tau"]),
+            "dist": np.sqrt(d2), "mask": mask}
+
+
+_register = register   # compare_meshes has a keyword of that name
 
 
 # ---- cameras (host only) ---------------------------------------------------------------------
