@@ -935,6 +935,76 @@ int rs_cloud_normals(rs_ctx *ctx, const double *pts, int64_t n, double radius,
 #define RS_CLOUD_TIMING_SLOTS 5
 int rs_cloud_timing(rs_ctx *ctx, int32_t enable, double *ms);
 
+/* Exact k nearest neighbours on a uniform grid (cloud_knn.hip): what GetKNeighbours of
+ * 3Dvisualization.py asks a kd-tree for (tree.query(points[None, j], k)), for every query at
+ * once, and two consumers that keep the index lists on the device. */
+#define RS_CLOUD_KNN_MAX_K 64
+#define RS_CLOUD_KNN_MAX_CELLS (1LL << 24)
+
+typedef struct rs_knn_info {
+  int64_t cells;         /* cells of the grid                                   */
+  int64_t largest_cell;  /* points in the fullest cell                          */
+  int64_t tested;        /* candidates whose d2 was computed                    */
+  int64_t found;         /* sum of count                                        */
+  int64_t rows_short;    /* queries with count < k                              */
+} rs_knn_info;           /* 40 bytes */
+
+/* pts (n, 3); queries (m, 3), or null: the points themselves (then m must equal n).
+ *   d2(q, j) = dx*dx + dy*dy + dz*dz with d = q - p_j: the differences first, the sum left to
+ *   right, no product fused with a sum -- the bits of the same expression in numpy.
+ *   The result of a query is the k smallest elements of { (bits of d2(q, j), j) } in
+ *   lexicographic order, j over the finite points with d2(q, j) <= max_dist * max_dist
+ *   (max_dist = +inf: all of them), written in that order to idx (m, k) and d2 (m, k).
+ *   A point is a candidate for itself like any other.  count[i] is the number of entries found;
+ *   the slots past it hold idx = -1 and d2 = +inf.  A non-finite point is nobody's neighbour, a
+ *   non-finite query has count 0.
+ * A minimum-k set under a total order does not depend on the order in which the candidates are
+ * visited, so the result depends neither on the grid, nor on `cell`, nor on the arrival order of
+ * an atomic.
+ * The search is a dense uniform grid of side `cell` from the minimum corner `lo` of the finite
+ * points, floor((hi - lo) / cell) + 1 cells per axis, every point registered in exactly one
+ * cell; cell = 0 picks the largest extent / clamp(round(cbrt(number of finite points)), 1, 256)
+ * (raised to 2^-24 of the box's largest coordinate magnitude; one cell where the extent is 0).
+ * A query walks the Chebyshev rings r = r0, r0 + 1, ... around its own cell
+ * floor((q - lo) / cell) (clamped to +-2^29), each clipped to the grid, and stops before ring
+ * r >= 1 when its list is full and the k-th d2 <= B^2, B = (r - 1) cell (1 - 2^-20), when
+ * B > max_dist, and after the last ring that meets the grid.
+ * RS_EINVAL before any launch: k outside 1..RS_CLOUD_KNN_MAX_K, n or m negative or above
+ * RS_CLOUD_MAX_POINTS, max_dist NaN or negative, cell negative or not finite, a null pointer
+ * where elements are expected.  RS_EINVAL once the box is known (after the box reduction, before
+ * any other kernel): a box whose extent hi - lo overflows to infinity on an axis, a grid of more
+ * than RS_CLOUD_KNN_MAX_CELLS cells or a cell below 2^-24 of the box's largest coordinate
+ * magnitude (the last two say "choose a larger cell").  n = 0 gives count = 0 everywhere; m = 0 returns without a
+ * launch. */
+int rs_cloud_knn(rs_ctx *ctx, const double *pts, int64_t n, const double *queries, int64_t m,
+                 int32_t k, double max_dist, double cell, int32_t *idx, double *d2,
+                 int32_t *count, rs_knn_info *info);
+
+/* The plane fit of GetNormalOfPlaneFromPoints(points[NN_index]) (3Dvisualization.py:16-31), by
+ * its mathematics, over every point's own k nearest (itself included, max_dist = +inf).  With
+ * c = count[i], d_j = p_j - p_i, s = sum d_j, S = sum d_j d_j^T, both in list order:
+ * M = S / c - (s / c)(s / c)^T; evals[i] its eigenvalues in ascending order (cyclic Jacobi),
+ * normals[i] the unit eigenvector of the smallest, signed as rs_cloud_normals signs it.  A row
+ * with c < 3 holds NaN in both.  Two calls give the same bits. */
+int rs_cloud_knn_normals(rs_ctx *ctx, const double *pts, int64_t n, int32_t k, double cell,
+                         const double *orient, double *normals, double *evals, int32_t *count,
+                         rs_knn_info *info);
+
+/* The mean distance to the k nearest other points, 1 <= k <= RS_CLOUD_KNN_MAX_K - 1.  Of the
+ * list of the k + 1 nearest of point i the entry with index i is dropped if it is there (it is
+ * not when more than k duplicates of p_i have lower indices), otherwise the last entry;
+ * mean_dist[i] = (sum of sqrt(d2) over the remaining entries, in list order) / their number,
+ * NaN where none remains and for a non-finite point.  count[i] is the length of the list before
+ * the drop; info counts rows_short against k + 1. */
+int rs_cloud_knn_mean_dist(rs_ctx *ctx, const double *pts, int64_t n, int32_t k, double cell,
+                           double *mean_dist, int32_t *count, rs_knn_info *info);
+
+/* HIP events between the stages of the next k-NN calls (enable != 0).  Returns the last timed
+ * call's device ms per stage: box (min/max reduction), grid (cell counts), scan, scatter, query,
+ * normals, mean_dist; -1 where none (tools/bench_knn.py). */
+#define RS_CLOUD_KNN_TIMING_SLOTS 7
+int rs_cloud_knn_timing(rs_ctx *ctx, int32_t enable, double *ms);
+
 /* ------------------------------------------------------------------------------------------
  * The dense stage (dense.hip): plane-sweep depth maps and their fusion.  The reference project
  * stops at a sparse cloud; nothing here restates code of it.  No atomics, one fixed summation

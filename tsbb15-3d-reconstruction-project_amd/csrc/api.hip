@@ -125,6 +125,7 @@ extern "C" int rs_ctx_destroy(rs_ctx *c) {
   c->feat.destroy();
   c->track.destroy();
   c->cloud.destroy();
+  c->knn.destroy();
   c->dense.destroy();
   c->dense_sgm.destroy();
   c->surface.destroy();

@@ -116,6 +116,9 @@ struct rs_ctx {
   rs::StageTimer<4, RS_TRACKING_TIMING_SLOTS> track{-1.0};
   // rs_cloud_timing: between the stages of the next point-cloud calls (cloud.hip), per stage
   rs::StageTimer<5, RS_CLOUD_TIMING_SLOTS> cloud{-1.0};
+  // rs_cloud_knn_timing: between the stages of the next k-NN calls (cloud_knn.hip): box, grid,
+  // scan, scatter, query, normals, mean_dist
+  rs::StageTimer<8, RS_CLOUD_KNN_TIMING_SLOTS> knn{-1.0};
   // rs_dense_timing: around the kernel of the next dense calls (dense.hip): plane sweep,
   // consistency
   rs::StageTimer<2, RS_DENSE_TIMING_SLOTS> dense{-1.0};

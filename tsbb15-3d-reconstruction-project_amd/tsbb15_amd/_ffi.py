@@ -82,6 +82,11 @@ class CloudInfo(C.Structure):
                 ("rows_not_ok", C.c_int64)]
 
 
+class KnnInfo(C.Structure):
+    _fields_ = [("cells", C.c_int64), ("largest_cell", C.c_int64), ("tested", C.c_int64),
+                ("found", C.c_int64), ("rows_short", C.c_int64)]
+
+
 class EvalInfo(C.Structure):
     _fields_ = [("cells", C.c_int64 * 3), ("entries", C.c_int64), ("largest_cell", C.c_int64),
                 ("tests", C.c_int64), ("faces_skipped", C.c_int64), ("beyond", C.c_int64)]
@@ -102,6 +107,9 @@ BA_MAX_CAMERAS = 128
 WASH_MAX_TRACK = 128
 CLOUD_MAX_CELLS = 1 << 21
 CLOUD_STAGES = ("grid", "scan", "sort", "normals", "attributes")
+CLOUD_MAX_POINTS = 1 << 28
+CLOUD_KNN_MAX_K = 64
+CLOUD_KNN_STAGES = ("box", "grid", "scan", "scatter", "query", "normals", "mean_dist")
 EVAL_STAGES = ("bin", "scan", "scatter", "query")
 EVAL_REG_STAGES = ("transform", "query", "select", "moments")
 EVAL_REG_METRICS = ("point", "plane")   # RS_EVAL_REG_*: the index is the code
@@ -240,6 +248,13 @@ _SIGS = {
     "rs_cloud_normals": (C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_double, _dp, _dp, _i32p, _dp,
                                    C.POINTER(CloudInfo)]),
     "rs_cloud_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "rs_cloud_knn": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, C.c_int32,
+                               C.c_double, C.c_double, _i32p, _dp, _i32p, C.POINTER(KnnInfo)]),
+    "rs_cloud_knn_normals": (C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int32, C.c_double, _dp,
+                                       _dp, _dp, _i32p, C.POINTER(KnnInfo)]),
+    "rs_cloud_knn_mean_dist": (C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int32, C.c_double, _dp,
+                                         _i32p, C.POINTER(KnnInfo)]),
+    "rs_cloud_knn_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
     "rs_dense_plane_sweep": (C.c_int, [C.c_void_p, _u8p, C.c_int64, C.c_int64, _u8p, C.c_int32,
                                        _dp, _dp, _dp, C.c_int64, C.c_int32, C.c_double, _i32p,
                                        _fp, _fp, _u8p, _fp]),

@@ -8,9 +8,12 @@ the export of 3Dvisualization.py.
                           (3Dvisualization.py:16-31, :96-113), by its mathematics: fixed-radius
                           neighbourhoods, the smallest eigenvector of the neighbourhood's
                           covariance, a sign
+  * ``knn``               exact k nearest neighbours (cloud_knn.hip), what GetKNeighbours asks a
+                          kd-tree for (3Dvisualization.py:33-69); ``knn_normals`` fits the plane
+                          to them, ``knn_mean_dist`` and ``remove_outliers`` clean a cloud up
   * ``save_txt``          the ten-column file of 3Dvisualization.py:139-145 (host only)
 
-The contract of both kernels stands in include/rsamd.h.  The table-level drop-in is
+The contract of the kernels stands in include/rsamd.h.  The table-level drop-in is
 ``tsbb15_amd.tables.get3DPointsColorsAndNormals``.
 """
 from __future__ import annotations
@@ -114,6 +117,138 @@ def timing(enable, ctx=None):
     ms = np.zeros(len(_ffi.CLOUD_STAGES))
     _ffi.check(_ffi.lib().rs_cloud_timing(ctx.handle, int(enable), _ffi.ptr(ms, _d)))
     return dict(zip(_ffi.CLOUD_STAGES, ms.tolist()))
+
+
+def _knn_args(pts, k, kmax, cell):
+    pts = _ffi.f64c(pts)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError('pts must be (n, 3)')
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError('k must be an integer')
+    if not 1 <= k <= kmax:
+        raise ValueError(f'k must be in 1..{kmax} (RS_CLOUD_KNN_MAX_K = {_ffi.CLOUD_KNN_MAX_K})')
+    if len(pts) > _ffi.CLOUD_MAX_POINTS:
+        raise ValueError('more points than RS_CLOUD_MAX_POINTS = 2^28')
+    cell = 0.0 if cell is None else float(cell)
+    if not np.isfinite(cell) or cell < 0.0:
+        raise ValueError('cell must be finite and >= 0 (None or 0: the default)')
+    return pts, int(k), cell
+
+
+def _knn_info(info):
+    return {"cells": info.cells, "largest_cell": info.largest_cell, "tested": info.tested,
+            "found": info.found, "rows_short": info.rows_short}
+
+
+def knn(pts, k, queries=None, max_dist=np.inf, cell=None, ctx=None):
+    """Exact k nearest neighbours (rs_cloud_knn): what ``cKDTree(pts).query(queries, k)`` returns,
+    as squared distances.
+
+    pts (n, 3); queries (m, 3), or None for the points themselves (a point is then its own
+    first neighbour unless duplicates with lower indices come before it).  d2 of a pair is
+    dx*dx + dy*dy + dz*dz of the fp64 differences, bit for bit numpy's; a row holds the k
+    smallest pairs (d2, index) in ascending order, the lower index first where two d2 are
+    bit-equal, over the finite points with d2 <= max_dist^2.  count is the number found; the
+    slots past it hold idx -1 and d2 +inf.  A non-finite point is nobody's neighbour, a
+    non-finite query has count 0.  The result depends neither on ``cell`` (None: the largest
+    extent / round(cbrt(n))) nor on anything else about the grid.
+
+    Returns (idx (m, k) int32, d2 (m, k), count (m,) int32, info); info = dict(cells,
+    largest_cell, tested, found, rows_short).  ValueError: pts or queries not (., 3), k outside
+    1..64, max_dist NaN or negative, cell negative or not finite, or a cell that needs more than
+    2^24 cells."""
+    pts, k, cell = _knn_args(pts, k, _ffi.CLOUD_KNN_MAX_K, cell)
+    max_dist = float(max_dist)
+    if not max_dist >= 0.0:
+        raise ValueError('max_dist must be >= 0 (inf: none)')
+    qp, m = None, len(pts)
+    if queries is not None:
+        queries = _ffi.f64c(queries)
+        if queries.ndim != 2 or queries.shape[1] != 3:
+            raise ValueError('queries must be (m, 3)')
+        if len(queries) > _ffi.CLOUD_MAX_POINTS:
+            raise ValueError('more queries than RS_CLOUD_MAX_POINTS = 2^28')
+        qp, m = _ffi.ptr(queries, _d), len(queries)
+    idx = np.full((m, k), -1, dtype=np.int32)
+    d2 = np.full((m, k), np.inf)
+    count = np.zeros(m, dtype=np.int32)
+    info = _ffi.KnnInfo()
+    _ffi.check(_ffi.lib().rs_cloud_knn(
+        _ctx(ctx), _ffi.ptr(pts, _d), len(pts), qp, m, k, max_dist, cell, _ffi.ptr(idx, _i32),
+        _ffi.ptr(d2, _d), _ffi.ptr(count, _i32), _ffi.C.byref(info)))
+    return idx, d2, count, _knn_info(info)
+
+
+def knn_normals(pts, k, orient=None, cell=None, ctx=None):
+    """Surface normals from every point's own k nearest (rs_cloud_knn_normals): the plane fit of
+    GetNormalOfPlaneFromPoints(points[NN_index]) (3Dvisualization.py:33-69), by its mathematics.
+    The neighbourhood adapts to the density, which a fixed radius cannot.
+
+    The list of point i is ``knn(pts, k)``'s row i (i itself included).  evals[i] are the
+    ascending eigenvalues of the list's covariance about p_i's own mean, normals[i] the unit
+    eigenvector of the smallest, signed as ``surface_normals`` signs it.  ok[i] = count[i] >= 3;
+    the other rows hold NaN.  Two calls give the same bits.
+
+    Returns (normals, ok, count, evals, info), the shape of ``surface_normals``; info as
+    ``knn``'s."""
+    pts, k, cell = _knn_args(pts, k, _ffi.CLOUD_KNN_MAX_K, cell)
+    n = len(pts)
+    op = None
+    if orient is not None:
+        orient = _ffi.f64c(orient)
+        if orient.shape != pts.shape:
+            raise ValueError('orient must have the shape of pts')
+        op = _ffi.ptr(orient, _d)
+    normals, evals = np.empty((n, 3)), np.empty((n, 3))
+    count = np.zeros(n, dtype=np.int32)
+    info = _ffi.KnnInfo()
+    _ffi.check(_ffi.lib().rs_cloud_knn_normals(
+        _ctx(ctx), _ffi.ptr(pts, _d), n, k, cell, op, _ffi.ptr(normals, _d), _ffi.ptr(evals, _d),
+        _ffi.ptr(count, _i32), _ffi.C.byref(info)))
+    return normals, count >= 3, count, evals, _knn_info(info)
+
+
+def knn_mean_dist(pts, k, cell=None, ctx=None):
+    """The mean distance from every point to its k nearest other points
+    (rs_cloud_knn_mean_dist), 1 <= k <= 63: of the k + 1 nearest the point itself is dropped
+    (the last entry where more than k duplicates with lower indices hide it), the square roots of
+    the rest are summed in list order and divided by their number.  NaN for a non-finite point
+    and where nothing remains.  Returns (mean_dist (n,), count (n,) int32, info)."""
+    pts, k, cell = _knn_args(pts, k, _ffi.CLOUD_KNN_MAX_K - 1, cell)
+    n = len(pts)
+    mean = np.full(n, np.nan)
+    count = np.zeros(n, dtype=np.int32)
+    info = _ffi.KnnInfo()
+    _ffi.check(_ffi.lib().rs_cloud_knn_mean_dist(
+        _ctx(ctx), _ffi.ptr(pts, _d), n, k, cell, _ffi.ptr(mean, _d), _ffi.ptr(count, _i32),
+        _ffi.C.byref(info)))
+    return mean, count, _knn_info(info)
+
+
+def remove_outliers(pts, k=16, std_ratio=2.0, cell=None, ctx=None):
+    """Statistical outlier removal: a point stays when its mean distance to its k nearest other
+    points (``knn_mean_dist``) is at most mean + std_ratio * std of the finite such distances
+    (np.mean and np.std on the host).  Returns (keep (n,) bool, mean_dist (n,), threshold);
+    rows whose mean_dist is NaN are dropped.  It belongs between ``dense.fuse`` and
+    ``save_txt`` / ``surface.integrate``."""
+    std_ratio = float(std_ratio)
+    if not np.isfinite(std_ratio):
+        raise ValueError('std_ratio must be finite')
+    mean, _, _ = knn_mean_dist(pts, k, cell=cell, ctx=ctx)
+    fin = mean[np.isfinite(mean)]
+    threshold = float(np.mean(fin) + std_ratio * np.std(fin)) if len(fin) else np.nan
+    with np.errstate(invalid='ignore'):
+        keep = mean <= threshold
+    return keep, mean, threshold
+
+
+def knn_timing(enable, ctx=None):
+    """Enable / disable HIP events between the stages of the next k-NN calls
+    (rs_cloud_knn_timing); returns the last timed call's {stage: device ms}, -1 where none."""
+    ctx = ctx or _ffi.default_context()
+    ms = np.zeros(len(_ffi.CLOUD_KNN_STAGES))
+    _ffi.check(_ffi.lib().rs_cloud_knn_timing(ctx.handle, int(enable), _ffi.ptr(ms, _d)))
+    return dict(zip(_ffi.CLOUD_KNN_STAGES, ms.tolist()))
 
 
 def save_txt(path, points, colors, normals, reflectance=1.0):

@@ -329,7 +329,7 @@ def depth_points(depth, cam, K):
 
 
 def fuse(images, cams, K, depths, neighbours=2, patch=7, min_var=4.0, min_views=2,
-         rel_tol=0.01, return_maps=False, smooth=None, ctx=None):
+         rel_tol=0.01, return_maps=False, smooth=None, outliers=None, ctx=None):
     """Dense cloud of V posed views: every view is swept against its ``neighbours`` nearest
     views by index on either side, the depths are refined, ``consistency`` counts the agreeing
     views over all V maps, and the pixels with count >= min_views are kept.  ``smooth`` =
@@ -339,7 +339,9 @@ def fuse(images, cams, K, depths, neighbours=2, patch=7, min_var=4.0, min_views=
     Returns (points (N, 3), grey (N,) in [0, 1], view (N,) int32), view by view in row-major
     pixel order -- ready for ``cloud.surface_normals`` and, with the grey repeated into three
     columns, ``cloud.save_txt``.  With ``return_maps`` a dict follows: index, delta, depth
-    (V, h, w), count and keep (V, h, w)."""
+    (V, h, w), count and keep (V, h, w).  With ``outliers`` = dict(k=..., std_ratio=...) (the
+    keywords of ``cloud.remove_outliers``) the three arrays are filtered by its mask; the maps
+    are not."""
     cams = _cameras(cams, 'cams')
     V = len(cams)
     if len(images) != V:
@@ -364,6 +366,10 @@ def fuse(images, cams, K, depths, neighbours=2, patch=7, min_var=4.0, min_views=
     grey = [np.asarray(images[i], dtype=np.float64)[keep[i]] / 255.0 for i in range(V)]
     view = np.repeat(np.arange(V, dtype=np.int32), keep.reshape(V, -1).sum(axis=1))
     out = (np.concatenate(pts), np.concatenate(grey), view)
+    if outliers is not None:
+        from .cloud import remove_outliers
+        mask = remove_outliers(out[0], ctx=ctx, **outliers)[0]
+        out = tuple(a[mask] for a in out)
     return out + (maps,) if return_maps else out
 
 
