@@ -1171,8 +1171,9 @@ int rs_surface_integrate(rs_ctx *ctx, const double *depth, const float *weights,
 
 /* Marching tetrahedra on the Kuhn decomposition of every cell.  The 6 x 16 case table follows
  * from a three-line rule (csrc/surface_table.h holds it), and there are no ambiguous cases: the
- * mesh is watertight by construction.  What follows fixes every output bit except the last ulps
- * of the positions.
+ * mesh is watertight by construction.  What follows fixes every output bit, the positions
+ * included: they are evaluated as written below, no product fused with a sum, which gives the
+ * bits of the same expression in numpy.
  *   Negative node.  tsdf < 0; -0.0 and 0.0 are not negative.
  *   Valid cell.  All 8 nodes have weight >= min_weight and a finite tsdf.
  *   Tets.  Tet k (0..5) of a cell is the path 000 -> +e_a -> +e_b -> 111 with (a, b, c) the k-th
@@ -1208,6 +1209,81 @@ int rs_surface_extract(rs_ctx *ctx, const float *tsdf, const float *weight, int6
  * (vertices and faces); -1 where none (tools/bench_surface.py). */
 #define RS_SURFACE_TIMING_SLOTS 4
 int rs_surface_timing(rs_ctx *ctx, int32_t enable, double *ms);
+
+/* ------------------------------------------------------------------------------------------
+ * Surface from oriented points (cloud_knn.hip): the signed distance volume of a cloud with
+ * normals, the step of Hoppe's "surface from unorganised points" that 3Dvisualization.py stops
+ * before.  An implicit moving-least-squares field over the k nearest points within a radius; the
+ * neighbour lists never leave the chip.  Nothing here restates code of the reference.
+ *   Inputs.  pts and normals (n, 3) fp64, a support radius > 0, a neighbour cap k in
+ *   1..RS_CLOUD_KNN_MAX_K.  A point is out when any of its six numbers is not finite: it is
+ *   nobody's neighbour, as a non-finite point is in rs_cloud_knn.  Normals are used as given,
+ *   not normalised.
+ *   The list of a position X is the list rs_cloud_knn returns for the query X with
+ *   max_dist = radius over the points that are not out: the c <= k smallest pairs (bits of d2, j)
+ *   in lexicographic order, d2 = dx dx + dy dy + dz dz with d = X - p_j, the differences first,
+ *   the sum left to right, d2 <= radius * radius.
+ *   Per slot s of the list, in list order, all fp64, no product fused with a sum, every
+ *   operation in exactly this order:
+ *     u   = min(sqrt(d2_s) / radius, 1.0)
+ *     a   = 1.0 - u;  a2 = a * a
+ *     w   = (a2 * a2) * (4.0 * u + 1.0)                   Wendland C2, exactly 0 at the rim
+ *     dot = dx * n_j[0] + dy * n_j[1] + dz * n_j[2]
+ *     acc += w * dot;  sw += w;  with colours cacc[ch] += w * col_j[ch]
+ *   f = acc / sw when sw > 0, otherwise NaN (c == 0, or every neighbour exactly on the rim);
+ *   colour[ch] = cacc[ch] / sw under the same condition.  Only + - * /, sqrt and min in a fixed
+ *   order: f is bit-equal to a numpy restatement that sums slot by slot (tests/points_ref.py).
+ *   Like the lists, f depends neither on the grid nor on `cell`.
+ *   Sign.  f > 0 on the side the normals point to, the convention of rs_surface_integrate
+ *   (positive in front of the surface): rs_surface_extract's faces then face along the cloud's
+ *   normals.
+ * The grid is rs_cloud_knn's (the same kernels).  cell = 0 picks radius (1 + 2^-19), the smallest
+ * cell for which the bound B > max_dist stops the walk after ring 1 (27 cells; at cell = radius
+ * exactly B falls short of it by the factor 1 - 2^-20 and ring 2 is walked as well), raised to
+ * 2^-24 of the box's largest coordinate magnitude and then by factors of 9/8 until the grid has at
+ * most RS_CLOUD_KNN_MAX_CELLS cells.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct rs_points_info {
+  int64_t cells;         /* cells of the grid                                   */
+  int64_t largest_cell;  /* points in the fullest cell                          */
+  int64_t tested;        /* candidates whose d2 was computed                    */
+  int64_t defined;       /* outputs with a finite value                         */
+  int64_t saturated;     /* outputs whose list was full, c == k                 */
+} rs_points_info;        /* 40 bytes */
+
+/* The field on the nodes of a volume.  Node (ix, iy, iz) lies at origin + voxel (ix, iy, iz),
+ * the expression of rs_surface_integrate with the product rounded before the sum (numpy's bits).
+ * tsdf and weight are (nz, ny, nx) float, only written:
+ *   tsdf   = (float) max(-1, min(1, f / trunc)), NaN where f is
+ *   weight = (float) c, the neighbour count, exact since c <= 64.
+ * rs_surface_extract(tsdf, weight, ..., min_weight = m) then reads min_weight as "at least m
+ * points within radius of all 8 corners" (Hoppe's density test).
+ * RS_EINVAL before any launch: a null pointer, k outside 1..RS_CLOUD_KNN_MAX_K, radius or trunc
+ * not finite or <= 0, cell negative or not finite, n negative or above RS_CLOUD_MAX_POINTS, the
+ * volume limits of rs_surface_integrate, origin or voxel not finite, voxel <= 0.  Once the box
+ * is known: what rs_cloud_knn lists there.  n = 0 or no point that is not out: an all-NaN volume
+ * with weight 0 and RS_OK. */
+int rs_surface_points_volume(rs_ctx *ctx, const double *pts, const double *normals, int64_t n,
+                             int32_t k, double radius, double trunc, double cell,
+                             const double *origin, double voxel, int64_t nz, int64_t ny,
+                             int64_t nx, float *tsdf, float *weight, rs_points_info *info);
+
+/* The same field at m caller positions queries (m, 3): value[m] fp64 is the unclamped f,
+ * count[m] int32 the neighbour count c.  With colors (n, 3) fp64 given, color (m, 3) =
+ * cacc / sw, NaN where f is; colors and color are null together.  A non-finite query has count 0
+ * and NaN.  RS_EINVAL as above, and for m negative or above RS_CLOUD_MAX_POINTS; m = 0 returns
+ * without a launch. */
+int rs_surface_points_eval(rs_ctx *ctx, const double *pts, const double *normals,
+                           const double *colors, int64_t n, const double *queries, int64_t m,
+                           int32_t k, double radius, double cell, double *value, int32_t *count,
+                           double *color, rs_points_info *info);
+
+/* HIP events between the stages of the next two calls above (enable != 0).  Returns the last
+ * timed call's device ms per stage: box (the mask of the points that are out and the min/max
+ * reduction), grid (cell counts), scan, scatter, field; -1 where none (tools/bench_points.py).
+ * rs_cloud_knn_timing does not see these calls. */
+#define RS_SURFACE_POINTS_TIMING_SLOTS 5
+int rs_surface_points_timing(rs_ctx *ctx, int32_t enable, double *ms);
 
 /* ------------------------------------------------------------------------------------------
  * Colour for the mesh (surface_texture.hip): the mesh rendered into a z-buffer per view, and a

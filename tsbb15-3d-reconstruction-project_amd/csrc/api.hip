@@ -126,6 +126,7 @@ extern "C" int rs_ctx_destroy(rs_ctx *c) {
   c->track.destroy();
   c->cloud.destroy();
   c->knn.destroy();
+  c->points.destroy();
   c->dense.destroy();
   c->dense_sgm.destroy();
   c->surface.destroy();

@@ -250,6 +250,78 @@ __global__ __launch_bounds__(kKnnThreads) void k_knn_scatter(const double *pts, 
   pidx[at] = static_cast<int32_t>(i);
 }
 
+// The walk of one lane over the Chebyshev rings around the cell of its finite position q: the
+// lane's sorted list of the k smallest pairs (d2, index) within max_dist ends in its LDS columns
+// ld and li (slot s at [s * 64]); returns the list's length and adds the candidates whose d2 was
+// computed to *tested.
+__device__ __forceinline__ int knn_walk(const double *packed, const int32_t *pidx,
+                                        const int32_t *cnt, int64_t nfin, const KnnGrid &G, int k,
+                                        double max_dist, const double *q, double *ld, int *li,
+                                        unsigned long long *tested_out) {
+#pragma clang fp contract(off)
+  const double md2 = max_dist * max_dist;
+  int have = 0, worst_j = kKnnNone;
+  double worst_d = INFINITY;   // the k-th key once the list is full, (+inf, none) before
+  unsigned long long tested = 0;
+  int c[3], r0 = 0, rmax = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    c[a] = static_cast<int>(knn_coord(q[a], G.lo[a], G.cell, kKnnFar));
+    r0 = max(r0, max(-c[a], c[a] - (G.dim[a] - 1)));   // rings until this axis meets the grid
+    rmax = max(rmax, max(c[a], G.dim[a] - 1 - c[a]));  // the last ring that touches it
+  }
+  // r0 <= rmax, and rmax - r0 is below the grid's largest dimension
+  for (int r = r0; r <= rmax; ++r) {
+    if (r > 0) {
+      const double bound = static_cast<double>(r - 1) * G.cell * kKnnShrink;
+      if ((have == k && worst_d <= bound * bound) || bound > max_dist) break;
+    }
+    const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, G.dim[2] - 1);
+    const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, G.dim[1] - 1);
+    for (int z = z0; z <= z1; ++z)
+      for (int y = y0; y <= y1; ++y) {
+        // a row on the shell's z or y faces is walked whole, another only at x = c0 -+ r
+        const bool whole = z - c[2] == r || c[2] - z == r || y - c[1] == r || c[1] - y == r;
+        const long long xs = whole ? max(c[0] - r, 0) : c[0] - r;
+        const long long xe = whole ? min(c[0] + r, G.dim[0] - 1) : c[0] + r;
+        const long long step = whole ? 1 : 2ll * r;   // r > 0 where a row is not whole
+        for (long long x = xs; x <= xe; x += step) {
+          if (x < 0 || x >= G.dim[0]) continue;
+          const int64_t cell = (static_cast<int64_t>(z) * G.dim[1] + y) * G.dim[0] + x;
+          const int64_t b = cnt[cell], e = min(static_cast<int64_t>(cnt[cell + 1]), nfin);
+          for (int64_t at = b; at < e; ++at) {
+            const double *p = packed + 3 * at;
+            const double d0 = q[0] - p[0], d1 = q[1] - p[1], dz = q[2] - p[2];
+            const double d = d0 * d0 + d1 * d1 + dz * dz;
+            ++tested;
+            if (!(d <= md2 && d <= worst_d)) continue;   // most candidates leave here
+            const int j = pidx[at];
+            if (!(d < worst_d || j < worst_j)) continue;
+            // insertion from the tail; a full list loses its last entry
+            int pos = have < k ? have : k - 1;
+            while (pos > 0) {
+              const double pd = ld[(pos - 1) * kKnnWave];
+              const int pj = li[(pos - 1) * kKnnWave];
+              if (pd < d || (pd == d && pj < j)) break;
+              ld[pos * kKnnWave] = pd;
+              li[pos * kKnnWave] = pj;
+              --pos;
+            }
+            ld[pos * kKnnWave] = d;
+            li[pos * kKnnWave] = j;
+            if (have < k) ++have;
+            if (have == k) {
+              worst_d = ld[(k - 1) * kKnnWave];
+              worst_j = li[(k - 1) * kKnnWave];
+            }
+          }
+        }
+      }
+  }
+  *tested_out += tested;
+  return have;
+}
+
 // One lane per query.  queries == null: lane t takes entry t of the scattered list (cell order,
 // so a wave walks the same cells) and writes to that point's own row; otherwise query t of m.
 // Dynamic LDS: k * 64 doubles, then k * 64 ints.  d2 == null (the plane fit): only idx and count
@@ -274,67 +346,10 @@ __global__ __launch_bounds__(kKnnWave) void k_knn_query(
     if (!queries) row = pidx[t];
   }
   const bool finite = knn_finite3(q);
-  const double md2 = max_dist * max_dist;
-  int have = 0, worst_j = kKnnNone;
-  double worst_d = INFINITY;   // the k-th key once the list is full, (+inf, none) before
+  int have = 0;
   unsigned long long tested = 0;
-  if (active && finite) {
-    int c[3], r0 = 0, rmax = 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      c[a] = static_cast<int>(knn_coord(q[a], G.lo[a], G.cell, kKnnFar));
-      r0 = max(r0, max(-c[a], c[a] - (G.dim[a] - 1)));   // rings until this axis meets the grid
-      rmax = max(rmax, max(c[a], G.dim[a] - 1 - c[a]));  // the last ring that touches it
-    }
-    // r0 <= rmax, and rmax - r0 is below the grid's largest dimension
-    for (int r = r0; r <= rmax; ++r) {
-      if (r > 0) {
-        const double bound = static_cast<double>(r - 1) * G.cell * kKnnShrink;
-        if ((have == k && worst_d <= bound * bound) || bound > max_dist) break;
-      }
-      const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, G.dim[2] - 1);
-      const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, G.dim[1] - 1);
-      for (int z = z0; z <= z1; ++z)
-        for (int y = y0; y <= y1; ++y) {
-          // a row on the shell's z or y faces is walked whole, another only at x = c0 -+ r
-          const bool whole = z - c[2] == r || c[2] - z == r || y - c[1] == r || c[1] - y == r;
-          const long long xs = whole ? max(c[0] - r, 0) : c[0] - r;
-          const long long xe = whole ? min(c[0] + r, G.dim[0] - 1) : c[0] + r;
-          const long long step = whole ? 1 : 2ll * r;   // r > 0 where a row is not whole
-          for (long long x = xs; x <= xe; x += step) {
-            if (x < 0 || x >= G.dim[0]) continue;
-            const int64_t cell = (static_cast<int64_t>(z) * G.dim[1] + y) * G.dim[0] + x;
-            const int64_t b = cnt[cell], e = min(static_cast<int64_t>(cnt[cell + 1]), nfin);
-            for (int64_t at = b; at < e; ++at) {
-              const double *p = packed + 3 * at;
-              const double d0 = q[0] - p[0], d1 = q[1] - p[1], dz = q[2] - p[2];
-              const double d = d0 * d0 + d1 * d1 + dz * dz;
-              ++tested;
-              if (!(d <= md2 && d <= worst_d)) continue;   // most candidates leave here
-              const int j = pidx[at];
-              if (!(d < worst_d || j < worst_j)) continue;
-              // insertion from the tail; a full list loses its last entry
-              int pos = have < k ? have : k - 1;
-              while (pos > 0) {
-                const double pd = ld[(pos - 1) * kKnnWave];
-                const int pj = li[(pos - 1) * kKnnWave];
-                if (pd < d || (pd == d && pj < j)) break;
-                ld[pos * kKnnWave] = pd;
-                li[pos * kKnnWave] = pj;
-                --pos;
-              }
-              ld[pos * kKnnWave] = d;
-              li[pos * kKnnWave] = j;
-              if (have < k) ++have;
-              if (have == k) {
-                worst_d = ld[(k - 1) * kKnnWave];
-                worst_j = li[(k - 1) * kKnnWave];
-              }
-            }
-          }
-        }
-    }
-  }
+  if (active && finite)
+    have = knn_walk(packed, pidx, cnt, nfin, G, k, max_dist, q, ld, li, &tested);
   for (int off = 32; off > 0; off >>= 1) tested += __shfl_xor(tested, off);
   if (lane == 0 && tested > 0) atomicAdd(&stats[kKnnTested], tested);
   if (!active) return;
@@ -437,6 +452,123 @@ __global__ __launch_bounds__(kKnnThreads) void k_knn_mean(int64_t n, int rows, c
   mean[i] = c > 1 ? sum / static_cast<double>(c - 1) : knn_nan();
 }
 
+// ---- surface from oriented points (rs_surface_points_volume, rs_surface_points_eval) ----
+
+// How the lanes of a wave map to the nodes of a volume: 1, a brick of 4 x 4 x 4 nodes, so that a
+// wave's lanes walk the same cells; 0, a run of 64 nodes along x.  Measured: DESIGN.md section 21.
+#ifndef RS_POINTS_BRICK
+#define RS_POINTS_BRICK 1
+#endif
+constexpr int kPtsBrickX = RS_POINTS_BRICK ? 4 : 64, kPtsBrickYZ = RS_POINTS_BRICK ? 4 : 1;
+
+// further stats words
+constexpr int kPtsDefined = 2, kPtsSaturated = 3;
+
+struct PtsVolume {
+  double o[3], voxel;
+  int n[3];   // nx, ny, nz
+  int b[2];   // bricks along x and y
+};
+
+// A point whose normal is not finite is out: its coordinates become NaN in the copy the grid is
+// built from, where the k-NN kernels drop it like any non-finite point.
+__global__ __launch_bounds__(kKnnThreads) void k_points_mask(const double *pts,
+                                                             const double *normals, int64_t n,
+                                                             double *out) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kKnnThreads + threadIdx.x;
+  if (i >= n) return;
+  const bool in = knn_finite3(normals + 3 * i);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) out[3 * i + a] = in ? pts[3 * i + a] : knn_nan();
+}
+
+// One lane per node (kVolume: workgroup w is brick w of the volume) or per query (lane t of m),
+// one wave per workgroup.  k_knn_query's walk with max_dist = radius leaves the sorted list in
+// the lane's LDS columns (dynamic LDS: k * 64 doubles, then k * 64 ints); the slot loop of the
+// contract consumes it where it stands and 8 bytes per node leave the chip.  `pts` is the masked
+// copy, so a listed index names a point with six finite numbers; it is below n because k_knn_
+// scatter wrote it from a lane index below n.
+template <bool kVolume>
+__global__ __launch_bounds__(kKnnWave) void k_points_field(
+    const double *packed, const int32_t *pidx, const int32_t *cnt, int64_t nfin, const double *pts,
+    const double *normals, const double *colors, int64_t n, const double *queries, int64_t m,
+    PtsVolume V, KnnGrid G, int k, double radius, double trunc, float *tsdf, float *weight,
+    double *value, int32_t *count, double *color, unsigned long long *stats) {
+#pragma clang fp contract(off)
+  extern __shared__ double s_knn[];
+  const int lane = threadIdx.x;
+  double *ld = s_knn + lane;                                          // slot s at ld[s * 64]
+  int *li = reinterpret_cast<int *>(s_knn + static_cast<size_t>(k) * kKnnWave) + lane;
+  int64_t out = -1;   // the lane's output element, -1: none
+  double q[3] = {0.0, 0.0, 0.0};
+  if (kVolume) {
+    const int64_t w = blockIdx.x, rest = w / V.b[0];
+    const int bx = static_cast<int>(w - rest * V.b[0]), bz = static_cast<int>(rest / V.b[1]);
+    const int by = static_cast<int>(rest - static_cast<int64_t>(bz) * V.b[1]);
+    const int lx = lane % kPtsBrickX, ly = lane / kPtsBrickX % kPtsBrickYZ,
+              lz = lane / kPtsBrickX / kPtsBrickYZ;
+    const int i[3] = {bx * kPtsBrickX + lx, by * kPtsBrickYZ + ly, bz * kPtsBrickYZ + lz};
+    if (i[0] < V.n[0] && i[1] < V.n[1] && i[2] < V.n[2]) {
+      out = (static_cast<int64_t>(i[2]) * V.n[1] + i[1]) * V.n[0] + i[0];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) q[a] = V.o[a] + V.voxel * static_cast<double>(i[a]);
+    }
+  } else {
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * kKnnWave + lane;
+    if (t < m) {
+      out = t;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) q[a] = queries[3 * t + a];
+    }
+  }
+  int have = 0;
+  unsigned long long tested = 0;
+  if (out >= 0 && knn_finite3(q))
+    have = knn_walk(packed, pidx, cnt, nfin, G, k, radius, q, ld, li, &tested);
+  double acc = 0.0, sw = 0.0, cacc[3] = {0.0, 0.0, 0.0};
+  for (int s = 0; s < have; ++s) {
+    const int64_t j = li[s * kKnnWave];
+    if (j < 0 || j >= n) continue;   // never: the list holds point indices
+    const double *p = pts + 3 * j, *nj = normals + 3 * j;
+    const double d0 = q[0] - p[0], d1 = q[1] - p[1], dz = q[2] - p[2];
+    const double u = fmin(sqrt(ld[s * kKnnWave]) / radius, 1.0);
+    const double a = 1.0 - u, a2 = a * a;
+    const double wt = (a2 * a2) * (4.0 * u + 1.0);
+    const double dot = d0 * nj[0] + d1 * nj[1] + dz * nj[2];
+    acc += wt * dot;
+    sw += wt;
+    if (!kVolume && colors) {
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) cacc[ch] += wt * colors[3 * j + ch];
+    }
+  }
+  const bool some = sw > 0.0;
+  const double f = some ? acc / sw : knn_nan();
+  const unsigned long long defined = __popcll(__ballot(out >= 0 && isfinite(f)));
+  const unsigned long long full = __popcll(__ballot(out >= 0 && have == k));
+  for (int off = 32; off > 0; off >>= 1) tested += __shfl_xor(tested, off);
+  if (lane == 0) {
+    if (tested > 0) atomicAdd(&stats[kKnnTested], tested);
+    if (defined > 0) atomicAdd(&stats[kPtsDefined], defined);
+    if (full > 0) atomicAdd(&stats[kPtsSaturated], full);
+  }
+  if (out < 0) return;
+  if (kVolume) {
+    double t = f / trunc;   // a NaN passes both comparisons
+    t = t > 1.0 ? 1.0 : t;
+    t = t < -1.0 ? -1.0 : t;
+    tsdf[out] = some ? static_cast<float>(t) : __int_as_float(0x7fc00000);
+    weight[out] = static_cast<float>(have);
+  } else {
+    value[out] = f;
+    count[out] = have;
+    if (color) {
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) color[3 * out + ch] = some ? cacc[ch] / sw : knn_nan();
+    }
+  }
+}
+
 }  // namespace rsd
 
 static_assert(RS_CLOUD_KNN_TIMING_SLOTS == 7, "box, grid, scan, scatter, query, normals, mean_dist");
@@ -467,6 +599,62 @@ void knn_fill_empty(KnnUse use, int64_t n, int64_t m, int K, const KnnOut &o) {
     for (int64_t i = 0; i < 3 * n; ++i) o.normals[i] = o.evals[i] = NAN;
   if (use == kKnnMean)
     for (int64_t i = 0; i < n; ++i) o.mean[i] = NAN;
+}
+
+// The grid over the box [lo, hi] of nfin > 0 finite points (box: what k_knn_box_fold leaves).
+// cell == 0 picks the default: rs_cloud_knn's with radius == 0, that of the surface from points
+// with its support radius.  RS_EINVAL with the message of the rule that failed.
+int knn_size_grid(const double *box, int64_t nfin, double cell, double radius, rsd::KnnGrid *G) {
+  double ext_max = 0.0, mag = 0.0;
+  for (int a = 0; a < 3; ++a) {
+    const double ext = box[3 + a] - box[a];
+    if (!std::isfinite(ext)) return fail(RS_EINVAL, "the extent of the cloud's box is not finite");
+    ext_max = std::fmax(ext_max, ext);
+    mag = std::fmax(mag, std::fmax(std::fabs(box[a]), std::fabs(box[3 + a])));
+    G->lo[a] = box[a];
+  }
+  if (cell == 0.0 && radius > 0.0) {
+    // surface from points: a hair above the support radius, so that B = cell (1 - 2^-20) exceeds
+    // it and the walk ends after ring 1, 27 cells (at cell == radius exactly it takes ring 2 as
+    // well, 125 cells: measured); raised to the floor and until the grid fits
+    cell = std::fmax(radius * (1.0 + 1.0 / 524288.0), mag / 16777216.0);
+    for (;;) {
+      double cells = 1.0, side = 0.0;
+      for (int a = 0; a < 3; ++a) {
+        const double nd = std::floor((box[3 + a] - box[a]) / cell) + 1.0;
+        side = std::fmax(side, nd);
+        cells *= nd;
+      }
+      if (side <= static_cast<double>(RS_CLOUD_KNN_MAX_CELLS) &&
+          cells <= static_cast<double>(RS_CLOUD_KNN_MAX_CELLS))
+        break;
+      cell *= 1.125;
+    }
+  } else if (cell == 0.0) {
+    const double g = std::fmin(std::fmax(std::round(std::cbrt(static_cast<double>(nfin))), 1.0),
+                               256.0);
+    cell = std::fmax(ext_max / g, mag / 16777216.0);
+    if (!(ext_max > 0.0) || !(cell > 0.0)) cell = mag > 0.0 ? mag : 1.0;   // one cell
+  }
+  double ncell_d = 1.0;
+  for (int a = 0; a < 3; ++a) {
+    const double nd = std::floor((box[3 + a] - box[a]) / cell) + 1.0;
+    if (!(nd <= static_cast<double>(RS_CLOUD_KNN_MAX_CELLS)))
+      return fail(RS_EINVAL,
+                  "the grid has more than RS_CLOUD_KNN_MAX_CELLS = 2^24 cells: choose a larger "
+                  "cell");
+    G->dim[a] = static_cast<int>(nd);
+    ncell_d *= nd;
+  }
+  if (ncell_d > static_cast<double>(RS_CLOUD_KNN_MAX_CELLS))
+    return fail(RS_EINVAL,
+                "the grid has more than RS_CLOUD_KNN_MAX_CELLS = 2^24 cells: choose a larger cell");
+  if (cell < mag / 16777216.0)
+    return fail(RS_EINVAL,
+                "cell is below 2^-24 of the box's largest coordinate magnitude: choose a larger "
+                "cell");
+  G->cell = cell;
+  return RS_OK;
 }
 
 // The grid, the query with lists K wide and, for the consumers, their kernel.  The arguments have
@@ -529,38 +717,7 @@ int knn_run(rs_ctx *c, KnnUse use, const double *pts, int64_t n, const double *q
     return RS_OK;
   }
   rsd::KnnGrid G;
-  double ext_max = 0.0, mag = 0.0;
-  for (int a = 0; a < 3; ++a) {
-    const double ext = box[3 + a] - box[a];
-    if (!std::isfinite(ext)) return fail(RS_EINVAL, "the extent of the cloud's box is not finite");
-    ext_max = std::fmax(ext_max, ext);
-    mag = std::fmax(mag, std::fmax(std::fabs(box[a]), std::fabs(box[3 + a])));
-    G.lo[a] = box[a];
-  }
-  if (cell == 0.0) {
-    const double g = std::fmin(std::fmax(std::round(std::cbrt(static_cast<double>(nfin))), 1.0),
-                               256.0);
-    cell = std::fmax(ext_max / g, mag / 16777216.0);
-    if (!(ext_max > 0.0) || !(cell > 0.0)) cell = mag > 0.0 ? mag : 1.0;   // one cell
-  }
-  double ncell_d = 1.0;
-  for (int a = 0; a < 3; ++a) {
-    const double nd = std::floor((box[3 + a] - box[a]) / cell) + 1.0;
-    if (!(nd <= static_cast<double>(RS_CLOUD_KNN_MAX_CELLS)))
-      return fail(RS_EINVAL,
-                  "the grid has more than RS_CLOUD_KNN_MAX_CELLS = 2^24 cells: choose a larger "
-                  "cell");
-    G.dim[a] = static_cast<int>(nd);
-    ncell_d *= nd;
-  }
-  if (ncell_d > static_cast<double>(RS_CLOUD_KNN_MAX_CELLS))
-    return fail(RS_EINVAL,
-                "the grid has more than RS_CLOUD_KNN_MAX_CELLS = 2^24 cells: choose a larger cell");
-  if (cell < mag / 16777216.0)
-    return fail(RS_EINVAL,
-                "cell is below 2^-24 of the box's largest coordinate magnitude: choose a larger "
-                "cell");
-  G.cell = cell;
+  if ((st = knn_size_grid(box, nfin, cell, 0.0, &G))) return st;
   const int64_t ncell = static_cast<int64_t>(G.dim[0]) * G.dim[1] * G.dim[2];
   const int nchunks = static_cast<int>((ncell + rsd::kKnnScanChunk - 1) / rsd::kKnnScanChunk);
   const auto b_cnt = L.add<int32_t>(static_cast<size_t>(ncell) + 1);
@@ -715,5 +872,259 @@ extern "C" int rs_cloud_knn_timing(rs_ctx *c, int32_t enable, double *ms) {
   const int st = c->knn.enable(enable != 0);
   if (st) return st;
   c->knn.copy_out(ms);
+  return RS_OK;
+}
+
+// ---- surface from oriented points ----
+
+static_assert(RS_SURFACE_POINTS_TIMING_SLOTS == 5, "box, grid, scan, scatter, field");
+static_assert(sizeof(rs_points_info) == 40, "rs_points_info");
+
+namespace {
+
+struct PtsOut {
+  float *tsdf = nullptr, *weight = nullptr;                      // volume
+  double *value = nullptr, *color = nullptr;                     // eval
+  int32_t *count = nullptr;                                      // eval
+};
+
+// what a call without a point that is not out returns: NaN everywhere, no neighbour
+void points_fill_empty(bool volume, int64_t m, const PtsOut &o) {
+  for (int64_t i = 0; i < m; ++i) {
+    if (volume) {
+      o.tsdf[i] = NAN;
+      o.weight[i] = 0.0f;
+    } else {
+      o.value[i] = NAN;
+      o.count[i] = 0;
+      if (o.color) o.color[3 * i] = o.color[3 * i + 1] = o.color[3 * i + 2] = NAN;
+    }
+  }
+}
+
+// The grid of knn_run over the points that are not out, then the field on the m nodes of the
+// volume V (queries == null) or at the m queries.  The arguments have been checked.
+int points_run(rs_ctx *c, const double *pts, const double *normals, const double *colors,
+               int64_t n, const double *queries, int64_t m, const rsd::PtsVolume &V, int K,
+               double radius, double trunc, double cell, const PtsOut &o, rs_points_info *info) {
+  using U64 = unsigned long long;
+  const bool volume = queries == nullptr;
+  const int nb = static_cast<int>(std::min<int64_t>(rsd::kKnnBoxBlocks,
+                                                    rs::blocks(n, rsd::kKnnThreads)));
+  const size_t sn = static_cast<size_t>(n), sm = static_cast<size_t>(m);
+  // the inputs go up and the box comes down before the grid can be sized ...
+  rs::Layout L;
+  const auto b_pts = L.add<double>(3 * sn), b_nrm = L.add<double>(3 * sn);
+  const auto b_col = L.add<double>(colors ? 3 * sn : 0);
+  const auto b_q = L.add<double>(volume ? 0 : 3 * sm);
+  const auto b_in = L.add<double>(3 * sn);   // the points that are not out, NaN rows for the rest
+  const auto b_part = L.add<double>(7 * static_cast<size_t>(nb)), b_box = L.add<double>(8);
+  // ... the results and the scattered points do not depend on it
+  const auto b_tsdf = L.add<float>(volume ? sm : 0), b_weight = L.add<float>(volume ? sm : 0);
+  const auto b_value = L.add<double>(volume ? 0 : sm);
+  const auto b_count = L.add<int32_t>(volume ? 0 : sm);
+  const auto b_color = L.add<double>(colors ? 3 * sm : 0);
+  const auto b_stats = L.add<U64>(8);
+  const auto b_packed = L.add<double>(3 * sn);
+  const auto b_pidx = L.add<int32_t>(sn), b_cell_of = L.add<int32_t>(sn);
+  HIP_TRY(hipSetDevice(c->device));
+  int st = L.bind(c);
+  if (st) return st;
+
+  hipStream_t s = c->stream;
+  const dim3 blk(rsd::kKnnThreads), sblk(rsd::kKnnScanThreads);
+  auto upload = [&]() -> int {
+    HIP_TRY(hipMemcpyAsync(b_pts.dev(), pts, b_pts.bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(b_nrm.dev(), normals, b_nrm.bytes, hipMemcpyHostToDevice, s));
+    if (colors)
+      HIP_TRY(hipMemcpyAsync(b_col.dev(), colors, b_col.bytes, hipMemcpyHostToDevice, s));
+    if (!volume) HIP_TRY(hipMemcpyAsync(b_q.dev(), queries, b_q.bytes, hipMemcpyHostToDevice, s));
+    return RS_OK;
+  };
+  auto mask = [&]() {
+    hipLaunchKernelGGL(rsd::k_points_mask, dim3(rs::blocks(n, rsd::kKnnThreads)), blk, 0, s,
+                       b_pts.dev(), b_nrm.dev(), n, b_in.dev());
+  };
+  if ((st = upload())) return st;
+  if ((st = c->points.mark(0, s))) return st;
+  mask();
+  hipLaunchKernelGGL(rsd::k_knn_box, dim3(nb), blk, 0, s, b_in.dev(), n, b_part.dev());
+  hipLaunchKernelGGL(rsd::k_knn_box_fold, dim3(1), dim3(rsd::kKnnWave), 0, s, b_part.dev(), nb,
+                     b_box.dev());
+  HIP_TRY(hipGetLastError());
+  if ((st = c->points.mark(1, s))) return st;
+  double box[7];
+  HIP_TRY(hipMemcpyAsync(box, b_box.dev(), sizeof(box), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if ((st = c->points.read(0, 0, 1))) return st;
+
+  const int64_t nfin = static_cast<int64_t>(box[6]);
+  if (nfin <= 0) {
+    points_fill_empty(volume, m, o);
+    return RS_OK;
+  }
+  rsd::KnnGrid G;
+  if ((st = knn_size_grid(box, nfin, cell, radius, &G))) return st;
+  const int64_t ncell = static_cast<int64_t>(G.dim[0]) * G.dim[1] * G.dim[2];
+  const int nchunks = static_cast<int>((ncell + rsd::kKnnScanChunk - 1) / rsd::kKnnScanChunk);
+  const auto b_cnt = L.add<int32_t>(static_cast<size_t>(ncell) + 1);
+  const auto b_fill = L.add<int32_t>(static_cast<size_t>(ncell));
+  const auto b_sums = L.add<int32_t>(static_cast<size_t>(nchunks) + 1);
+  // a scratch that has to grow is allocated anew without a copy: the inputs go up again
+  const bool kept = c->scratch_bytes >= L.total() + 256;
+  if ((st = L.bind(c))) return st;
+  if (!kept) {
+    if ((st = upload())) return st;
+    mask();
+  }
+
+  HIP_TRY(hipMemsetAsync(b_stats.dev(), 0, b_stats.bytes, s));
+  HIP_TRY(hipMemsetAsync(b_cnt.dev(), 0, L.span(b_cnt, b_sums), s));   // cnt and fill
+  if ((st = c->points.mark(2, s))) return st;
+  hipLaunchKernelGGL(rsd::k_knn_count, dim3(rs::blocks(n, rsd::kKnnThreads)), blk, 0, s,
+                     b_in.dev(), n, G, b_cell_of.dev(), b_cnt.dev(), 0, nullptr, nullptr, nullptr);
+  if ((st = c->points.mark(3, s))) return st;
+  hipLaunchKernelGGL(rsd::k_knn_scan_chunks, dim3(nchunks), sblk, 0, s, b_cnt.dev(), ncell,
+                     b_sums.dev(), b_stats.dev());
+  hipLaunchKernelGGL(rsd::k_knn_scan, dim3(1), sblk, 0, s, b_sums.dev(),
+                     static_cast<int64_t>(nchunks));
+  hipLaunchKernelGGL(rsd::k_knn_scan_add, dim3(nchunks), sblk, 0, s, b_cnt.dev(), ncell,
+                     b_sums.dev(), nchunks);
+  if ((st = c->points.mark(4, s))) return st;
+  hipLaunchKernelGGL(rsd::k_knn_scatter, dim3(rs::blocks(n, rsd::kKnnThreads)), blk, 0, s,
+                     b_in.dev(), n, b_cell_of.dev(), b_cnt.dev(), b_fill.dev(), nfin,
+                     b_packed.dev(), b_pidx.dev());
+  if ((st = c->points.mark(5, s))) return st;
+  const size_t lds = 768 * static_cast<size_t>(K);
+  if (volume) {
+    const unsigned bricks = static_cast<unsigned>(
+        static_cast<int64_t>(V.b[0]) * V.b[1] * rs::blocks(V.n[2], rsd::kPtsBrickYZ));
+    hipLaunchKernelGGL(rsd::k_points_field<true>, dim3(bricks), dim3(rsd::kKnnWave), lds, s,
+                       b_packed.dev(), b_pidx.dev(), b_cnt.dev(), nfin, b_in.dev(), b_nrm.dev(),
+                       nullptr, n, nullptr, m, V, G, K, radius, trunc, b_tsdf.dev(),
+                       b_weight.dev(), nullptr, nullptr, nullptr, b_stats.dev());
+  } else {
+    hipLaunchKernelGGL(rsd::k_points_field<false>, dim3(rs::blocks(m, rsd::kKnnWave)),
+                       dim3(rsd::kKnnWave), lds, s, b_packed.dev(), b_pidx.dev(), b_cnt.dev(),
+                       nfin, b_in.dev(), b_nrm.dev(), colors ? b_col.dev() : nullptr, n,
+                       b_q.dev(), m, V, G, K, radius, trunc, nullptr, nullptr, b_value.dev(),
+                       b_count.dev(), colors ? b_color.dev() : nullptr, b_stats.dev());
+  }
+  HIP_TRY(hipGetLastError());
+  if ((st = c->points.mark(6, s))) return st;
+  U64 stats[8];
+  if (volume) {
+    HIP_TRY(hipMemcpyAsync(o.tsdf, b_tsdf.dev(), b_tsdf.bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(o.weight, b_weight.dev(), b_weight.bytes, hipMemcpyDeviceToHost, s));
+  } else {
+    HIP_TRY(hipMemcpyAsync(o.value, b_value.dev(), b_value.bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(o.count, b_count.dev(), b_count.bytes, hipMemcpyDeviceToHost, s));
+    if (colors)
+      HIP_TRY(hipMemcpyAsync(o.color, b_color.dev(), b_color.bytes, hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(hipMemcpyAsync(stats, b_stats.dev(), b_stats.bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int k = 1; k < 5; ++k)
+    if ((st = c->points.read(k, k + 1, k + 2))) return st;
+
+  info->cells = ncell;
+  info->largest_cell = static_cast<int64_t>(stats[rsd::kKnnLargest]);
+  info->tested = static_cast<int64_t>(stats[rsd::kKnnTested]);
+  info->defined = static_cast<int64_t>(stats[rsd::kPtsDefined]);
+  info->saturated = static_cast<int64_t>(stats[rsd::kPtsSaturated]);
+  return RS_OK;
+}
+
+int points_check(const rs_ctx *c, const rs_points_info *info, const double *pts,
+                 const double *normals, int64_t n, int32_t k, double radius, double cell) {
+  if (!c || !info) return fail(RS_EINVAL, "null pointer");
+  if (k < 1 || k > RS_CLOUD_KNN_MAX_K)
+    return fail(RS_EINVAL, "k must be in 1..RS_CLOUD_KNN_MAX_K = 64");
+  if (n < 0) return fail(RS_EINVAL, "negative size");
+  if (n > RS_CLOUD_MAX_POINTS)
+    return fail(RS_EINVAL, "more points or queries than RS_CLOUD_MAX_POINTS = 2^28");
+  if (n > 0 && (!pts || !normals)) return fail(RS_EINVAL, "null pointer: pts or normals");
+  if (!std::isfinite(radius) || !(radius > 0.0))
+    return fail(RS_EINVAL, "radius must be finite and > 0");
+  if (!std::isfinite(cell) || cell < 0.0)
+    return fail(RS_EINVAL, "cell must be finite and >= 0 (0: the default)");
+  return RS_OK;
+}
+
+}  // namespace
+
+extern "C" int rs_surface_points_volume(rs_ctx *c, const double *pts, const double *normals,
+                                        int64_t n, int32_t k, double radius, double trunc,
+                                        double cell, const double *origin, double voxel,
+                                        int64_t nz, int64_t ny, int64_t nx, float *tsdf,
+                                        float *weight, rs_points_info *info) {
+  int st = points_check(c, info, pts, normals, n, k, radius, cell);
+  if (st) return st;
+  if (!origin || !tsdf || !weight) return fail(RS_EINVAL, "null pointer");
+  if (!std::isfinite(trunc) || !(trunc > 0.0))
+    return fail(RS_EINVAL, "trunc must be finite and > 0");
+  if (nx < 1 || ny < 1 || nz < 1 || nx > RS_SURFACE_MAX_SIDE || ny > RS_SURFACE_MAX_SIDE ||
+      nz > RS_SURFACE_MAX_SIDE)
+    return fail(RS_EINVAL, "each side of the volume must be in 1..RS_SURFACE_MAX_SIDE = 2048");
+  if (nx * ny * nz > RS_SURFACE_MAX_NODES)
+    return fail(RS_EINVAL, "a volume of more than RS_SURFACE_MAX_NODES = 2^27 nodes");
+  if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]) ||
+      !std::isfinite(voxel) || !(voxel > 0.0))
+    return fail(RS_EINVAL, "origin and voxel must be finite, voxel > 0");
+  const rs_points_info zero = {0, 0, 0, 0, 0};
+  *info = zero;
+  PtsOut o;
+  o.tsdf = tsdf;
+  o.weight = weight;
+  const int64_t m = nx * ny * nz;
+  if (n == 0) {
+    points_fill_empty(true, m, o);
+    return RS_OK;
+  }
+  rsd::PtsVolume V;
+  for (int a = 0; a < 3; ++a) V.o[a] = origin[a];
+  V.voxel = voxel;
+  V.n[0] = static_cast<int>(nx);
+  V.n[1] = static_cast<int>(ny);
+  V.n[2] = static_cast<int>(nz);
+  V.b[0] = static_cast<int>(rs::blocks(nx, rsd::kPtsBrickX));
+  V.b[1] = static_cast<int>(rs::blocks(ny, rsd::kPtsBrickYZ));
+  return points_run(c, pts, normals, nullptr, n, nullptr, m, V, k, radius, trunc, cell, o, info);
+}
+
+extern "C" int rs_surface_points_eval(rs_ctx *c, const double *pts, const double *normals,
+                                      const double *colors, int64_t n, const double *queries,
+                                      int64_t m, int32_t k, double radius, double cell,
+                                      double *value, int32_t *count, double *color,
+                                      rs_points_info *info) {
+  int st = points_check(c, info, pts, normals, n, k, radius, cell);
+  if (st) return st;
+  if (m < 0) return fail(RS_EINVAL, "negative size");
+  if (m > RS_CLOUD_MAX_POINTS)
+    return fail(RS_EINVAL, "more points or queries than RS_CLOUD_MAX_POINTS = 2^28");
+  if ((colors == nullptr) != (color == nullptr))
+    return fail(RS_EINVAL, "colors and color are given together or not at all");
+  const rs_points_info zero = {0, 0, 0, 0, 0};
+  *info = zero;
+  if (m == 0) return RS_OK;
+  if (!queries || !value || !count) return fail(RS_EINVAL, "null pointer");
+  PtsOut o;
+  o.value = value;
+  o.count = count;
+  o.color = color;
+  if (n == 0) {
+    points_fill_empty(false, m, o);
+    return RS_OK;
+  }
+  rsd::PtsVolume V = {};
+  return points_run(c, pts, normals, colors, n, queries, m, V, k, radius, 1.0, cell, o, info);
+}
+
+extern "C" int rs_surface_points_timing(rs_ctx *c, int32_t enable, double *ms) {
+  if (!c || !ms) return fail(RS_EINVAL, "null pointer");
+  HIP_TRY(hipSetDevice(c->device));
+  const int st = c->points.enable(enable != 0);
+  if (st) return st;
+  c->points.copy_out(ms);
   return RS_OK;
 }

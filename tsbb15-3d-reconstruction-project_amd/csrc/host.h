@@ -119,6 +119,9 @@ struct rs_ctx {
   // rs_cloud_knn_timing: between the stages of the next k-NN calls (cloud_knn.hip): box, grid,
   // scan, scatter, query, normals, mean_dist
   rs::StageTimer<8, RS_CLOUD_KNN_TIMING_SLOTS> knn{-1.0};
+  // rs_surface_points_timing: between the stages of the next surface-from-points calls
+  // (cloud_knn.hip): box, grid, scan, scatter, field
+  rs::StageTimer<7, RS_SURFACE_POINTS_TIMING_SLOTS> points{-1.0};
   // rs_dense_timing: around the kernel of the next dense calls (dense.hip): plane sweep,
   // consistency
   rs::StageTimer<2, RS_DENSE_TIMING_SLOTS> dense{-1.0};

@@ -306,6 +306,8 @@ __global__ __launch_bounds__(kSurfThreads) void k_surface_vertices(SurfGrid G, c
                                                                    const uint8_t *nmask,
                                                                    const int32_t *vbase,
                                                                    double *vertices) {
+  // no product fused with a sum: the positions are the bits of the same expression in numpy
+#pragma clang fp contract(off)
   SurfNode p;
   if (!surf_node(G, &p)) return;
   const int mask = nmask[p.t];

@@ -87,6 +87,11 @@ class KnnInfo(C.Structure):
                 ("found", C.c_int64), ("rows_short", C.c_int64)]
 
 
+class PointsInfo(C.Structure):
+    _fields_ = [("cells", C.c_int64), ("largest_cell", C.c_int64), ("tested", C.c_int64),
+                ("defined", C.c_int64), ("saturated", C.c_int64)]
+
+
 class EvalInfo(C.Structure):
     _fields_ = [("cells", C.c_int64 * 3), ("entries", C.c_int64), ("largest_cell", C.c_int64),
                 ("tests", C.c_int64), ("faces_skipped", C.c_int64), ("beyond", C.c_int64)]
@@ -275,6 +280,14 @@ _SIGS = {
                                      C.c_double, C.c_double, _dp, C.c_int64, _i32p, C.c_int64,
                                      _i64p, _i64p]),
     "rs_surface_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "rs_surface_points_volume": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int64, C.c_int32, C.c_double,
+                                           C.c_double, C.c_double, _dp, C.c_double, C.c_int64,
+                                           C.c_int64, C.c_int64, _fp, _fp,
+                                           C.POINTER(PointsInfo)]),
+    "rs_surface_points_eval": (C.c_int, [C.c_void_p, _dp, _dp, _dp, C.c_int64, _dp, C.c_int64,
+                                         C.c_int32, C.c_double, C.c_double, _dp, _i32p, _dp,
+                                         C.POINTER(PointsInfo)]),
+    "rs_surface_points_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
     "rs_surface_render_depth": (C.c_int, [C.c_void_p, _dp, C.c_int64, _i32p, C.c_int64, _dp,
                                           C.c_int32, C.c_int64, C.c_int64, _fp]),
     "rs_surface_colorize": (C.c_int, [C.c_void_p, _dp, C.c_int64, _i32p, C.c_int64, _u8p,

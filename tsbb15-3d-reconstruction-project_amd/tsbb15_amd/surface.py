@@ -21,6 +21,11 @@ has no such stage and nothing here restates code of it.
   * ``clean``           ``remove_small`` -> ``smooth``
   * ``simplify``        vertex clustering on a grid, quadric placement (rs_mesh_simplify,
                         simplify.hip)
+  * ``points_volume``   the signed distance volume of an oriented cloud
+                        (rs_surface_points_volume, cloud_knn.hip)
+  * ``points_field``    the same field, and colours, at given positions (rs_surface_points_eval)
+  * ``from_points``     oriented cloud -> ``points_volume`` -> ``extract`` (-> ``clean``
+                        -> ``simplify`` -> colours from ``points_field``)
 
 Conventions are those of ``dense``: cameras are the project's normalised (3, 4) ``C``,
 ``P = K @ C``, pixel centres at integers, the depth of X in a view is ``C[2] @ [X; 1]`` and may
@@ -53,6 +58,9 @@ MESH_SCAN_CHUNK = 2048       # RS_MESH_SCAN_CHUNK
 SIMPLIFY_STAGES = ("cluster", "rows", "quadric", "faces")
 SIMPLIFY_PLACEMENTS = ("mean", "quadric")   # RS_SIMPLIFY_MEAN, RS_SIMPLIFY_QUADRIC
 SIMPLIFY_MAX_CELLS = 1 << 27                # RS_SIMPLIFY_MAX_CELLS
+POINTS_STAGES = ("box", "grid", "scan", "scatter", "field")
+POINTS_MAX_K = 64                           # RS_CLOUD_KNN_MAX_K
+POINTS_MAX = 1 << 28                        # RS_CLOUD_MAX_POINTS
 
 
 def _ctx(ctx):
@@ -732,6 +740,173 @@ def reconstruct(images, cams, K, depths, origin, voxel, dims, trunc, min_weight=
     return vertices, faces, tsdf, weight, col
 
 
+def _oriented(points, normals, k, radius, cell):
+    """points and normals as contiguous (n, 3) float64 after the ABI's rules for k, radius, cell."""
+    points, normals = _ffi.f64c(points), _ffi.f64c(normals)
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError('points must be (n, 3)')
+    if normals.shape != points.shape:
+        raise ValueError('normals must have the shape of points')
+    if len(points) > POINTS_MAX:
+        raise ValueError('more points than RS_CLOUD_MAX_POINTS = 2^28')
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError('k must be an integer')
+    if not 1 <= k <= POINTS_MAX_K:
+        raise ValueError('k must be in 1..64 (RS_CLOUD_KNN_MAX_K)')
+    radius = float(radius)
+    if not np.isfinite(radius) or not radius > 0.0:
+        raise ValueError('radius must be finite and positive')
+    cell = 0.0 if cell is None else float(cell)
+    if not np.isfinite(cell) or cell < 0.0:
+        raise ValueError('cell must be finite and >= 0 (None or 0: the default)')
+    return points, normals, int(k), radius, cell
+
+
+def _points_info(info):
+    return {"cells": info.cells, "largest_cell": info.largest_cell, "tested": info.tested,
+            "defined": info.defined, "saturated": info.saturated}
+
+
+def points_volume(points, normals, origin, voxel, dims, radius, k=16, trunc=None, cell=None,
+                  return_info=False, ctx=None):
+    """The signed distance volume of an oriented cloud (rs_surface_points_volume): an implicit
+    moving-least-squares field over the k nearest points within ``radius`` of every node.
+
+    points and normals are (n, 3) float64; a point with a non-finite number among its six is
+    out, and normals are used as given.  The list of a node X is ``cloud.knn``'s row for the
+    query X with ``max_dist=radius``.  Per slot in list order, in fp64 without fused products:
+    u = min(sqrt(d2) / radius, 1), a = 1 - u, w = (a^2 a^2)(4 u + 1) (Wendland C2, 0 at the
+    rim), acc += w (X - p_j) . n_j, sw += w; f = acc / sw, NaN when sw is not > 0.  f > 0 on the
+    side the normals point to.  The result depends neither on ``cell`` (None: a hair above
+    ``radius``, which ends the walk after 27 cells) nor on
+    anything else about the grid, and two calls give the same bits.
+
+    Returns (tsdf, weight), float32 (nz, ny, nx): tsdf = clip(f / trunc, -1, 1), NaN where f is
+    (``trunc=None``: ``radius``), and weight = the number of neighbours, so that
+    ``extract(..., min_weight=m)`` keeps the cells with at least m points within ``radius`` of
+    all 8 corners.  With ``return_info`` a third item: dict(cells, largest_cell, tested, defined:
+    nodes with a finite value, saturated: nodes whose list was full).
+
+    ValueError before any launch: points or normals not (n, 3), k outside 1..64, radius or trunc
+    not finite or <= 0, cell negative or not finite, the volume limits of ``integrate``, origin
+    or voxel not finite, voxel <= 0."""
+    points, normals, k, radius, cell = _oriented(points, normals, k, radius, cell)
+    origin, voxel, dims = _grid(origin, voxel, dims)
+    trunc = radius if trunc is None else float(trunc)
+    if not np.isfinite(trunc) or not trunc > 0.0:
+        raise ValueError('trunc must be finite and positive')
+    tsdf, weight = np.empty(dims, np.float32), np.empty(dims, np.float32)
+    info = _ffi.PointsInfo()
+    n = len(points)
+    _ffi.check(_ffi.lib().rs_surface_points_volume(
+        _ctx(ctx), _ffi.ptr(points, _d) if n else None, _ffi.ptr(normals, _d) if n else None, n,
+        k, radius, trunc, cell, _ffi.ptr(origin, _d), voxel, dims[0], dims[1], dims[2],
+        _ffi.ptr(tsdf, _f), _ffi.ptr(weight, _f), _ffi.C.byref(info)))
+    return (tsdf, weight, _points_info(info)) if return_info else (tsdf, weight)
+
+
+def points_field(points, normals, queries, radius, k=16, colors=None, cell=None,
+                 return_info=False, ctx=None):
+    """The field of ``points_volume`` at caller positions (rs_surface_points_eval).  queries is
+    (m, 3); colors (n, 3) float64 or None.
+
+    Returns (value (m,) float64: the unclamped f; count (m,) int32: the neighbours found), with
+    colours a third item color (m, 3) = sum w col_j / sum w over the same list, NaN where f is,
+    and with ``return_info`` the info of ``points_volume`` last.  A non-finite query has count 0
+    and NaN.
+
+    ValueError before any launch: what ``points_volume`` lists for the cloud, queries not
+    (m, 3) or more than 2^28, colors not of the points' shape."""
+    points, normals, k, radius, cell = _oriented(points, normals, k, radius, cell)
+    queries = _ffi.f64c(queries)
+    if queries.ndim != 2 or queries.shape[1] != 3:
+        raise ValueError('queries must be (m, 3)')
+    if len(queries) > POINTS_MAX:
+        raise ValueError('more queries than RS_CLOUD_MAX_POINTS = 2^28')
+    if colors is not None:
+        colors = _ffi.f64c(colors)
+        if colors.shape != points.shape:
+            raise ValueError('colors must have the shape of points')
+    n, m = len(points), len(queries)
+    value, count = np.full(m, np.nan), np.zeros(m, np.int32)
+    color = np.full((m, 3), np.nan) if colors is not None else None
+    info = _ffi.PointsInfo()
+    # an empty cloud has no array to point to: the call then takes no colours either
+    with_col = colors is not None and n > 0
+    _ffi.check(_ffi.lib().rs_surface_points_eval(
+        _ctx(ctx), _ffi.ptr(points, _d) if n else None, _ffi.ptr(normals, _d) if n else None,
+        _ffi.ptr(colors, _d) if with_col else None, n, _ffi.ptr(queries, _d) if m else None, m,
+        k, radius, cell, _ffi.ptr(value, _d) if m else None, _ffi.ptr(count, _i32) if m else None,
+        _ffi.ptr(color, _d) if with_col else None, _ffi.C.byref(info)))
+    out = (value, count) if colors is None else (value, count, color)
+    return out + (_points_info(info),) if return_info else out
+
+
+def oriented_cloud(points, normals, colors=None):
+    """The rows ``from_points`` works on: (points, unit normals, colours or None, keep (n,) bool).
+    A row goes when one of its numbers (the colours included) is not finite or its normal is
+    zero; the normals that stay are divided by their length.  Host numpy."""
+    points, normals = _ffi.f64c(points), _ffi.f64c(normals)
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError('points must be (n, 3)')
+    if normals.shape != points.shape:
+        raise ValueError('normals must have the shape of points')
+    keep = np.isfinite(points).all(axis=1) & np.isfinite(normals).all(axis=1)
+    if colors is not None:
+        colors = np.asarray(colors)
+        if colors.shape != points.shape or colors.dtype.kind not in 'fiu':
+            raise ValueError('colors must have the shape of points')
+        colors = colors.astype(np.float64) / (255.0 if colors.dtype == np.uint8 else 1.0)
+        keep &= np.isfinite(colors).all(axis=1)
+    with np.errstate(invalid='ignore', over='ignore'):
+        length = np.sqrt((normals * normals).sum(axis=1))
+    keep &= np.isfinite(length) & (length > 0.0)
+    unit = normals[keep] / length[keep, None]
+    return (np.ascontiguousarray(points[keep]), np.ascontiguousarray(unit),
+            np.ascontiguousarray(colors[keep]) if colors is not None else None, keep)
+
+
+def from_points(points, normals, voxel, radius, k=16, min_count=3, margin=None, colors=None,
+                clean=None, simplify=None, return_info=False, ctx=None):
+    """An oriented cloud to a mesh: ``oriented_cloud`` (rows with a non-finite entry or a zero
+    normal go, normals become unit vectors), ``bounds(points, voxel, margin)`` with
+    ``margin=None`` for two voxels, ``points_volume`` with ``trunc = radius``, and
+    ``extract(..., min_weight=min_count)``: a cell is meshed when every corner has at least
+    ``min_count`` points within ``radius``.  ``clean`` and ``simplify`` are dicts of those
+    functions' keywords, applied in that order as ``reconstruct`` applies them.
+
+    With ``colors`` (n, 3), uint8 or floats in [0, 1] as ``cloud.point_attributes`` gives them,
+    the colour of a vertex is ``points_field``'s at the final vertices, as uint8 after
+    ``rint(255 c)`` clipped to 0..255; a vertex without a neighbour gets 0, the fill of
+    ``vertex_colors``.
+
+    Returns (vertices, faces), with colours (vertices, faces, vertex_colors (Nv, 3) uint8), and
+    with ``return_info`` a dict last: the info of ``points_volume`` plus origin, dims and points
+    (the rows that stayed)."""
+    pts, unit, col, keep = oriented_cloud(points, normals, colors)
+    voxel = float(voxel)
+    if not np.isfinite(voxel) or not voxel > 0.0:
+        raise ValueError('voxel must be finite and positive')
+    origin, dims = bounds(pts, voxel, 2.0 * voxel if margin is None else margin)
+    tsdf, weight, info = points_volume(pts, unit, origin, voxel, dims, radius, k=k,
+                                       return_info=True, ctx=ctx)
+    vertices, faces = extract(tsdf, weight, origin, voxel, min_weight=min_count, ctx=ctx)
+    if clean is not None:
+        vertices, faces, _ = _clean(vertices, faces, ctx=ctx, **dict(clean))
+    if simplify is not None:
+        vertices, faces = _simplify(vertices, faces, ctx=ctx,
+                                    **dict(simplify, return_info=False))[:2]
+    out = (vertices, faces)
+    if col is not None:
+        c = points_field(pts, unit, vertices, radius, k=k, colors=col, ctx=ctx)[2]
+        c = np.where(np.isnan(c), 0.0, c)
+        out += (np.clip(np.rint(c * 255.0), 0, 255).astype(np.uint8),)
+    if return_info:
+        info.update(origin=origin, dims=dims, points=int(keep.sum()))
+        out += (info,)
+    return out
+
+
 def timing(enable, ctx=None):
     """Enable / disable HIP events around the kernels of the next surface calls
     (rs_surface_timing); returns the last timed calls' {integrate, classify, scan, emit: device
@@ -769,3 +944,13 @@ def texture_timing(enable, ctx=None):
     ms = np.zeros(len(TEXTURE_STAGES))
     _ffi.check(_ffi.lib().rs_surface_texture_timing(ctx.handle, int(enable), _ffi.ptr(ms, _d)))
     return dict(zip(TEXTURE_STAGES, ms.tolist()))
+
+
+def points_timing(enable, ctx=None):
+    """The same for the next ``points_volume`` and ``points_field`` calls
+    (rs_surface_points_timing): {box, grid, scan, scatter, field: device ms}, -1 where none.
+    ``cloud.knn_timing`` does not see these calls."""
+    ctx = ctx or _ffi.default_context()
+    ms = np.zeros(len(POINTS_STAGES))
+    _ffi.check(_ffi.lib().rs_surface_points_timing(ctx.handle, int(enable), _ffi.ptr(ms, _d)))
+    return dict(zip(POINTS_STAGES, ms.tolist()))
