@@ -1681,6 +1681,106 @@ int rs_mesh_simplify(rs_ctx *ctx, const double *vertices, int64_t nv, const int3
 int rs_simplify_timing(rs_ctx *ctx, int32_t enable, double *ms);
 
 /* ------------------------------------------------------------------------------------------
+ * Global registration (global_reg.hip): descriptors, descriptor matching and a RANSAC over
+ * three-point similarities, the coarse alignment that lands inside the basin of the trimmed ICP
+ * above from any pose.  Every device computation is fp64 without contraction and uses only
+ * + - * /, sqrt, floor, min, max and comparisons, with every sum in the order written here, so
+ * that every output is a function of the inputs alone; tests/global_ref.py restates it in numpy.
+ * Below, dot(a, b) = (a0 b0 + a1 b1) + a2 b2, |a|^2 = dot(a, a) and
+ * cross(a, b) = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0).
+ * ---------------------------------------------------------------------------------------- */
+
+/* Fast point feature histograms over k-NN neighbourhoods, 3 x 11 bins, 1 <= k <=
+ * RS_CLOUD_KNN_MAX_K - 1.  pts (n, 3), normals (n, 3), used as given (unit length is the caller's
+ * business).
+ *   Neighbours.  The list of point i is rs_cloud_knn's row of the k + 1 nearest with one entry
+ *   dropped by the rule of rs_cloud_knn_mean_dist (the entry that names i, else the last), walked
+ *   in list order; d2 is the list's.  The lists stay on the device.
+ *   Pairs.  With d = p_j - p_i and c = cross(d, n_i), the pair (i, j) is counted when d2 > 0, the
+ *   six numbers of n_i and n_j are finite and |c|^2 > 0.  Then u = n_i, v = c / sqrt(|c|^2),
+ *   w = cross(u, v), f1 = dot(v, n_j), f2 = dot(u, d) / sqrt(d2), x = dot(u, n_j),
+ *   y = dot(w, n_j).
+ *   Pseudo-angle a in [0, 4] of (x, y): den = |x| + |y|; a = 0 unless den > 0; r = y / den;
+ *   a = 1 + r where x >= 0, else 3 - r where y >= 0, else (-1 - r) + 4.
+ *   Bins.  bin(q) = 0 unless floor(q) >= 0, 10 where floor(q) > 10, else floor(q);
+ *   b1 = bin((f1 + 1) 5.5), b2 = bin((f2 + 1) 5.5), b3 = bin(a 2.75).  SPFH_i, 33 int32 counts,
+ *   gains one at b1, 11 + b2 and 22 + b3 for every counted pair; c_i is their number.
+ *   Histograms.  Over the listed j with d2 > 0 and c_j > 0, in list order from +0.0, with
+ *   w_j = 1 / sqrt(d2): A[b] += (w_j SPFH_j[b]) / c_j and W += w_j.  Then
+ *   fpfh[i][b] = SPFH_i[b] / c_i + A[b] / W.  A row with c_i = 0 or without such a j is NaN.
+ * count[i] = c_i.  info is rs_cloud_knn's for the lists (rows_short against k + 1).  The result
+ * does not depend on `cell`.  RS_EINVAL as rs_cloud_knn_mean_dist; n = 0 returns at once. */
+#define RS_FPFH_BINS 33
+int rs_cloud_fpfh(rs_ctx *ctx, const double *pts, const double *normals, int64_t n, int32_t k,
+                  double cell, double *fpfh, int32_t *count, rs_knn_info *info);
+
+/* Nearest descriptor by brute force.  fa (n, D), fb (m, D), 1 <= D <= RS_FEATURE_MATCH_MAX_D.
+ *   d2(i, j) = sum over c = 0 .. D - 1, left to right from the first term, of
+ *   (fa[i][c] - fb[j][c]) (fa[i][c] - fb[j][c]).
+ *   idx[i] is the lowest j among those with the smallest d2(i, j) < +inf, d2[i] that value;
+ *   idx[i] = -1 and d2[i] = +inf where there is none: a NaN in row i, in every row of fb, or
+ *   m = 0.  A row of fb that holds a NaN is nobody's match.
+ * fb goes through LDS in tiles of RS_FEATURE_MATCH_TILE rows; the result does not depend on it.
+ * RS_EINVAL: a null pointer where elements are expected, D out of range, n or m negative or
+ * above RS_CLOUD_MAX_POINTS.  n = 0 returns at once. */
+#define RS_FEATURE_MATCH_MAX_D 64
+#define RS_FEATURE_MATCH_TILE 96
+int rs_feature_match(rs_ctx *ctx, const double *fa, int64_t n, const double *fb, int64_t m,
+                     int32_t D, int32_t *idx, double *d2);
+
+/* RANSAC over the similarities of three correspondences src[i] <-> dst[i], i < M.
+ *   Hypothesis h, 0 <= h < H, draws (i0, i1, i2) = floyd_sample<3>(seed, h, M), the sampler of
+ *   the F and PnP kernels (tests/philox_ref.py); a_k = src[i_k], b_k = dst[i_k].
+ *   Edges (0, 1), (0, 2), (1, 2): la = sqrt(|a_p - a_q|^2), lb = sqrt(|b_p - b_q|^2).
+ *   Gates, in this order; a hypothesis leaves at the first it fails, and a comparison with a NaN
+ *   fails:
+ *   1. no two of b_0, b_1, b_2 are equal in all three coordinates;
+ *   2. every la > min_edge;
+ *   3. with r = lb / la per edge, max r <= (1 + edge_tol) min r (max and min taken over the
+ *      edges in the order above); without with_scale also 1 / (1 + edge_tol) <= r <= 1 + edge_tol
+ *      for every edge;
+ *   4. scale_lo <= s <= scale_hi;
+ *   5. the 13 numbers of the model are finite (a collinear triple is not).
+ *   Model.  ca = ((a_0 + a_1) + a_2) / 3, cb likewise.  The frame of a triangle: e1 = a_1 - a_0,
+ *   e2 = a_2 - a_0, x = e1 / sqrt(|e1|^2), g = cross(e1, e2), z = g / sqrt(|g|^2),
+ *   y = cross(z, x).  R[r][c] = (xb[r] xa[c] + yb[r] ya[c]) + zb[r] za[c].
+ *   s = sqrt((|b_0 - cb|^2 + |b_1 - cb|^2) + |b_2 - cb|^2) / sqrt(the same of a), 1 without
+ *   with_scale.  t[r] = cb[r] - s ((R[r][0] ca[0] + R[r][1] ca[1]) + R[r][2] ca[2]).
+ *   Score.  count = the number of i with |p' - dst[i]|^2 <= inlier_dist inlier_dist, p' the
+ *   image of src[i] under rs_eval_index_step's transform expression,
+ *   p'[r] = s ((R[r][0] x + R[r][1] y) + R[r][2] z) + t[r].
+ * out holds the `candidates` best survivors by (count descending, h ascending), found of them
+ * (info); the rest of out is zero.  Nothing depends on the launch shape, on the chunks of
+ * RS_SIM3_CHUNK hypotheses the call works through or on the order in which survivors are
+ * compacted.  RS_EINVAL: a null pointer, M < 3 or above 2^24, H < 1 or above 2^32, candidates
+ * outside 1..RS_SIM3_MAX_CANDIDATES, inlier_dist, edge_tol, min_edge negative or not finite,
+ * scale_lo or scale_hi NaN or negative. */
+#define RS_SIM3_MAX_CANDIDATES 1024
+#define RS_SIM3_CHUNK (1 << 20)
+typedef struct rs_sim3_candidate {
+  int64_t h;        /* the hypothesis                                  */
+  int64_t count;    /* its score                                       */
+  double model[13]; /* s, R row-major, t                               */
+} rs_sim3_candidate; /* 120 bytes */
+typedef struct rs_sim3_info {
+  int64_t hypotheses; /* H                                             */
+  int64_t passed[5];  /* hypotheses that passed gate 1, .., gate 5     */
+  int64_t tests;      /* survivors x M                                 */
+  int64_t found;      /* entries of out that are filled                */
+} rs_sim3_info;       /* 64 bytes */
+int rs_sim3_ransac(rs_ctx *ctx, const double *src, const double *dst, int64_t M, int64_t H,
+                   double inlier_dist, uint64_t seed, int32_t with_scale, double scale_lo,
+                   double scale_hi, double edge_tol, double min_edge, int32_t candidates,
+                   rs_sim3_candidate *out, rs_sim3_info *info);
+
+/* HIP events between the kernels of the next global-registration calls (enable != 0).  Returns
+ * the last timed call's device ms per stage: spfh, fpfh (rs_cloud_fpfh, after the k-NN stages
+ * that rs_cloud_knn_timing reports), match (rs_feature_match), solve, count, gather
+ * (rs_sim3_ransac, summed over its chunks); -1 where none (tools/bench_global.py). */
+#define RS_GLOBAL_TIMING_SLOTS 6
+int rs_global_timing(rs_ctx *ctx, int32_t enable, double *ms);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU (RCCL over xGMI).  One process per GPU; the unique id travels out of band.
  * ---------------------------------------------------------------------------------------- */
 #define RS_COMM_ID_BYTES 128

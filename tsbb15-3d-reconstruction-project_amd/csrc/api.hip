@@ -134,6 +134,7 @@ extern "C" int rs_ctx_destroy(rs_ctx *c) {
   c->eval.destroy();
   c->mesh.destroy();
   c->simplify.destroy();
+  c->global.destroy();
   if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;

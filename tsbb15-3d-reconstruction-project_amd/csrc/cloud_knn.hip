@@ -19,6 +19,7 @@
 //                   lives in registers; most candidates are rejected there without an LDS access,
 //                   an accepted one is inserted from the tail
 //   k_knn_normals, k_knn_mean   one lane per point over its own row of the lists
+//   (rs_cloud_fpfh keeps the lists in the same way; its two kernels stand in global_reg.hip)
 // The list is the k smallest of the pairs (d2 bits, index), a set that does not depend on the
 // order of the visits: neither the arrival order inside a cell, nor the cells' layout, nor `cell`
 // can change a bit of the result, and no per-cell sort is needed.
@@ -31,6 +32,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 #include "device_math.h"
 #include "host.h"
@@ -576,7 +578,7 @@ static_assert(sizeof(rs_knn_info) == 40, "rs_knn_info");
 
 namespace {
 
-enum KnnUse { kKnnLists = 0, kKnnNormals = 1, kKnnMean = 2 };
+enum KnnUse { kKnnLists = 0, kKnnNormals = 1, kKnnMean = 2, kKnnFpfh = 3 };
 
 struct KnnOut {
   int32_t *idx = nullptr;      // lists
@@ -585,6 +587,8 @@ struct KnnOut {
   double *normals = nullptr;   // normals
   double *evals = nullptr;     // normals
   double *mean = nullptr;      // mean
+  double *fpfh = nullptr;      // fpfh: (n, 33)
+  int32_t *pairs = nullptr;    // fpfh: the counted pairs per point
 };
 
 // what a call without a finite point returns: empty lists, NaN rows
@@ -599,6 +603,10 @@ void knn_fill_empty(KnnUse use, int64_t n, int64_t m, int K, const KnnOut &o) {
     for (int64_t i = 0; i < 3 * n; ++i) o.normals[i] = o.evals[i] = NAN;
   if (use == kKnnMean)
     for (int64_t i = 0; i < n; ++i) o.mean[i] = NAN;
+  if (use == kKnnFpfh) {
+    for (int64_t i = 0; i < n; ++i) o.pairs[i] = 0;
+    for (int64_t i = 0; i < RS_FPFH_BINS * n; ++i) o.fpfh[i] = NAN;
+  }
 }
 
 // The grid over the box [lo, hi] of nfin > 0 finite points (box: what k_knn_box_fold leaves).
@@ -659,7 +667,8 @@ int knn_size_grid(const double *box, int64_t nfin, double cell, double radius, r
 
 // The grid, the query with lists K wide and, for the consumers, their kernel.  The arguments have
 // been checked: 1 <= K <= RS_CLOUD_KNN_MAX_K, 0 < n, m <= RS_CLOUD_MAX_POINTS, queries null only
-// with m == n, max_dist >= 0, cell >= 0 and finite.
+// with m == n, max_dist >= 0, cell >= 0 and finite.  For the descriptors (kKnnFpfh) `orient`
+// carries the normals and the kernels of global_reg.hip follow the query.
 int knn_run(rs_ctx *c, KnnUse use, const double *pts, int64_t n, const double *queries, int64_t m,
             int K, double max_dist, double cell, const double *orient, const KnnOut &o,
             rs_knn_info *info) {
@@ -677,7 +686,12 @@ int knn_run(rs_ctx *c, KnnUse use, const double *pts, int64_t n, const double *q
   const auto b_idx = L.add<int32_t>(sm * sK);
   const auto b_d2 = L.add<double>(use == kKnnNormals ? 0 : sm * sK);   // the plane fit reads none
   const auto b_count = L.add<int32_t>(sm);
-  const auto b_res = L.add<double>(use == kKnnNormals ? 6 * sn : (use == kKnnMean ? sn : 0));
+  const auto b_res = L.add<double>(use == kKnnNormals ? 6 * sn
+                                   : use == kKnnMean  ? sn
+                                   : use == kKnnFpfh  ? RS_FPFH_BINS * sn
+                                                      : 0);
+  const auto b_spfh = L.add<int32_t>(use == kKnnFpfh ? RS_FPFH_BINS * sn : 0);
+  const auto b_pairs = L.add<int32_t>(use == kKnnFpfh ? sn : 0);
   const auto b_stats = L.add<U64>(8);
   const auto b_packed = L.add<double>(3 * sn);
   const auto b_pidx = L.add<int32_t>(sn), b_cell_of = L.add<int32_t>(sn);
@@ -762,6 +776,9 @@ int knn_run(rs_ctx *c, KnnUse use, const double *pts, int64_t n, const double *q
   if (use == kKnnMean)
     hipLaunchKernelGGL(rsd::k_knn_mean, dim3(rs::blocks(n, rsd::kKnnThreads)), blk, 0, s, n, K,
                        b_idx.dev(), b_d2.dev(), b_count.dev(), b_res.dev());
+  if (use == kKnnFpfh)
+    rs::fpfh_launch(c, b_pts.dev(), b_orient.dev(), n, K, b_idx.dev(), b_d2.dev(), b_count.dev(),
+                    b_spfh.dev(), b_pairs.dev(), b_res.dev());
   HIP_TRY(hipGetLastError());
   if ((st = c->knn.mark(7, s))) return st;
   U64 stats[8];
@@ -773,6 +790,9 @@ int knn_run(rs_ctx *c, KnnUse use, const double *pts, int64_t n, const double *q
                            s));
     HIP_TRY(hipMemcpyAsync(o.evals, b_res.dev() + 3 * n, 3 * sn * sizeof(double),
                            hipMemcpyDeviceToHost, s));
+  } else if (use == kKnnFpfh) {
+    HIP_TRY(hipMemcpyAsync(o.fpfh, b_res.dev(), b_res.bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(o.pairs, b_pairs.dev(), b_pairs.bytes, hipMemcpyDeviceToHost, s));
   } else {
     HIP_TRY(hipMemcpyAsync(o.mean, b_res.dev(), b_res.bytes, hipMemcpyDeviceToHost, s));
   }
@@ -781,7 +801,10 @@ int knn_run(rs_ctx *c, KnnUse use, const double *pts, int64_t n, const double *q
   HIP_TRY(hipStreamSynchronize(s));
   for (int k = 1; k < 5; ++k)
     if ((st = c->knn.read(k, k + 1, k + 2))) return st;
-  if (use != kKnnLists && (st = c->knn.read(use == kKnnNormals ? 5 : 6, 6, 7))) return st;
+  if ((use == kKnnNormals || use == kKnnMean) &&
+      (st = c->knn.read(use == kKnnNormals ? 5 : 6, 6, 7)))
+    return st;
+  if (use == kKnnFpfh && (st = rs::fpfh_read_timing(c))) return st;
 
   info->cells = ncell;
   info->largest_cell = static_cast<int64_t>(stats[rsd::kKnnLargest]);
@@ -864,6 +887,23 @@ extern "C" int rs_cloud_knn_mean_dist(rs_ctx *c, const double *pts, int64_t n, i
   o.mean = mean_dist;
   o.count = count;
   return knn_run(c, kKnnMean, pts, n, nullptr, n, k + 1, INFINITY, cell, nullptr, o, info);
+}
+
+extern "C" int rs_cloud_fpfh(rs_ctx *c, const double *pts, const double *normals, int64_t n,
+                             int32_t k, double cell, double *fpfh, int32_t *count,
+                             rs_knn_info *info) {
+  int st = knn_check(c, info, n, n, k, RS_CLOUD_KNN_MAX_K - 1, INFINITY, cell);
+  if (st) return st;
+  const rs_knn_info zero = {0, 0, 0, 0, 0};
+  *info = zero;
+  if (n == 0) return RS_OK;
+  if (!pts || !normals || !fpfh || !count) return fail(RS_EINVAL, "null pointer");
+  std::vector<int32_t> listed(static_cast<size_t>(n));   // the lists' lengths, for info
+  KnnOut o;
+  o.fpfh = fpfh;
+  o.pairs = count;
+  o.count = listed.data();
+  return knn_run(c, kKnnFpfh, pts, n, nullptr, n, k + 1, INFINITY, cell, normals, o, info);
 }
 
 extern "C" int rs_cloud_knn_timing(rs_ctx *c, int32_t enable, double *ms) {

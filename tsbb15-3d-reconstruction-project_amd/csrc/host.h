@@ -143,6 +143,9 @@ struct rs_ctx {
   // rs_simplify_timing: between the stages of the next rs_mesh_simplify calls (simplify.hip):
   // cluster, rows, quadric, faces
   rs::StageTimer<5, RS_SIMPLIFY_TIMING_SLOTS> simplify{-1.0};
+  // rs_global_timing: around the kernels of the next global-registration calls (global_reg.hip):
+  // spfh, fpfh, match, solve, count, gather
+  rs::StageTimer<9, RS_GLOBAL_TIMING_SLOTS> global{-1.0};
 };
 
 namespace rs {
@@ -262,4 +265,11 @@ void dense_sweep_launch(hipStream_t s, const uint8_t *ref, const uint8_t *src, i
 int mesh_check(const rs_ctx *c, const int32_t *faces, int64_t nf, int64_t nv);
 void mesh_scan(hipStream_t s, int32_t *v, int64_t n, int32_t *sums);
 int fmatrix_stls_lsq(rs_ctx *c, const double *pl, const double *pr, int64_t n, double *F_out);
+// The two descriptor kernels of rs_cloud_fpfh (global_reg.hip) on the lists knn_run left on the
+// device (`rows` wide, k + 1), enqueued on the context's stream: spfh (n, 33) and pairs (n) are
+// scratch, out (n, 33) the descriptors; and, after the stream has been waited for, their timing.
+void fpfh_launch(rs_ctx *c, const double *pts, const double *normals, int64_t n, int rows,
+                 const int32_t *idx, const double *d2, const int32_t *count, int32_t *spfh,
+                 int32_t *pairs, double *out);
+int fpfh_read_timing(rs_ctx *c);
 }  // namespace rs

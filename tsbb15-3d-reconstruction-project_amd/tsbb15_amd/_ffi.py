@@ -102,6 +102,15 @@ class EvalStep(C.Structure):
                 ("tests", C.c_int64), ("tau", C.c_double), ("moments", C.c_double * 40)]
 
 
+class Sim3Candidate(C.Structure):
+    _fields_ = [("h", C.c_int64), ("count", C.c_int64), ("model", C.c_double * 13)]
+
+
+class Sim3Info(C.Structure):
+    _fields_ = [("hypotheses", C.c_int64), ("passed", C.c_int64 * 5), ("tests", C.c_int64),
+                ("found", C.c_int64)]
+
+
 class SimplifyInfo(C.Structure):
     _fields_ = [("clusters", C.c_int64), ("fallbacks", C.c_int64),
                 ("degenerate_faces", C.c_int64), ("duplicate_faces", C.c_int64),
@@ -115,6 +124,12 @@ CLOUD_STAGES = ("grid", "scan", "sort", "normals", "attributes")
 CLOUD_MAX_POINTS = 1 << 28
 CLOUD_KNN_MAX_K = 64
 CLOUD_KNN_STAGES = ("box", "grid", "scan", "scatter", "query", "normals", "mean_dist")
+FPFH_BINS = 33
+FEATURE_MATCH_MAX_D = 64
+FEATURE_MATCH_TILE = 96
+SIM3_MAX_CANDIDATES = 1024
+SIM3_CHUNK = 1 << 20
+GLOBAL_STAGES = ("spfh", "fpfh", "match", "solve", "count", "gather")
 EVAL_STAGES = ("bin", "scan", "scatter", "query")
 EVAL_REG_STAGES = ("transform", "query", "select", "moments")
 EVAL_REG_METRICS = ("point", "plane")   # RS_EVAL_REG_*: the index is the code
@@ -260,6 +275,15 @@ _SIGS = {
     "rs_cloud_knn_mean_dist": (C.c_int, [C.c_void_p, _dp, C.c_int64, C.c_int32, C.c_double, _dp,
                                          _i32p, C.POINTER(KnnInfo)]),
     "rs_cloud_knn_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "rs_cloud_fpfh": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int64, C.c_int32, C.c_double, _dp, _i32p,
+                                C.POINTER(KnnInfo)]),
+    "rs_feature_match": (C.c_int, [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, C.c_int32, _i32p,
+                                   _dp]),
+    "rs_sim3_ransac": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64, C.c_double,
+                                 C.c_uint64, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                 C.c_double, C.c_int32, C.POINTER(Sim3Candidate),
+                                 C.POINTER(Sim3Info)]),
+    "rs_global_timing": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
     "rs_dense_plane_sweep": (C.c_int, [C.c_void_p, _u8p, C.c_int64, C.c_int64, _u8p, C.c_int32,
                                        _dp, _dp, _dp, C.c_int64, C.c_int32, C.c_double, _i32p,
                                        _fp, _fp, _u8p, _fp]),

@@ -251,6 +251,78 @@ def knn_timing(enable, ctx=None):
     return dict(zip(_ffi.CLOUD_KNN_STAGES, ms.tolist()))
 
 
+def fpfh(points, normals, k=32, cell=None, ctx=None):
+    """Fast point feature histograms over k-NN neighbourhoods (rs_cloud_fpfh, where every order of
+    operations is written down): 3 x 11 bins per point, the descriptor ``match_features`` and
+    ``evaluation.global_register`` work on.
+
+    The neighbours of point i are ``knn(points, k + 1)``'s row i with i dropped by the rule of
+    ``knn_mean_dist``; neighbours by number and not by radius make the descriptor invariant to
+    scale for clouds of comparable sampling.  A pair (i, j) is counted unless d2 = 0, a normal
+    is not finite, or p_j - p_i is parallel to n_i; the third feature is a diamond pseudo-angle
+    in place of atan2, so that every bit can be restated (tests/global_ref.py).  1 <= k <= 63.
+
+    Returns (fpfh (n, 33), count (n,) int32, info): count the number of counted pairs, info as
+    ``knn``'s.  A row without a counted pair, or whose neighbours have none, is NaN.  The result
+    does not depend on ``cell``."""
+    points, k, cell = _knn_args(points, k, _ffi.CLOUD_KNN_MAX_K - 1, cell)
+    normals = _ffi.f64c(normals)
+    if normals.shape != points.shape:
+        raise ValueError('normals must have the shape of points')
+    n = len(points)
+    out = np.full((n, _ffi.FPFH_BINS), np.nan)
+    count = np.zeros(n, dtype=np.int32)
+    info = _ffi.KnnInfo()
+    _ffi.check(_ffi.lib().rs_cloud_fpfh(
+        _ctx(ctx), _ffi.ptr(points, _d), _ffi.ptr(normals, _d), n, k, cell, _ffi.ptr(out, _d),
+        _ffi.ptr(count, _i32), _ffi.C.byref(info)))
+    return out, count, _knn_info(info)
+
+
+def match_features(fa, fb, mutual=False, ctx=None):
+    """For every row of fa (n, D) the nearest row of fb (m, D) by brute force (rs_feature_match),
+    D <= 64: idx (n,) int32 the lowest index among the rows with the smallest
+    d2 = sum_c (a_c - b_c)^2 (summed left to right), d2 (n,) that value.  A row with a NaN matches
+    nothing and is nobody's match: idx = -1, d2 = +inf; so is every row when m = 0.
+
+    ``mutual=True`` is a host-side filter on two calls: idx[i] stays only where the nearest row
+    of fa to fb[idx[i]] is i again; the others become -1 / +inf.  Returns (idx, d2)."""
+    fa, fb = _ffi.f64c(fa), _ffi.f64c(fb)
+    if fa.ndim != 2 or fb.ndim != 2 or fa.shape[1] != fb.shape[1]:
+        raise ValueError('fa and fb must be (n, D) and (m, D)')
+    D = fa.shape[1]
+    if not 1 <= D <= _ffi.FEATURE_MATCH_MAX_D:
+        raise ValueError(f'D must be in 1..{_ffi.FEATURE_MATCH_MAX_D}')
+    if max(len(fa), len(fb)) > _ffi.CLOUD_MAX_POINTS:
+        raise ValueError('more rows than RS_CLOUD_MAX_POINTS = 2^28')
+
+    def one(a, b):
+        idx = np.full(len(a), -1, dtype=np.int32)
+        d2 = np.full(len(a), np.inf)
+        _ffi.check(_ffi.lib().rs_feature_match(
+            _ctx(ctx), _ffi.ptr(a, _d), len(a), _ffi.ptr(b, _d), len(b), D, _ffi.ptr(idx, _i32),
+            _ffi.ptr(d2, _d)))
+        return idx, d2
+
+    idx, d2 = one(fa, fb)
+    if mutual:
+        back, _ = one(fb, fa)
+        keep = idx >= 0
+        keep[keep] = back[idx[keep]] == np.flatnonzero(keep)
+        idx, d2 = np.where(keep, idx, -1).astype(np.int32), np.where(keep, d2, np.inf)
+    return idx, d2
+
+
+def global_timing(enable, ctx=None):
+    """Enable / disable HIP events around the kernels of the next fpfh, match_features and
+    evaluation.ransac_similarity calls (rs_global_timing); returns the last timed calls'
+    {stage: device ms}, -1 where none."""
+    ctx = ctx or _ffi.default_context()
+    ms = np.zeros(len(_ffi.GLOBAL_STAGES))
+    _ffi.check(_ffi.lib().rs_global_timing(ctx.handle, int(enable), _ffi.ptr(ms, _d)))
+    return dict(zip(_ffi.GLOBAL_STAGES, ms.tolist()))
+
+
 def save_txt(path, points, colors, normals, reflectance=1.0):
     """The export of 3Dvisualization.py:139-145: one row per point -- x y z, reflectance, r g b,
     nx ny nz -- through np.savetxt(..., delimiter=' ')."""

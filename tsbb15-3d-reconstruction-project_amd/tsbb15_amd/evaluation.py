@@ -16,7 +16,10 @@ them -- is host numpy: ``decompose_projection``, ``align_similarity``, ``camera_
 Both measures assume the two meshes stand in one frame.  ``register`` brings them there: trimmed
 ICP of a point cloud to a mesh kept on the device (``MeshIndex``, the rs_eval_index_* entries),
 one device step and one small host solve per iteration; ``compare_meshes(register=...)`` runs it
-first.
+first.  ``register`` needs a start inside its basin; ``global_register`` finds one from any pose
+and scale: FPFH descriptors (``cloud.fpfh``), nearest-descriptor matches, a RANSAC over
+three-point similarities (``ransac_similarity``, global_reg.hip) and a verification of the best
+hypotheses against the mesh.
 """
 from __future__ import annotations
 
@@ -186,7 +189,9 @@ def compare_meshes(rec_v, rec_f, gt_v, gt_f, fraction=0.9, threshold=None, max_d
     ``register``, a dict of keywords for ``register`` (an empty one for its defaults), first
     registers the reconstruction's points to the true mesh and applies the similarity found to
     ``rec_v`` before both distance calls; the result gains s, R, t and ``registration``, what
-    ``register`` returned.  With None nothing is aligned.
+    ``register`` returned.  With None nothing is aligned.  ``register="global"`` needs no start:
+    ``global_register`` with its defaults on ``samples`` (2 000 when None) surface samples of the
+    reconstruction and their faces' normals, so both meshes must be wound the same way.
 
     Returns dict(accuracy, completeness, fraction, threshold, dist_rec, dist_gt, info_rec,
     info_gt)."""
@@ -197,9 +202,16 @@ def compare_meshes(rec_v, rec_f, gt_v, gt_f, fraction=0.9, threshold=None, max_d
         if len(finite) == 0:
             raise ValueError('the truth has no finite vertex to take a threshold from')
         threshold = 0.01 * float(np.sqrt(((finite.max(axis=0) - finite.min(axis=0)) ** 2).sum()))
-    if register is not None:
+    if isinstance(register, str):
+        if register != "global":
+            raise ValueError('register must be None, a dict of keywords or "global"')
+        src, face = sample_surface(rec_v, rec_f, 2000 if samples is None else samples, seed)
+        reg = global_register(src, face_normals(rec_v, rec_f)[face], gt_v, gt_f, seed=seed,
+                              ctx=ctx)
+    elif register is not None:
         src = rec_v if samples is None else sample_surface(rec_v, rec_f, samples, seed)[0]
         reg = _register(src, gt_v, gt_f, ctx=ctx, **dict(register))
+    if register is not None:
         moved = apply_similarity(rec_v, reg["s"], reg["R"], reg["t"])
         out = compare_meshes(moved, rec_f, gt_v, gt_f, fraction=fraction, threshold=threshold,
                              max_dist=max_dist, samples=samples, seed=seed, ctx=ctx)
@@ -482,6 +494,144 @@ def register(points, vertices, faces, metric="plane", keep=1.0, with_scale=True,
 
 
 _register = register   # compare_meshes has a keyword of that name
+
+
+# ---- global registration -----------------------------------------------------------------------
+
+def ransac_similarity(src, dst, H, inlier_dist, seed=0, with_scale=True, scale=None,
+                      edge_tol=0.15, min_edge=0.0, candidates=32, ctx=None):
+    """RANSAC over the similarities of three correspondences src[i] <-> dst[i] (rs_sim3_ransac,
+    where the sampler, the gates, the closed form and the score are written down).
+
+    Hypothesis h < H draws three correspondences with the Philox / Floyd sampler, passes the
+    gates (distinct targets, source edges > ``min_edge``, the three edge ratios within a factor
+    1 + ``edge_tol`` of each other -- and of 1 without ``with_scale`` --, ``scale`` = (lo, hi)
+    around the scale, (0, inf) when None), takes the similarity that maps one triangle's frame
+    onto the other's, and counts the correspondences it brings within ``inlier_dist``.  The count
+    alone does not pick the answer: ``global_register`` verifies the candidates against the mesh.
+
+    Returns dict(h (c,) int64, count (c,) int64, s (c,), R (c, 3, 3), t (c, 3), info): the
+    c <= ``candidates`` best survivors by (count descending, h ascending); info =
+    dict(hypotheses, passed (5,) survivors per gate, tests, found)."""
+    src, dst = _points(src, 'src'), _points(dst, 'dst')
+    if src.shape != dst.shape:
+        raise ValueError('src and dst must have the same shape')
+    H, candidates = int(H), int(candidates)
+    lo, hi = (0.0, np.inf) if scale is None else (float(scale[0]), float(scale[1]))
+    cand = (_ffi.Sim3Candidate * max(candidates, 1))()
+    info = _ffi.Sim3Info()
+    _ffi.check(_ffi.lib().rs_sim3_ransac(
+        _ctx(ctx), _ffi.ptr(src, _d), _ffi.ptr(dst, _d), len(src), H, float(inlier_dist),
+        int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(with_scale)), lo, hi, float(edge_tol),
+        float(min_edge), candidates, cand, _ffi.C.byref(info)))
+    c = info.found
+    model = np.array([cand[i].model[:] for i in range(c)], dtype=np.float64).reshape(c, 13)
+    return {"h": np.array([cand[i].h for i in range(c)], dtype=np.int64),
+            "count": np.array([cand[i].count for i in range(c)], dtype=np.int64),
+            "s": model[:, 0].copy(), "R": model[:, 1:10].reshape(c, 3, 3).copy(),
+            "t": model[:, 10:13].copy(),
+            "info": {"hypotheses": info.hypotheses, "passed": np.array(info.passed[:]),
+                     "tests": info.tests, "found": info.found}}
+
+
+def face_normals(vertices, faces):
+    """Unit normals of the faces, cross(b - a, c - a) normalised (NaN for a face without area)."""
+    tri = np.asarray(vertices, dtype=np.float64)[np.asarray(faces).reshape(-1, 3)]
+    cr = np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return cr / np.sqrt((cr * cr).sum(axis=1))[:, None]
+
+
+def rms_radius(points):
+    """The root mean square distance of the finite points from their centroid."""
+    p = np.asarray(points, dtype=np.float64)
+    p = p[np.isfinite(p).all(axis=1)]
+    if len(p) == 0:
+        raise ValueError('no finite point')
+    return float(np.sqrt(((p - p.mean(axis=0)) ** 2).sum(axis=1).mean()))
+
+
+def global_correspondences(points, normals, vertices, faces, samples=None, k=32, seed=0,
+                           ctx=None):
+    """Steps 1 to 3 of ``global_register``: (src (M, 3), dst (M, 3), target (samples, 3)), the
+    matched pairs of the cloud and of ``samples`` surface samples of the mesh (as many as the
+    cloud has points when None) by nearest FPFH descriptor."""
+    from . import cloud
+    points = _points(points, 'points')
+    samples = len(points) if samples is None else int(samples)
+    target, face = sample_surface(vertices, faces, samples, seed)
+    fa, _, _ = cloud.fpfh(points, normals, k=k, ctx=ctx)
+    fb, _, _ = cloud.fpfh(target, face_normals(vertices, faces)[face], k=k, ctx=ctx)
+    idx, _ = cloud.match_features(fa, fb, ctx=ctx)
+    ok = idx >= 0
+    return points[ok], target[idx[ok]], target
+
+
+def global_register(points, normals, vertices, faces, samples=None, k=32, H=100000,
+                    inlier_dist=None, scale=None, with_scale=True, edge_tol=0.15, min_edge=0.0,
+                    candidates=32, keep=0.75, seed=0, refine=True, metric="plane", max_iter=50,
+                    index=None, ctx=None):
+    """The similarity (s, R, t) that brings an oriented cloud onto a mesh from any pose and
+    scale: a coarse, correspondence-based alignment that lands inside the basin of ``register``,
+    and with ``refine`` that refinement.
+
+    1. ``samples`` surface samples of the mesh (as many as the cloud has points when None, so
+       that both samplings are comparable) with their faces' normals;
+    2. ``cloud.fpfh`` on both (``normals`` must point to the side the faces' normals do);
+    3. ``cloud.match_features``, the cloud's descriptors against the samples';
+    4. ``ransac_similarity`` with ``H`` hypotheses; by default ``scale`` is (0.5, 2) x the ratio
+       of the two clouds' rms radii about their centroids (without an interval, collapsed
+       hypotheses win) and ``inlier_dist`` 0.03 x the diagonal of the mesh's box;
+    5. every candidate is verified by one ``MeshIndex.step(keep=keep, metric="point")`` of the
+       whole cloud against the mesh, and the one with the lowest trimmed rms is kept (the first
+       among equals): the correspondence count alone picks poses a half turn off;
+    6. with ``refine``, ``register(init=...)`` with the same ``keep``, ``metric``, ``with_scale``.
+
+    Returns dict(s, R, t, coarse (s, R, t), coarse_rms (c,), chosen, candidates (what
+    ``ransac_similarity`` returned), correspondences, scale, inlier_dist, registration (what
+    ``register`` returned, None without ``refine``)).  ValueError when no hypothesis survives the
+    gates."""
+    points = _points(points, 'points')
+    if len(points) < 3:
+        raise ValueError('points must hold at least three points')
+    own = index is None
+    if own:
+        index = MeshIndex(vertices, faces, ctx=ctx)
+    try:
+        src, dst, target = global_correspondences(points, normals, vertices, faces, samples, k,
+                                                  seed, ctx)
+        if len(src) < 3:
+            raise ValueError('fewer than three descriptors found a match')
+        if scale is None:
+            ratio = rms_radius(target) / rms_radius(points)
+            scale = (0.5 * ratio, 2.0 * ratio)
+        if inlier_dist is None:
+            inlier_dist = 0.03 * index.diagonal
+        cand = ransac_similarity(src, dst, H, inlier_dist, seed=seed, with_scale=with_scale,
+                                 scale=scale, edge_tol=edge_tol, min_edge=min_edge,
+                                 candidates=candidates, ctx=ctx)
+        if len(cand["h"]) == 0:
+            raise ValueError('no hypothesis survived the gates')
+        index.set_points(points)
+        rms = np.full(len(cand["h"]), np.inf)
+        for c in range(len(rms)):
+            rec = index.step(cand["s"][c], cand["R"][c], cand["t"][c], keep=keep, metric="point")
+            if rec["kept"] > 0:
+                rms[c] = step_rms("point", rec)
+        best = int(np.argmin(rms))
+        coarse = (float(cand["s"][best]), cand["R"][best].copy(), cand["t"][best].copy())
+        reg = None
+        if refine:
+            reg = _register(points, vertices, faces, metric=metric, keep=keep,
+                            with_scale=with_scale, init=coarse, max_iter=max_iter, index=index,
+                            ctx=ctx)
+    finally:
+        if own:
+            index.close()
+    s, R, t = (reg["s"], reg["R"], reg["t"]) if refine else coarse
+    return {"s": s, "R": R, "t": t, "coarse": coarse, "coarse_rms": rms, "chosen": best,
+            "candidates": cand, "correspondences": len(src), "scale": tuple(scale),
+            "inlier_dist": float(inlier_dist), "registration": reg}
 
 
 # ---- cameras (host only) ---------------------------------------------------------------------
